@@ -14,6 +14,12 @@ With N > 1 the trait axis is sharded (q/N traits per rank, same total problem: s
 scaling); the only data-path exchange is one all-reduce of p+8 doubles per sweep (+ 8
 doubles on ELBO sweeps).
 
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed sweeps and the
+JSON line (the roofline fields come from the library's own event timing of those sweeps).  --full adds
+the legs that take runs of their own: the CPU baseline and the ELBO-to-tol runs (N = 1 only;
+--no-cpu-baseline / --no-to-tol skip one of them).  --dump-outputs DIR writes the VB state the last
+timed sweep left as DIR/<name>.npy (dump_outputs), so that two builds can be compared output for output.
+
 Environment overrides for quick checks: AQ_BENCH_N / AQ_BENCH_P / AQ_BENCH_Q.
 """
 from __future__ import annotations
@@ -195,19 +201,74 @@ def cpu_baseline(n, p, q_total, seed=7, budget_s=10.0):
     return out
 
 
+DUMP_SAMPLE = 1 << 20      # sampled entries of each p x q matrix (3 x 8 MiB of float64)
+
+
+def dump_outputs(run, out_dir, k0, q_total, pg, seed=2024):
+    """Writes what a caller of VbRun.result(full_output=True) would receive after the last timed sweep, as float64 .npy files:
+    the p- and q-vectors in full, the scalars of the status, and of the three p x q matrices (4 GB each at the default size) the
+    same seeded sample of DUMP_SAMPLE (SNP, trait) entries, in column-major order (the whole matrix when it is smaller).  Each rank
+    fills in its own traits and a sum over the ranks assembles the rest, so the files do not depend on the rank count."""
+    import ctypes as C
+    import torch
+    import torch.distributed as dist
+    from atlasqtl_amd import _lib
+    L, p, q_loc = _lib.lib(), run.p, run.q
+    flat = np.sort(np.random.default_rng(seed).choice(p * q_total, size=min(DUMP_SAMPLE, p * q_total), replace=False))
+    rows, cols = flat % p, flat // p
+    mine = (cols >= k0) & (cols < k0 + q_loc)
+    loc = rows[mine] + p * (cols[mine] - k0)             # column-major index into this rank's p x q_loc block
+    host = np.empty(p * q_loc)                           # one staging buffer, reused for each matrix
+    nul = C.cast(None, _lib.dp)
+    sampled = {}
+    for i, name in enumerate(("beta_vb", "gam_vb", "mu_beta_vb")):
+        ptrs = [nul] * 3
+        ptrs[i] = _lib.as_dp(host)
+        _lib.check(L.aq_vb_get_result(run.h, *ptrs, nul, nul, nul, nul, nul, nul), "aq_vb_get_result")
+        sampled[name] = np.zeros(flat.size)
+        sampled[name][mine] = host[loc]
+    del host
+    vec = dict(theta_vb=np.zeros(p), zeta_vb=np.zeros(q_loc), lam2_inv_vb=np.zeros(p), sig2_theta_vb=np.zeros(p),
+               tau_vb=np.zeros(q_loc), sig2_beta_vb=np.zeros(q_loc))          # in the order of aq_vb_get_result's arguments
+    _lib.check(L.aq_vb_get_result(run.h, nul, nul, nul, *(_lib.as_dp(v) for v in vec.values())), "aq_vb_get_result")
+    for k in ("zeta_vb", "tau_vb", "sig2_beta_vb"):     # trait vectors in global position; the SNP vectors are the same on every rank
+        sampled[k] = np.zeros(q_total)
+        sampled[k][k0:k0 + q_loc] = vec.pop(k)
+    if pg is not None:
+        names = list(sampled)
+        t = torch.from_numpy(np.concatenate([sampled[k] for k in names])).cuda()
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=pg)
+        sampled = dict(zip(names, np.split(t.cpu().numpy(), np.cumsum([sampled[k].size for k in names])[:-1])))
+        if dist.get_rank(pg) != 0:
+            return
+    st = run.status()
+    out = dict(sampled, **vec, **{k: np.array([float(st[k])]) for k in ("it", "lb_opt", "diff_lb", "sig02_inv_vb", "sig2_inv_vb")})
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure (N = 1 only): the CPU baseline and the ELBO-to-tol runs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed sweeps, write the VB state they left as DIR/<name>.npy (float64, a seeded sample of the "
+                         "p x q matrices)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-to-tol", action="store_true",
-                    help="skip the ELBO-to-tol leg (N = 1 only): the reference's default run (tol 0.1, maxit 1000, anneal (1,2,10), "
-                         "thinned ELBO schedule) from loop entry to `converged`, on C2 (n=1000 p=5000 q=1000) and on the bench workload")
+                    help="with --full: skip the ELBO-to-tol leg (N = 1 only): the reference's default run (tol 0.1, maxit 1000, "
+                         "anneal (1,2,10), thinned ELBO schedule) from loop entry to `converged`, on C2 (n=1000 p=5000 q=1000) and on "
+                         "the bench workload")
     ap.add_argument("--to-tol-maxit", type=int, default=1000,
                     help="maxit of the ELBO-to-tol leg on the bench workload (the reference's default is 1000, R/atlasqtl.R:181; C3 "
                          "needs more sweeps than that for |dELBO| < 0.1 on an ELBO of -1.4e7: profiles/r03_elbo_to_tol_c3.json)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -273,6 +334,8 @@ def main():
     st1 = run.status()
     sweeps_done = st1["it"] - st0["it"]
     assert sweeps_done == args.steps, (sweeps_done, args.steps)
+    if args.dump_outputs:
+        dump_outputs(run, args.dump_outputs, k0, q, pg)
 
     if rank == 0:
         core_ms = (st1["core_ms"] - st0["core_ms"]) / max(st1["core_launches"] - st0["core_launches"], 1)
@@ -318,13 +381,13 @@ def main():
             rf["hbm_GBps"] = rf["traffic"] / (core_ms * 1e-3) / 1e9
             rf["hbm_peak_GBps"] = 8000.0
             rf["hbm_frac"] = rf["hbm_GBps"] / 8000.0
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(n, p, q)
             except Exception as e:  # the baseline is a report, never a reason to lose the measurement
                 out["cpu_baseline"] = {"value": None, "unit": "sweeps/s", "cores": 1, "kind": "port",
                                        "sample": f"failed: {e!r}"}
-        if world == 1 and not args.no_to_tol:
+        if args.full and world == 1 and not args.no_to_tol:
             # second half of BASELINE.json's metric: ELBO-to-tol wall-clock (loop entry -> converged; defaults of
             # R/atlasqtl.R:179-182).  C2 converges; the C3-sized workload reaches maxit = 1000 first (reported as such).
             run.close()
