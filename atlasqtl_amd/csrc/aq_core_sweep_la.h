@@ -156,9 +156,12 @@ constexpr int aq_req_issued(int D, int last, int t) {
 // is an agent-scope release (producer) / acquire (consumer) around done[k], and the wait is bounded.
 // MASK: Y with missing values (reference coreDualMisLoop, src/coreLoop.cpp:91-138): masked residual, per-trait Gram blocks and
 // per-entry sig2_beta_vb, the NA forms of the column sums (six rows).  One trait tile per workgroup only.
-template <int NT, int NT2, bool SEG, int TT, bool MASK = false, int NT3_ = -1>
+// WIDE: the wide sample split (9 <= C <= AQ_LA_CMAX parts, n > 10240): the partial S' are combined by split_exchange_wide
+// (reduce-scatter + all-gather) instead of every part reading every other part's words.  One tile per workgroup, unchained.
+template <int NT, int NT2, bool SEG, int TT, bool MASK = false, int NT3_ = -1, bool WIDE = false>
 __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCoreArgs a) {
   static_assert(!MASK || TT == 1, "the masked form keeps 16 per-trait Gram blocks in LDS: one trait tile per workgroup");
+  static_assert(!WIDE || (TT == 1 && !SEG), "the wide sample split: one trait tile per workgroup, never chained");
   constexpr int NWM = 6;                        // matrix waves: 0,1,2,4,5,6
   // residual tiles of the recurrence wave (its matrix work follows its chain): aq_la_nt3 unless the instance names its own count
   constexpr int NT3 = NT3_ >= 0 ? NT3_ : aq_la_nt3(NT, NT2, TT);
@@ -692,6 +695,90 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
     for (int r = 0; r < RPG; r++) own[r] = tot[r];
   };
 
+  // ---- wide sample split (WIDE, C > 8): the same contract as split_exchange -- on return own[] holds the sum over all parts,
+  // the same bits in every part, in an order that depends on C only -- at a cost per part that does not grow with C.
+  // Pbuf of a group and parity holds C + 1 slots of ENT words: slot c = part c's tagged partial, slot C = the tagged totals.
+  //   1. every part publishes its partial (4 words per lane);
+  //   2. reduce-scatter: part c owns the entries e = c, c + C, c + 2C, ... (ceil(256 / C) at most).  Lane i * nch + k of its wave
+  //      sums partners k pc .. k pc + pc - 1 of owned entry i in ascending order (nch chunks of pc partners: nch * ceil(256 / C)
+  //      <= 64, pc <= AQ_LA_WPC), all its words requested at once; lane i * nch then adds the nch chunk sums in ascending k;
+  //   3. the owner publishes the tagged total of each of its entries to slot C;
+  //   4. all-gather: every part reads the 256 tagged totals (4 words per lane) -- its own included, so every part uses the same bits.
+  // Per part and block that is four trips through the level the XCDs share whatever C is, and 3 C + 1 slot reads of traffic per
+  // group instead of C (C - 1).  Words validate themselves as in split_exchange (tag 1..3 in the two lowest mantissa bits, one per
+  // use of a parity slot, slots zeroed before every sweep).
+  // Slot lifetime.  Partials: part X overwrites its slot of block b with block b + 2 only after its exchange of b + 1 has read all
+  // totals of b + 1; each owner published those after reading every part's partial of b + 1, i.e. after its own exchange of b (and
+  // so its reads of partials of b) had ended.  Totals: owner O overwrites its totals of b with b + 2 only after reading every part's
+  // partial of b + 2, which each part publishes after its exchange of b + 1 -- so after it has read the totals of b.  A reader
+  // therefore meets only the previous or the expected tag in either kind of slot.
+  auto split_exchange_wide = [&](int b, double (&own)[RPG], auto meanwhile) __attribute__((always_inline)) {
+    static_assert(RPG == 4 && ENT == 256, "one trait tile per workgroup");
+    const int par = b & 1;
+    const unsigned long long tag = 1ull + (unsigned long long)(((b - seg_b0) >> 1) % 3);
+    unsigned long long *slots = (unsigned long long *)a.Pbuf + ((size_t)(wg * 2 + par) * (C + 1)) * ENT;
+    tl_mark(b - seg_b0 + 1, 2);   // (diag) exchange: publish
+#pragma unroll
+    for (int r = 0; r < RPG; r++)
+      __hip_atomic_store(&slots[(size_t)part * ENT + lane + 64 * r], ((unsigned long long)__double_as_longlong(own[r]) & ~3ull) | tag,
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    meanwhile();
+    const int cmax = (ENT + C - 1) / C, nch = 64 / cmax, pc = (C + nch - 1) / nch;
+    const int cnt = (ENT - 1 - part) / C + 1;            // entries owned by this part
+    const int i = lane / nch, k = lane - i * nch, c0 = k * pc;
+    const bool act = i < cnt && c0 < C;
+    const int e = part + C * i;
+    unsigned long long v[AQ_LA_WPC];
+    auto request = [&]() __attribute__((always_inline)) {
+#pragma unroll
+      for (int m = 0; m < AQ_LA_WPC; m++)
+        if (act && m < pc && c0 + m < C)
+          v[m] = __hip_atomic_load(&slots[(size_t)(c0 + m) * ENT + e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    request();
+    for (int spins = 0;;) {
+      bool ok = true;
+#pragma unroll
+      for (int m = 0; m < AQ_LA_WPC; m++)
+        if (act && m < pc && c0 + m < C) ok = ok && ((v[m] & 3ull) == tag);
+      if (__all(ok) || split_dead) break;
+      __builtin_amdgcn_s_sleep(1);
+      if (++spins > (1 << 22)) { *a.errflag = 1; split_dead = true; }   // give up for good: results are invalid
+      request();
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int m = 0; m < AQ_LA_WPC; m++)
+      if (act && m < pc && c0 + m < C) acc += __longlong_as_double((long long)v[m]);
+    tl_mark(b - seg_b0 + 1, 3);   // (diag) exchange: every part's partial of the owned entries has arrived
+    double tot = acc;
+    for (int kk = 1; kk < nch; kk++) {                   // chunk sums in ascending k (wave-uniform loop: every lane shuffles)
+      const double t = __shfl(acc, min(63, i * nch + kk), 64);
+      if (kk * pc < C) tot += t;
+    }
+    if (act && k == 0)
+      __hip_atomic_store(&slots[(size_t)C * ENT + e], ((unsigned long long)__double_as_longlong(tot) & ~3ull) | tag,
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned long long w4[RPG];
+    auto request_tot = [&]() __attribute__((always_inline)) {
+#pragma unroll
+      for (int r = 0; r < RPG; r++) w4[r] = __hip_atomic_load(&slots[(size_t)C * ENT + lane + 64 * r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    request_tot();
+    for (int spins = 0;;) {
+      bool ok = true;
+#pragma unroll
+      for (int r = 0; r < RPG; r++) ok = ok && ((w4[r] & 3ull) == tag);
+      if (__all(ok) || split_dead) break;
+      __builtin_amdgcn_s_sleep(1);
+      if (++spins > (1 << 22)) { *a.errflag = 1; split_dead = true; }
+      request_tot();
+    }
+#pragma unroll
+    for (int r = 0; r < RPG; r++) own[r] = __longlong_as_double((long long)w4[r]);
+    tl_mark(b - seg_b0 + 1, 4);   // (diag) exchange: all totals read
+  };
+
   __syncthreads();   // counters and the helper's LDS initialisation are visible to every role
   if (is_rec) {
     // =========================== recurrence wave ===========================================
@@ -780,7 +867,8 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
         bool corrected = false;
         if constexpr (!SEG && TT == 1) {
           if (C > 1 && !a.xhelper) {
-            split_exchange(b, Sown, [&]() __attribute__((always_inline)) { correction(std::false_type{}); });
+            if constexpr (WIDE) split_exchange_wide(b, Sown, [&]() __attribute__((always_inline)) { correction(std::false_type{}); });
+            else split_exchange(b, Sown, [&]() __attribute__((always_inline)) { correction(std::false_type{}); });
 #pragma unroll
             for (int r = 0; r < RPG; r++) Sown[r] -= cxs[r];
             corrected = true;
@@ -1190,9 +1278,11 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
     // chain of block b starts -- so the round trip through the shared cache level is off the recurrence wave's path
     auto exchange = [&](int b) __attribute__((always_inline)) {
       const int par = b & 1, kdone = b - seg_b0 + 1;
+      if constexpr (WIDE) tl_mark(kdone, 0);        // (diag) helper enters the exchange of block b
 #pragma unroll
       for (int m = 0; m < NWM; m++) wait_ge(m, kdone);
       if constexpr (NT3 > 0) wait_ge(11, kdone);   // the recurrence wave's own tiles
+      if constexpr (WIDE) tl_mark(kdone, 1);        // (diag) this part's S' of block b is complete
       double own[RPG];
 #pragma unroll
       for (int r = 0; r < RPG; r++) {
@@ -1202,7 +1292,8 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
         for (int ww = 1; ww < NPS; ww++) sv += Sp[par][ww][e];
         own[r] = sv;
       }
-      split_exchange(b, own, [] {});
+      if constexpr (WIDE) split_exchange_wide(b, own, [] {});
+      else split_exchange(b, own, [] {});
 #pragma unroll
       for (int r = 0; r < RPG; r++) Stot[par][lane + 64 * r] = own[r];
       signal(14, kdone);

@@ -602,3 +602,47 @@ __global__ __launch_bounds__(512) void aq_k_gk_blocks(const double *__restrict__
     }
   }
 }
+
+// ---- per-trait Gram blocks for the wide sample split (n > 10240): the same blocks as aq_k_gk_blocks, for any missingness ------
+// The index lists stay in global memory (int32, [ntile][16][Mmax], padded to groups of 16 with the all-zero row n_pad of XR), and
+// each trait uses the shorter of its two lists: obs[k] = 0 -- the missing samples, blocks = G - Xm' Xm as above; obs[k] = 1 -- the
+// observed samples, blocks = Xo' Xo directly.  Either way at most n / 2 rows per trait.  Once per handle.
+__global__ __launch_bounds__(512) void aq_k_gk_blocks_g(const double *__restrict__ XR, const double *__restrict__ G,
+                                                      const double *__restrict__ Gx, const int *__restrict__ midx,
+                                                      const int *__restrict__ mcnt4, const int *__restrict__ obs,
+                                                      double *__restrict__ GK, int nb, int NR, int Mmax, int bchunk) {
+  const int tile = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, col = lane & 15;
+  const int b0 = blockIdx.x * bchunk, b1 = min(nb, b0 + bchunk);
+  for (int b = b0; b < b1; b++) {
+    double *out = GK + ((size_t)tile * nb + b) * AQ_GK_STRIDE;
+    const double *xr = XR + (size_t)b * NR * 16 + col;
+    const double *xp = XR + (size_t)(b > 0 ? b - 1 : 0) * NR * 16 + col;
+    for (int job = w; job < 32; job += 8) {
+      const int k = job & 15, cross = job >> 4;
+      const bool direct = obs[tile * 16 + k] != 0;
+      aq_d4 acc = (aq_d4){0, 0, 0, 0};
+      const int n4 = (cross && b == 0) ? 0 : mcnt4[tile * 16 + k];
+      const int *ix = midx + ((size_t)tile * 16 + k) * Mmax + g;
+      for (int t = 0; t < n4; t += 4) {
+        const int i0 = ix[4 * t], i1 = ix[4 * t + 4], i2 = ix[4 * t + 8], i3 = ix[4 * t + 12];
+        const double a0 = xr[(size_t)i0 * 16], a1 = xr[(size_t)i1 * 16], a2 = xr[(size_t)i2 * 16], a3 = xr[(size_t)i3 * 16];
+        if (cross) {
+          const double c0 = xp[(size_t)i0 * 16], c1 = xp[(size_t)i1 * 16], c2 = xp[(size_t)i2 * 16], c3 = xp[(size_t)i3 * 16];
+          acc = aq_mfma(a0, c0, acc); acc = aq_mfma(a1, c1, acc); acc = aq_mfma(a2, c2, acc); acc = aq_mfma(a3, c3, acc);
+        } else {
+          acc = aq_mfma(a0, a0, acc); acc = aq_mfma(a1, a1, acc); acc = aq_mfma(a2, a2, acc); acc = aq_mfma(a3, a3, acc);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int i = 4 * r + g, j = col;            // D layout: row = 4 reg + (lane >> 4), column = lane & 15
+        if (cross) {
+          const double base = (b > 0 && !direct) ? Gx[(size_t)b * 256 + i * 16 + j] : 0.0;
+          out[AQ_GK_DIAG + (i * 16 + j) * 16 + k] = direct ? (b > 0 ? acc[r] : 0.0) : base - acc[r];
+        } else if (i >= j) {
+          out[(i * (i + 1) / 2 + j) * 16 + k] = direct ? acc[r] : G[(size_t)b * 256 + i * 16 + j] - acc[r];
+        }
+      }
+    }
+  }
+}

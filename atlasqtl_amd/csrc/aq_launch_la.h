@@ -15,3 +15,7 @@ int aq_la_launch_tt2(int NT, int NT2, int nt3x, bool seg, unsigned grid, hipStre
 // the MASK instances (Y with missing values; one trait tile per workgroup): aq_launch_la1m.hip
 // nt3x = 3: three residual tiles on the recurrence wave (NT2 == NT, NT in 8..11); -1: none
 int aq_la_launch_mask(int NT, int NT2, int nt3x, bool seg, unsigned grid, hipStream_t st, const AqCoreArgs &a);
+// the wide sample split (9 <= C <= AQ_LA_CMAX parts, n > 10240; NT2 == NT, unchained): aq_launch_la1w.hip (complete Y) and
+// aq_launch_la1wm.hip (MASK).  Returns -1 when NT is outside 1..18.
+int aq_la_launch_wide(int NT, unsigned grid, hipStream_t st, const AqCoreArgs &a);
+int aq_la_launch_wide_mask(int NT, unsigned grid, hipStream_t st, const AqCoreArgs &a);

@@ -147,6 +147,7 @@ struct aq_vb {
   int laC = 1;           // look-ahead kernel: workgroups (sample parts) per trait group, n > 1056
   int max_missing = 0;   // most missing samples of one trait
   bool la_mask = false;  // look-ahead kernel, MASK instances: Y with missing values, per-trait Gram blocks precomputed into GK
+  bool la_wide = false;  // look-ahead kernel, wide sample split (9 <= laC <= AQ_LA_CMAX; n > 10240 or AQ_LA_C >= 9)
   double *GK = nullptr;  // [ntile][nb][AQ_GK_STRIDE]
   int TT = 1;            // look-ahead kernel: 16-trait tiles per workgroup (2 when there are enough tiles to fill the chip)
   int stagger = 0;       // look-ahead kernel: tile at which a matrix wave releases its SIMD partner into the phase (0 = off)
@@ -158,6 +159,7 @@ struct aq_vb {
   bool use_mis = false;  // masked blocked MFMA kernel (aq_core_sweep_mis.h): missing Y, n <= 2048
   double *XR = nullptr;  // [nb][NR][16] row-major SNP panels (gather source of the per-trait Gram corrections)
   int *midx = nullptr, *mcnt4 = nullptr;   // per-trait lists of missing samples
+  int *mobs = nullptr;   // wide split: 1 = the trait's list holds its observed samples (the shorter list), aq_k_gk_blocks_g
   int Mmax = 0, NR = 0;
   int misC = 1;          // masked kernel: workgroups (sample parts) per trait tile
   double *Pbuf = nullptr, *rnpart = nullptr;
@@ -219,7 +221,7 @@ static const char *aq_env(aq_vb *s, const char *name) {
 static void aq_free_all(aq_vb *s) {
   if (!s) return;
   hipSetDevice(s->device);
-  void *ptrs[] = {s->GK, s->Pbuf, s->rnpart, s->pflag, s->XR, s->midx, s->mcnt4, s->Xcm, s->mis, s->XN, s->XA, s->XU, s->G, s->Gx, s->R, s->gam, s->mu, s->theta, s->sig2_theta, s->L, s->lam2_inv, s->Q, s->ppart,
+  void *ptrs[] = {s->mobs, s->GK, s->Pbuf, s->rnpart, s->pflag, s->XR, s->midx, s->mcnt4, s->Xcm, s->mis, s->XN, s->XA, s->XU, s->G, s->Gx, s->R, s->gam, s->mu, s->theta, s->sig2_theta, s->L, s->lam2_inv, s->Q, s->ppart,
                   s->eta_h, s->kappa_h, s->n0, s->nobs, s->zeta, s->tau, s->sig2b, s->log_tau, s->eta_vb, s->kappa_vb,
                   s->coef, s->inv2s, s->cst, s->sums, s->rowA, s->rowGB, s->Aarr, s->Barr, s->colApart, s->Hpart, s->sc};
   for (void *ptr : ptrs)
@@ -337,7 +339,7 @@ static int aq_launch_core(aq_vb *s, int mode, double c) {
     a.sig2_inv_p = &s->sc->sig2_inv; a.log_sig2_inv_p = &s->sc->log_sig2_inv;
     if (s->laC > 1 && (!a.Pbuf || !a.rnpart || !a.errflag)) return aq_fail(AQ_ERR_DEVICE, "sample split without its exchange buffers");
     if (s->laC > 1 && mode == 0)   // the exchange slots start with tag 0 (aq_core_sweep_la.h, split_exchange)
-      AQ_HIP(hipMemsetAsync(s->Pbuf, 0, (size_t)s->ntile * 2 * s->laC * 256 * sizeof(double), 0));
+      AQ_HIP(hipMemsetAsync(s->Pbuf, 0, (size_t)s->ntile * 2 * (s->laC + (s->la_wide ? 1 : 0)) * 256 * sizeof(double), 0));
     a.dbg = nullptr;
     static long long *dbg_buf = nullptr;   // AQ_DIAG_DUMP=<file> with a -DAQ_DIAG_TIME build: per-role wait / total cycles of sweep 15
     const char *dump = getenv("AQ_DIAG_DUMP");
@@ -360,7 +362,8 @@ static int aq_launch_core(aq_vb *s, int mode, double c) {
     const unsigned grid = chained ? (unsigned)((long long)s->chain * nwg) : nwg * (unsigned)s->laC;
     // One instance per handle for annealed and post-annealing sweeps alike: with the probit tables an annealed entry costs the
     // same three polynomials as any other (round 2 swapped to a (NT, NT, 3) geometry for the annealed sweeps).
-    int lrc = s->la_mask ? aq_la_launch_mask(s->NT, s->NT2, s->NT3x, chained, grid, 0, a)
+    int lrc = s->la_wide ? (s->la_mask ? aq_la_launch_wide_mask(s->NT, grid, 0, a) : aq_la_launch_wide(s->NT, grid, 0, a))
+              : s->la_mask ? aq_la_launch_mask(s->NT, s->NT2, s->NT3x, chained, grid, 0, a)
               : s->TT == 2 ? aq_la_launch_tt2(s->NT, s->NT2, s->NT3x, chained, grid, 0, a) : aq_la_launch_tt1(s->NT, s->NT2, s->NT3x, chained, grid, 0, a);
     if (lrc != 0) return aq_fail(AQ_ERR_UNSUPPORTED, "no look-ahead kernel instantiation for this n");
     if (chained) {
@@ -461,8 +464,9 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
   }
   bool has_missing = false;
   for (size_t i = 0; i < nq && !has_missing; i++) has_missing = !(Yh[i] == Yh[i]);
-  if (pr->n > 10240)
-    return aq_fail(AQ_ERR_UNSUPPORTED, "n > 10240: a trait's residual no longer fits the registers of 4 waves (not implemented yet)");
+  if (pr->n > AQ_N_MAX)
+    return aq_fail(AQ_ERR_UNSUPPORTED, "n = " + std::to_string(pr->n) + " exceeds the largest supported sample count, n <= " +
+                                           std::to_string(AQ_N_MAX) + " (AQ_N_MAX, the wide sample split)");
 
   aq_vb *s = new aq_vb();
   s->device = pr->device;
@@ -496,7 +500,17 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
     // SNP block, computed once) fit next to the rest of the state in HBM; else the masked two-barrier kernel (AQ_KERNEL=3
     // forces that one), which recomputes them every sweep.  Complete Y beyond n = 1056: look-ahead kernel with a sample split.
     const bool n_la_ok = pr->n <= 8 * 16 * 105;
+    // n > 10240 (or AQ_LA_C = 9 ... AQ_LA_CMAX, test hook): the look-ahead kernel's wide sample split, complete Y or MASK with the
+    // Gram blocks of aq_k_gk_blocks_g (any missingness); no other kernel serves this n
+    const char *ecw = aq_env(s, "AQ_LA_C");
+    const bool wide = pr->n > 10240 || (ecw && atoi(ecw) >= 9);
+    if (wide && ecw && (atoi(ecw) > AQ_LA_CMAX || (pr->n > 10240 && atoi(ecw) < 9))) {
+      delete s;
+      return aq_fail(AQ_ERR_ARG, "AQ_LA_C: the wide sample split takes 9 ... " + std::to_string(AQ_LA_CMAX) + " parts");
+    }
+    if (wide && ek && atoi(ek) >= 2) { delete s; return aq_fail(AQ_ERR_UNSUPPORTED, "AQ_KERNEL: only the look-ahead kernel serves n > 10240"); }
     bool la_mask_ok = has_missing && n_la_ok && max_missing <= AQ_MIS_MMAX && !(ek && atoi(ek) >= 2);
+    if (wide) la_mask_ok = has_missing;
     if (la_mask_ok) {
       size_t free_b = 0, tot_b = 0;
       const size_t ntile_ = (size_t)(pr->q + 15) / 16, nb_ = (size_t)(pr->p + 15) / 16;
@@ -506,11 +520,24 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
       // decided on the device's TOTAL memory (minus a tenth), not on what happens to be free: the same problem gets the same
       // kernel on every rank and in every run, so a checkpoint of one is accepted by the other.  Should the allocation then fail
       // because other processes hold memory, aq_vb_create reports the out-of-memory error (AQ_GK_MAX_GB lowers the limit).
-      if (hipMemGetInfo(&free_b, &tot_b) != hipSuccess || (double)(gk_b + rest_b) * 1.05 > 0.9 * (double)tot_b) la_mask_ok = false;
+      const hipError_t mrc = hipMemGetInfo(&free_b, &tot_b);
+      if (wide && mrc != hipSuccess) {
+        delete s;
+        return aq_fail(AQ_ERR_DEVICE, std::string("hipMemGetInfo: ") + hipGetErrorString(mrc));
+      }
+      // (the wide split sizes its whole budget, with its own n_pad, before allocating: see "device memory of the wide split" below)
+      if (mrc != hipSuccess || (!wide && (double)(gk_b + rest_b) * 1.05 > 0.9 * (double)tot_b)) la_mask_ok = false;
       if (const char *e = aq_env(s, "AQ_GK_MAX_GB")) if ((double)gk_b > atof(e) * 1e9) la_mask_ok = false;   // test hook: force the fallback
+      if (wide && !la_mask_ok) {   // AQ_GK_MAX_GB: no fallback kernel at this n
+        char msg[256];
+        snprintf(msg, sizeof msg, "Y with missing values at n = %d: the per-trait Gram blocks need %.1f GB of device memory, which does not "
+                 "fit; shard the traits (fewer traits per device)", pr->n, (double)gk_b / 1e9);
+        delete s;
+        return aq_fail(AQ_ERR_UNSUPPORTED, msg);
+      }
     }
-    const bool la_split_ok = !has_missing && pr->n > 1056 && n_la_ok && !(ek && atoi(ek) >= 2);   // complete Y, large n
-    if (!la_mask_ok && (has_missing || (pr->n > 1056 && !la_split_ok)) && pr->n <= 16384 && max_missing <= AQ_MIS_MMAX && !(ek && atoi(ek) == 2)) {
+    const bool la_split_ok = (!has_missing && pr->n > 1056 && n_la_ok && !(ek && atoi(ek) >= 2)) || (wide && !has_missing);   // complete Y, large n
+    if (!wide && !la_mask_ok && (has_missing || (pr->n > 1056 && !la_split_ok)) && pr->n <= 16384 && max_missing <= AQ_MIS_MMAX && !(ek && atoi(ek) == 2)) {
       s->use_mis = true;
       s->NW = 8;
       // n_pad = 128 NT C: C workgroups per trait tile, NT in {1,2,4,8,16} residual tiles per wave.  Model of a sweep:
@@ -536,7 +563,7 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
       }
       s->Mmax = (max_missing + 15) / 16 * 16;
       if (s->Mmax < 16) s->Mmax = 16;
-    } else if ((has_missing && !la_mask_ok) || (ek && atoi(ek) == 2) || (pr->n > 1056 && !la_split_ok && !la_mask_ok)) {
+    } else if (!wide && ((has_missing && !la_mask_ok) || (ek && atoi(ek) == 2) || (pr->n > 1056 && !la_split_ok && !la_mask_ok))) {
       // generic kernel geometry: n_pad = 64 * NE * WPT samples, WPT waves (and workgroups) per trait (tile)
       s->use_tw = true;
       s->WPT = pr->n <= 2048 ? 1 : pr->n <= 5120 ? 2 : 4;
@@ -640,7 +667,7 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
           s->TT = 1; s->q_pad = (pr->q + 15) / 16 * 16; s->ntile = s->q_pad / 16; s->stagger = 0;
           double best = 1e300;
           const char *ec = aq_env(s, "AQ_LA_C");
-          for (int C = 2; C <= 8; C++) {
+          for (int C = 2; C <= 8 && !wide; C++) {
             if (ec && atoi(ec) != C) continue;
             int NT = 0, NT2 = 0, N3x = -1;
             const int tiles = fit((ntiles + C - 1) / C, 18, &NT, &NT2, &N3x);
@@ -649,11 +676,31 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
             const double cost = rounds * std::max(0.213 * (NT + NT2) + 1.0, 4.5 + 0.2 * (C - 2));
             if (cost < best - 1e-9) { best = cost; s->laC = C; s->NT = NT; s->NT2 = NT2; s->NT3x = N3x; s->n_pad = 16 * tiles * C; }
           }
+          if (wide) {
+            // the wide split (aq_launch_la1w.hip): C = 9 ... AQ_LA_CMAX parts of 6 NT residual tiles (NT2 = NT, none on the recurrence
+            // wave), the exchange a block ahead on the helper wave.  Same model: rounds of workgroups x time per SNP block, here
+            // max(MFMA stream of one SIMD, helper wave), because the exchange runs on the helper wave next to its own per-block work
+            // (staging, column sums) and adds to it.  Measured (timelines of workgroup 0, profiles/large_n_timeline.txt, n = 20 480):
+            // helper period 8.5 us at C = 12, 10.9 us at C = 29 (exchange 3.7 -> 6.3 us, the rest 4.6 - 4.9 us) -> 8.5 + 0.14 (C - 12).
+            // (Not modelled: at n = 50 000 the operand stream of the matrix waves and the exchange are both slower)
+            auto helper_us = [](int C) { return 8.5 + 0.14 * (C - 12); };
+            s->la_wide = true;
+            const int cf = ec ? atoi(ec) : 0;
+            for (int C = 9; C <= AQ_LA_CMAX && C <= s->ncu; C++) {
+              if (cf >= 9 && C != cf) continue;
+              const int NT = ((ntiles + C - 1) / C + 5) / 6;
+              if (NT > 18) continue;
+              const double rounds = (double)(((long long)s->ntile * C + s->ncu - 1) / s->ncu);
+              const double cost = rounds * std::max(0.213 * 2 * NT + 1.0, helper_us(C));
+              if (cost < best - 1e-9) { best = cost; s->laC = C; s->NT = NT; s->NT2 = NT; s->NT3x = -1; s->n_pad = 16 * 6 * NT * C; }
+            }
+            s->la_xhelper = 1;
+          }
           if (best >= 1e300) { delete s; return aq_fail(AQ_ERR_UNSUPPORTED, "no look-ahead geometry for this n"); }
           // Who exchanges the partial S': the recurrence wave at the start of its chain.  The helper wave can do it a block ahead
           // (AQ_LA_XHELPER=1); that paid at n = 5000 while an exchange was three trips through the shared cache (236 vs 225 ms),
           // with self-validating words it no longer does (222.5 vs 222.0; n = 1500: 58.3 vs 64.5).
-          s->la_xhelper = 0;
+          if (!wide) s->la_xhelper = 0;
         }
         if (const char *e = aq_env(s, "AQ_LA_XHELPER")) s->la_xhelper = atoi(e) != 0;   // test hook
         if (const char *e = aq_env(s, "AQ_XTOUCH")) s->la_xtouch = atoi(e) != 0;
@@ -730,6 +777,35 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
 #define AQ_TRYF(x) do { int rc2_ = (x); if (rc2_ != AQ_OK) return fail(rc2_); } while (0)
 #define AQ_HIPF(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { aq_fail(AQ_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); return fail(AQ_ERR_DEVICE); } } while (0)
 
+  if (s->la_wide) {
+    if (s->la_mask) {   // aq_k_gk_blocks_g: per trait the shorter of the missing and the observed list
+      int mm = 0;
+      for (int k = 0; k < s->q; k++) {
+        int m = 0;
+        for (int i = 0; i < s->n; i++) m += !(Yh[(size_t)i + (size_t)s->n * k] == Yh[(size_t)i + (size_t)s->n * k]);
+        mm = std::max(mm, std::min(m, s->n - m));
+      }
+      s->Mmax = (mm + 15) / 16 * 16;
+    }
+    if (s->Mmax < 16) s->Mmax = 16;
+    // device memory of the wide split: the X operand panels (XA, XU: n_pad p 8 B each), residual and mask tiles, and with missing
+    // values the Gram blocks plus, while they are built, the row panels XR and the index lists.  No other kernel serves this n:
+    // fail here, before anything is allocated, when it cannot fit.
+    size_t free_b = 0, tot_b = 0;
+    const double xb = 2.0 * (double)s->nb * (s->n_pad / 16) * 128 * sizeof(double);
+    const double rb = (s->la_mask ? 2.0 : 1.0) * (double)s->ntile * s->n_pad * 16 * sizeof(double);
+    const double gb = s->la_mask ? (double)s->ntile * s->nb * AQ_GK_STRIDE * sizeof(double) + (double)s->nb * (s->n_pad + 8) * 16 * sizeof(double) +
+                                       (double)s->ntile * 16 * s->Mmax * sizeof(int)
+                                 : 0.0;
+    if (hipMemGetInfo(&free_b, &tot_b) != hipSuccess) { delete s; return aq_fail(AQ_ERR_DEVICE, "hipMemGetInfo failed"); }
+    if ((xb + rb + gb) * 1.05 > 0.9 * (double)tot_b) {
+      char msg[256];
+      snprintf(msg, sizeof msg, "n = %d, p = %d, q = %d: the wide sample split needs %.1f GB of device memory, more than the device holds; "
+               "shard the traits (fewer traits per device)", s->n, s->p, s->q, (xb + rb + gb) * 1.05 / 1e9);
+      delete s;
+      return aq_fail(AQ_ERR_UNSUPPORTED, msg);
+    }
+  }
   const int NTT = s->n_pad / 16;
   size_t xelems = s->use_tw ? 1 : (size_t)s->nb * NTT * 128;
   AQ_TRYF(aq_dalloc(&s->XA, xelems));
@@ -741,7 +817,7 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
     AQ_TRYF(aq_dalloc(&s->XN, (size_t)s->ntile * s->p_pad * 16));
   }
   if (s->la_mask) {
-    s->Mmax = (s->max_missing + 15) / 16 * 16;
+    if (!s->la_wide) s->Mmax = (s->max_missing + 15) / 16 * 16;
     if (s->Mmax < 16) s->Mmax = 16;
     s->NR = s->n_pad + 8;
   }
@@ -756,19 +832,32 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
       AQ_TRYF(aq_dalloc(&s->rnpart, (size_t)s->misC * s->q_pad));
     }
     // lists of missing samples per trait, padded to groups of 16 with the all-zero row n_pad of XR
-    std::vector<int> idx((size_t)s->ntile * 16 * s->Mmax, s->n_pad), cnt((size_t)s->ntile * 16, 0);
+    std::vector<int> idx((size_t)s->ntile * 16 * s->Mmax, s->n_pad), cnt((size_t)s->ntile * 16, 0), obs((size_t)s->ntile * 16, 0);
     for (int k = 0; k < s->q; k++) {
       int m = 0;
       int *dst = idx.data() + (size_t)k * s->Mmax;      // trait k = tile (k / 16), slot (k % 16): contiguous
-      for (int i = 0; i < s->n; i++)
-        if (!(Yh[(size_t)i + (size_t)s->n * k] == Yh[(size_t)i + (size_t)s->n * k])) dst[m++] = i;
+      const double *yk = Yh + (size_t)s->n * k;
+      int mk = 0;
+      if (s->la_wide) for (int i = 0; i < s->n; i++) mk += !(yk[i] == yk[i]);
+      if (s->la_wide && 2 * mk > s->n) {   // wide split: more missing than observed -- list the observed samples
+        obs[k] = 1;
+        for (int i = 0; i < s->n; i++)
+          if (yk[i] == yk[i]) dst[m++] = i;
+      } else {
+        for (int i = 0; i < s->n; i++)
+          if (!(yk[i] == yk[i])) dst[m++] = i;
+      }
       cnt[k] = (m + 15) / 16 * 4;
+    }
+    if (s->la_wide) {
+      AQ_TRYF(aq_dalloc(&s->mobs, obs.size()));
+      AQ_HIPF(hipMemcpy(s->mobs, obs.data(), obs.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     AQ_HIPF(hipMemcpy(s->midx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
     AQ_HIPF(hipMemcpy(s->mcnt4, cnt.data(), cnt.size() * sizeof(int), hipMemcpyHostToDevice));
   }
   if (s->use_la && s->laC > 1) {
-    AQ_TRYF(aq_dalloc(&s->Pbuf, (size_t)s->ntile * 2 * s->laC * 256));
+    AQ_TRYF(aq_dalloc(&s->Pbuf, (size_t)s->ntile * 2 * (s->laC + (s->la_wide ? 1 : 0)) * 256));   // wide: + the slot of the totals
     AQ_TRYF(aq_dalloc(&s->pflag, (size_t)s->ntile * s->laC));
     AQ_TRYF(aq_dalloc(&s->rnpart, (size_t)s->laC * s->q_pad));
   }
@@ -832,6 +921,10 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
         AQ_TRYF(aq_dalloc(&s->GK, (size_t)s->ntile * s->nb * AQ_GK_STRIDE));
         const int bchunk = 32;
         const size_t lds = (size_t)16 * s->Mmax * sizeof(unsigned short);
+        if (s->la_wide)   // lists of any length, from global memory (aq_core_sweep_mis.h::aq_k_gk_blocks_g)
+          hipLaunchKernelGGL(aq_k_gk_blocks_g, dim3((s->nb + bchunk - 1) / bchunk, s->ntile), dim3(512), 0, 0, s->XR, s->G, s->Gx, s->midx,
+                             s->mcnt4, s->mobs, s->GK, s->nb, s->NR, s->Mmax, bchunk);
+        else
         hipLaunchKernelGGL(aq_k_gk_blocks, dim3((s->nb + bchunk - 1) / bchunk, s->ntile), dim3(512), lds, 0, s->XR, s->G, s->Gx, s->midx, s->mcnt4,
                            s->GK, s->nb, s->NR, s->Mmax, bchunk);
         AQ_HIPF(hipGetLastError());

@@ -131,6 +131,9 @@ typedef struct aq_vb_problem {
  * [ rowSums(Z) (p padded to 16) , sum(gam) , sum_k tau_k colSums(m2)_k , sum(zeta) , 5 spare ]. */
 int64_t aq_vb_reduce_len(int32_t p);
 
+/* Creates the device state of one VB run.  n may be at most 82 944 (AQ_N_MAX): beyond 10 240 samples the sweep runs as the
+ * wide sample split of the look-ahead kernel (9 ... 48 workgroups per trait group); larger n, or a problem whose operand panels
+ * or per-trait Gram blocks (Y with missing values) do not fit in device memory, is AQ_ERR_UNSUPPORTED with the reason. */
 int aq_vb_create(const aq_vb_problem *prob, aq_vb_handle *out);
 void aq_vb_destroy(aq_vb_handle h);
 
