@@ -60,6 +60,9 @@ class AqVbStatus(C.Structure):
         ("core_launches", C.c_int32), ("sig02_inv_vb", C.c_double), ("sig2_inv_vb", C.c_double),
         ("lentz_iters", C.c_int32), ("core_kernel", C.c_int32), ("split_parts", C.c_int32),
         ("tiles_per_group", C.c_int32), ("chain_segments", C.c_int32),
+        # the launched instance of the core kernel (appended fields): NT, NT2, NT3, flags (1 MASK, 2 WIDE, 4 chained), padded n
+        ("tiles_matrix", C.c_int32), ("tiles_matrix2", C.c_int32), ("tiles_recurrence", C.c_int32),
+        ("instance_flags", C.c_int32), ("n_pad", C.c_int32),
     ]
 
 

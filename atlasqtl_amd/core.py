@@ -580,7 +580,10 @@ def atlasqtl_global_local_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, verbo
         if full_output:
             res.update(sig02_inv_vb=st["sig02_inv_vb"], sig2_inv_vb=st["sig2_inv_vb"], elbo_trace=(its, lbs),
                        core_ms=st["core_ms"], core_launches=st["core_launches"], lentz_iters=st["lentz_iters"],
-                       core_kernel=st["core_kernel"])
+                       core_kernel=st["core_kernel"],
+                       # the launched instance of the core kernel (aq_vb_status)
+                       **{k: st[k] for k in ("split_parts", "tiles_matrix", "tiles_matrix2", "tiles_recurrence",
+                                             "instance_flags", "n_pad")})
         return res
     finally:
         run.close()

@@ -1482,6 +1482,12 @@ extern "C" int aq_vb_get_status(aq_vb_handle s, aq_vb_status *st) {
   st->split_parts = s->use_la ? s->laC : s->use_mis ? s->misC : 1;
   st->tiles_per_group = s->use_la ? s->TT : 1;
   st->chain_segments = s->chain > 1 ? s->chain : 0;
+  // the instance aq_launch_core dispatches to (aq_launch_la.h): a wide instance has NT2 == NT and no tiles on the recurrence wave
+  st->tiles_matrix = (s->use_la || s->use_mis) ? s->NT : 0;
+  st->tiles_matrix2 = s->use_la ? s->NT2 : 0;
+  st->tiles_recurrence = (s->use_la && !s->la_wide) ? (s->NT3x > 0 ? s->NT3x : aq_la_nt3(s->NT, s->NT2, s->TT)) : 0;
+  st->instance_flags = s->use_la ? (s->la_mask ? 1 : 0) | (s->la_wide ? 2 : 0) | (s->chain > 1 ? 4 : 0) : 0;
+  st->n_pad = s->n_pad;
   return AQ_OK;
 }
 

@@ -206,6 +206,14 @@ typedef struct aq_vb_status {
   int32_t split_parts;   /* launch plan of the core kernel: workgroups sharing one trait group along the samples (1 = none), */
   int32_t tiles_per_group;   /* 16-trait tiles per workgroup (1 or 2),                                                  */
   int32_t chain_segments;    /* chained SNP segments per trait group (0 = none)                                         */
+  /* Which template instance of the core kernel the handle launches (appended; the fields above keep their offsets).  For the
+   * look-ahead kernel (core_kernel 0) the residual-tile geometry NT / NT2 / NT3; the masked two-barrier kernel (3) reports its
+   * own NT (residual tiles per wave) in tiles_matrix and 0 in the other two; the generic kernel (2) reports 0 in all three. */
+  int32_t tiles_matrix;      /* NT: residual tiles of matrix waves 0-2                                                   */
+  int32_t tiles_matrix2;     /* NT2: residual tiles of matrix waves 4-6 (NT or NT - 1)                                   */
+  int32_t tiles_recurrence;  /* NT3: residual tiles on the recurrence wave, as the launched instance has them             */
+  int32_t instance_flags;    /* look-ahead kernel: bit 0 MASK (Y with NA), bit 1 WIDE (9 ... 48 sample parts), bit 2 chained (SEG) */
+  int32_t n_pad;             /* samples after padding: 16 x the residual tiles of all parts                              */
 } aq_vb_status;
 int aq_vb_get_status(aq_vb_handle h, aq_vb_status *st);
 

@@ -24,6 +24,25 @@ def test_header_and_binding_agree():
     assert set(names) == set(_lib.SYMBOLS), (set(names) ^ set(_lib.SYMBOLS))
 
 
+def test_status_struct_and_binding_agree():
+    """aq_vb_status field by field against its ctypes mirror: same names, same order, same C types -- the plan and instance
+    fields were appended, so the fields that came before keep their offsets."""
+    txt = open(os.path.join(ROOT, "include", "atlasqtl_hip.h")).read()
+    body = re.search(r"typedef struct aq_vb_status \{(.*?)\} aq_vb_status;", txt, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    ctype = {"int32_t": C.c_int32, "double": C.c_double}
+    fields = []
+    for decl in body.split(";"):
+        if decl.strip():
+            typ, names = decl.split(None, 1)
+            fields += [(nm.strip(), ctype[typ]) for nm in names.split(",")]
+    assert fields == list(_lib.AqVbStatus._fields_)
+    names = [f[0] for f in fields]
+    assert names[12:16] == ["core_kernel", "split_parts", "tiles_per_group", "chain_segments"]
+    assert names[16:] == ["tiles_matrix", "tiles_matrix2", "tiles_recurrence", "instance_flags", "n_pad"]
+    assert _lib.AqVbStatus.chain_segments.offset == 88 and C.sizeof(_lib.AqVbStatus) == 112
+
+
 def test_library_exports_every_declared_symbol(hiplib):
     for name in declared_functions():
         assert hasattr(hiplib, name), name

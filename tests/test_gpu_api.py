@@ -339,6 +339,49 @@ def test_launch_plan_follows_the_problem_shape(monkeypatch):
     assert plan(1000, 64, 24) == (0, 1, 1, 0)
 
 
+def test_status_names_the_launched_instance(monkeypatch):
+    """aq_vb_status names the template instance the plan launches: NT / NT2 / NT3 and the MASK, WIDE and chained flags of the
+    look-ahead kernel (63 residual tiles at n = 1000: 9 / 9 / 9 with two trait tiles per workgroup, 10 / 9 / 6 with one); the
+    masked two-barrier kernel reports its own NT, the generic kernel zeros; the result dict carries the same fields."""
+    import atlasqtl_amd as A
+    from tests.util import make_problem
+
+    def instance(prob, **env):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        run = _vbrun(prob)
+        st = run.status()
+        run.close()
+        for k in env:
+            monkeypatch.delenv(k)
+        return st
+
+    def geometry(st):
+        return st["tiles_matrix"], st["tiles_matrix2"], st["tiles_recurrence"], st["instance_flags"], st["n_pad"]
+
+    prob = make_problem(1000, 150, 40, p_act=8, prob_assoc=0.3)
+    st = instance(prob, AQ_TT="2", AQ_NT3="9", AQ_CHAIN="3", AQ_LA_NOSPLIT="1")
+    assert (st["core_kernel"], st["tiles_per_group"], st["chain_segments"]) == (0, 2, 3)
+    assert geometry(st) == (9, 9, 9, 4, 1008)
+    st = instance(prob, AQ_TT="1", AQ_NT3="6", AQ_CHAIN="0", AQ_LA_NOSPLIT="1")
+    assert (st["core_kernel"], st["split_parts"], st["tiles_per_group"]) == (0, 1, 1)
+    assert geometry(st) == (10, 9, 6, 0, 1008)
+    na = make_problem(300, 130, 49, p_act=8, prob_assoc=0.3, na_frac=0.04)
+    st = instance(na)
+    assert st["core_kernel"] == 0 and st["instance_flags"] == 1 and st["tiles_recurrence"] == 0
+    assert st["n_pad"] == 16 * 3 * (st["tiles_matrix"] + st["tiles_matrix2"]) >= 300
+    st = instance(na, AQ_KERNEL="3")
+    assert st["core_kernel"] == 3 and st["tiles_matrix"] in (1, 2, 4, 8, 16)
+    assert geometry(st) == (st["tiles_matrix"], 0, 0, 0, 128 * st["tiles_matrix"] * st["split_parts"]) and st["n_pad"] >= 300
+    st = instance(na, AQ_KERNEL="2")
+    assert st["core_kernel"] == 2 and geometry(st)[:4] == (0, 0, 0, 0) and st["n_pad"] >= 300 and st["n_pad"] % 64 == 0
+    small = make_problem(100, 75, 20, p_act=5)
+    got = A.atlasqtl_global_local_core_(small["Y"], small["X"], 20, None, 1, 0.1, 3, 0, small["list_hyper"], small["list_init"],
+                                        full_output=True)
+    assert got["core_kernel"] == 0 and got["split_parts"] == 1 and got["instance_flags"] == 0
+    assert got["n_pad"] == 16 * (3 * (got["tiles_matrix"] + got["tiles_matrix2"]) + got["tiles_recurrence"]) >= 100
+
+
 def test_env_overrides_are_reported(monkeypatch):
     """The AQ_* launch-plan hooks a handle was created under are visible through the C ABI (aq_vb_get_overrides): a host that
     inherits its environment can tell that the plan is not the library's own."""

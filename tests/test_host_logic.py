@@ -191,3 +191,46 @@ def test_operand_prefetch_protocol_is_consistent():
     for D in (3, 4):
         for NTC in range(4, 19):
             simulate(NTC, D)
+
+
+def test_split_instance_ledger_is_complete():
+    """tests/test_gpu_split_instances.py claims to run every sample-split instance of the look-ahead kernel and every part count
+    of the wide exchange against the oracle.  Its tables must name the complete set -- wide: NT = 1 ... 18, medium split: NT =
+    12 ... 18 with NT2 in {NT, NT - 1}, each for complete Y and MASK; C = 9 ... 48 -- and that set must be the one the launch
+    files compile: an instance added to an AQ_LB / AQ_LW list fails here until a case runs it."""
+    import os
+    import re
+    from tests import test_gpu_split_instances as T
+    medium, wide, parts = T.ledger()
+    want_medium = {(m, nt, nt2) for m in (0, 1) for nt in range(12, 19) for nt2 in (nt, nt - 1)}
+    want_wide = {(m, nt) for m in (0, 1) for nt in range(1, 19)}
+    assert medium == want_medium, sorted(want_medium ^ medium)
+    assert wide == want_wide, sorted(want_wide ^ wide)
+    assert parts == set(range(9, 49)), sorted(set(range(9, 49)) ^ parts)
+    # the forced tables alone reach every instance; the planned cases add none of their own
+    assert {(m, nt, nt2) for m in (0, 1) for nt, nt2 in T.MEDIUM_FORCED.values()} == want_medium
+    assert {nt for nt, cs in T.PARTS_NT.items() for C in cs} | set(T.WIDE_FORCED_NT) == set(range(1, 19))
+    assert sorted(C for cs in T.PARTS_NT.values() for C in cs) == list(range(9, 49))     # each C on exactly one NT
+    assert set(T.PARTS_NA_C) | set(T.PARTS_WHOLE_C) | set(T.PARTS_TWICE_C) <= set(range(9, 49))
+    # one C of each lane layout of split_exchange_wide: cmax = ceil(256 / C) entries per part, nch = 64 / cmax chunks of
+    # pc = ceil(C / nch) parts, the last chunk live or (C <= (nch - 1) pc) wholly beyond C: 17 layouts over C = 9 ... 48
+
+    def layout(C):
+        cmax = (256 + C - 1) // C
+        nch = 64 // cmax
+        pc = (C + nch - 1) // nch
+        return nch, pc, C <= (nch - 1) * pc
+    assert {layout(C) for C in T.PARTS_NA_C} == {layout(C) for C in range(9, 49)}
+    assert len({layout(C) for C in range(9, 49)}) == 17
+    assert any(layout(C)[2] for C in T.PARTS_WHOLE_C) and any(layout(C)[2] for C in T.PARTS_TWICE_C)
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "atlasqtl_amd", "csrc")
+
+    def listed(name, macro):
+        with open(os.path.join(csrc, name)) as f:
+            src = f.read()
+        body = src.split("#define " + macro + "(NT_)", 1)[1].split("#undef " + macro, 1)[0]
+        return sorted(int(x) for x in re.findall(macro + r"\((\d+)\)", body))
+    for name in ("aq_launch_la1.hip", "aq_launch_la1m.hip"):
+        assert listed(name, "AQ_LB") == sorted({nt for _, nt, _ in medium}), name
+    for m, name in ((0, "aq_launch_la1w.hip"), (1, "aq_launch_la1wm.hip")):
+        assert listed(name, "AQ_LW") == sorted(nt for mm, nt in wide if mm == m), name
