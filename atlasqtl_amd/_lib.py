@@ -104,6 +104,10 @@ SYMBOLS = {
     "aq_vb_bfdr_query": (C.c_int, [C.c_void_p, C.c_double, dp]),
     "aq_vb_bfdr_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     "aq_vb_bfdr_end": (None, [C.c_void_p]),
+    "aq_vb_select_pairs": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.c_int64, ip, ip, dp, dp, dp, C.POINTER(C.c_int64)]),
+    "aq_select_pairs": (C.c_int, [dp, dp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, ip, ip, dp, dp, dp,
+                                  C.POINTER(C.c_int64), C.c_int32]),
+    "aq_vb_bfdr_pairs": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, ip, ip, dp, dp]),
     "aq_vb_state_bytes": (C.c_int64, [C.c_void_p]),
     "aq_vb_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "aq_vb_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

@@ -193,6 +193,7 @@ class VbRun:
         self.n, self.p, self.q = n, p, q
         self.q_total = int(q if q_total is None else q_total)
         self.pg = process_group
+        self.trait_offset = int(trait_offset)
         self.world = 1
         self._red = self._ered = None
         ext_main = ext_elbo = None
@@ -287,7 +288,26 @@ class VbRun:
         return t.cpu().numpy()
 
     def _hotspot_sizes_fdr_sharded(self, thres):
-        """{FDR < thres} is a prefix of the global decreasing PPI order (the running mean of 1 - PPI never decreases along
+        """rowSums(assign_bFDR(gam_vb) < thres) over the traits of all ranks: the cutoff of `_fdr_cutoff_sharded`, counted
+        per predictor by aq_vb_bfdr_rows and summed over the ranks."""
+        L = lib()
+        check(L.aq_vb_bfdr_begin(self.h), "aq_vb_bfdr_begin")
+        try:
+            rs = np.zeros(self.p, dtype=np.int64)
+            cut = self._fdr_cutoff_sharded(thres)
+            if cut is None:                                       # FDR of the very first entry >= thres: nothing qualifies
+                return rs, 0
+            upto, tie_first, take = cut
+            check(L.aq_vb_bfdr_rows(self.h, upto, tie_first, take, rs.ctypes.data_as(C.POINTER(C.c_int64))), "aq_vb_bfdr_rows")
+            rs = self._sum_over_ranks(rs)
+            return rs, int(rs.sum())
+        finally:
+            L.aq_vb_bfdr_end(self.h)
+
+    def _fdr_cutoff_sharded(self, thres):
+        """Between aq_vb_bfdr_begin and aq_vb_bfdr_end: this rank's part (upto, tie_first, take) of the global
+        {FDR < thres} set, or None when it is empty.
+        {FDR < thres} is a prefix of the global decreasing PPI order (the running mean of 1 - PPI never decreases along
         it).  M(c) = mean of 1 - PPI over all entries >= c is the estimated FDR at the end of c's tie block; it grows as c
         falls, so a bisection over the bit patterns of c in [0, max PPI] finds the smallest c* with M(c*) < thres: every
         entry >= c* is in.  Of the next tie block down, the first entries (original order: lower ranks, then position) are
@@ -299,58 +319,112 @@ class VbRun:
         rank, world = dist.get_rank(self.pg), dist.get_world_size(self.pg)
         bits = lambda x: struct.unpack("<q", struct.pack("<d", x))[0]
         val = lambda b: struct.unpack("<d", struct.pack("<q", b))[0]
-        check(L.aq_vb_bfdr_begin(self.h), "aq_vb_bfdr_begin")
-        try:
-            def query(c):              # local five numbers, global sums of the first four
-                out = np.zeros(5)
-                check(L.aq_vb_bfdr_query(self.h, float(c), as_dp(out)), "aq_vb_bfdr_query")
-                return out, self._sum_over_ranks(out[:4].copy())
 
-            def below(c):              # M(c) < thres, with at least one entry >= c
-                _, g = query(c)
-                return g[0] > 0 and g[1] / g[0] < thres
+        def query(c):              # local five numbers, global sums of the first four
+            out = np.zeros(5)
+            check(L.aq_vb_bfdr_query(self.h, float(c), as_dp(out)), "aq_vb_bfdr_query")
+            return out, self._sum_over_ranks(out[:4].copy())
 
-            vmax = self._max_over_ranks(query(2.0)[0][4])         # the largest PPI of all
-            rs = np.zeros(self.p, dtype=np.int64)
-            if not below(vmax):                                   # FDR of the very first entry >= thres: nothing qualifies
-                return rs, 0
-            if below(0.0):
-                c_star = 0.0
-            else:
-                lo, hi = bits(0.0), bits(vmax)                    # below(lo) false, below(hi) true
-                while hi - lo > 1:
-                    mid = (lo + hi) // 2
-                    lo, hi = (lo, mid) if below(val(mid)) else (mid, hi)
-                c_star = val(hi)
-            loc, g = query(c_star)
-            upto = int(loc[0])                                    # this rank's entries >= c*
-            n_star, s_star = float(g[0]), float(g[1])
-            tie_val = self._max_over_ranks(loc[4])                # next PPI value down, over all ranks (-1: none)
-            take, tie_first = 0, upto
-            if tie_val >= 0.0:
-                loc_t, g_t = query(tie_val)
-                t_loc, t_glob = int(loc_t[0]) - int(loc_t[2]), int(g_t[0] - g_t[2])
-                d = 1.0 - tie_val
-                step_ok = lambda i: (s_star + i * d) / (n_star + i) < thres      # running mean after i entries of the block
-                i = 0
-                if d > thres:                                     # (else the whole block would have qualified)
-                    i = int(max(0, min(t_glob, np.floor((thres * n_star - s_star) / (d - thres)))))
-                    while i > 0 and not step_ok(i):
-                        i -= 1
-                    while i < t_glob and step_ok(i + 1):
-                        i += 1
-                counts = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
-                tl = torch.tensor([t_loc], dtype=torch.int64)
-                if dist.get_backend(self.pg) != "gloo":
-                    counts, tl = [c.cuda() for c in counts], tl.cuda()
-                dist.all_gather(counts, tl, group=self.pg)
-                before = sum(int(c.item()) for c in counts[:rank])                # ties of lower ranks come first
-                take = int(min(max(i - before, 0), t_loc))
-            check(L.aq_vb_bfdr_rows(self.h, upto, tie_first, take, rs.ctypes.data_as(C.POINTER(C.c_int64))), "aq_vb_bfdr_rows")
-            rs = self._sum_over_ranks(rs)
-            return rs, int(rs.sum())
-        finally:
-            L.aq_vb_bfdr_end(self.h)
+        def below(c):              # M(c) < thres, with at least one entry >= c
+            _, g = query(c)
+            return g[0] > 0 and g[1] / g[0] < thres
+
+        vmax = self._max_over_ranks(query(2.0)[0][4])         # the largest PPI of all
+        if not below(vmax):
+            return None
+        if below(0.0):
+            c_star = 0.0
+        else:
+            lo, hi = bits(0.0), bits(vmax)                    # below(lo) false, below(hi) true
+            while hi - lo > 1:
+                mid = (lo + hi) // 2
+                lo, hi = (lo, mid) if below(val(mid)) else (mid, hi)
+            c_star = val(hi)
+        loc, g = query(c_star)
+        upto = int(loc[0])                                    # this rank's entries >= c*
+        n_star, s_star = float(g[0]), float(g[1])
+        tie_val = self._max_over_ranks(loc[4])                # next PPI value down, over all ranks (-1: none)
+        take, tie_first = 0, upto
+        if tie_val >= 0.0:
+            loc_t, g_t = query(tie_val)
+            t_loc, t_glob = int(loc_t[0]) - int(loc_t[2]), int(g_t[0] - g_t[2])
+            d = 1.0 - tie_val
+            step_ok = lambda i: (s_star + i * d) / (n_star + i) < thres      # running mean after i entries of the block
+            i = 0
+            if d > thres:                                     # (else the whole block would have qualified)
+                i = int(max(0, min(t_glob, np.floor((thres * n_star - s_star) / (d - thres)))))
+                while i > 0 and not step_ok(i):
+                    i -= 1
+                while i < t_glob and step_ok(i + 1):
+                    i += 1
+            counts = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+            tl = torch.tensor([t_loc], dtype=torch.int64)
+            if dist.get_backend(self.pg) != "gloo":
+                counts, tl = [c.cuda() for c in counts], tl.cuda()
+            dist.all_gather(counts, tl, group=self.pg)
+            before = sum(int(c.item()) for c in counts[:rank])                # ties of lower ranks come first
+            take = int(min(max(i - before, 0), t_loc))
+        return upto, tie_first, take
+
+    def associations(self, thres=0.5, fdr_adjust=False, max_pairs=None):
+        """The associated (SNP, trait) pairs as a table, from the gam_vb / mu_beta_vb resident on the device (no p x q copy
+        to the host): {gam_vb > thres}, or {assign_bFDR(gam_vb) < thres} with fdr_adjust (summary.atlasqtl /
+        plot.atlasqtl, R/summarise_output.R:99-106).  Returns a dict of numpy arrays in the order of
+        order(as.vector(gam_vb), decreasing = TRUE) -- snp, trait (0-based, trait = global index), ppi,
+        beta (= gam_vb * mu_beta_vb) and fdr (= assign_bFDR at those entries) -- and n_pairs, the full count; the arrays
+        are shorter only when max_pairs cut them.  With a process group every rank returns the same whole-problem table."""
+        thres, fdr_adjust = float(thres), bool(fdr_adjust)
+        if max_pairs is not None and int(max_pairs) < 0:
+            raise ValueError("max_pairs must be None or >= 0")
+        if self.pg is None or not fdr_adjust:
+            tab = self._select_pairs(thres, fdr_adjust, max_pairs)
+            if self.pg is None:
+                return tab
+            n_pairs = int(self._sum_over_ranks(np.array([tab["n_pairs"]], dtype=np.int64))[0])
+        else:
+            L = lib()
+            check(L.aq_vb_bfdr_begin(self.h), "aq_vb_bfdr_begin")
+            try:
+                upto, tie_first, take = self._fdr_cutoff_sharded(thres) or (0, 0, 0)
+                n_pairs = int(self._sum_over_ranks(np.array([upto + take], dtype=np.int64))[0])
+                if max_pairs is not None:                     # a rank's share of the first max_pairs rows is among its own first
+                    upto = min(upto, int(max_pairs))
+                    take = min(take, int(max_pairs) - upto)
+                m = upto + take
+                tab = dict(snp=np.zeros(m, dtype=np.int32), trait=np.zeros(m, dtype=np.int32), ppi=np.zeros(m), beta=np.zeros(m))
+                check(L.aq_vb_bfdr_pairs(self.h, upto, tie_first, take, as_ip(tab["snp"]), as_ip(tab["trait"]), as_dp(tab["ppi"]),
+                                         as_dp(tab["beta"])), "aq_vb_bfdr_pairs")
+                tab["trait"] = tab["trait"] + np.int32(self.trait_offset)
+            finally:
+                L.aq_vb_bfdr_end(self.h)
+        return merge_pair_tables(self._gather_tables(tab), self.p, max_pairs=max_pairs, n_pairs=n_pairs)
+
+    def _select_pairs(self, thres, fdr_adjust, max_pairs):
+        """aq_vb_select_pairs on this handle, trait made global."""
+        L = lib()
+        tab = _fetch_pairs(lambda cap, *out: L.aq_vb_select_pairs(self.h, thres, int(fdr_adjust), cap, *out),
+                           "aq_vb_select_pairs", True, max_pairs)
+        tab["trait"] = tab["trait"] + np.int32(self.trait_offset)
+        return tab
+
+    def _gather_tables(self, tab):
+        """Every rank's rows (snp, global trait, ppi, beta) on every rank: one all-gather of the counts, one of the rows
+        padded to the longest table (int32 indices travel as doubles, exactly)."""
+        import torch
+        import torch.distributed as dist
+        world = dist.get_world_size(self.pg)
+        dev = (lambda t: t) if dist.get_backend(self.pg) == "gloo" else (lambda t: t.cuda())
+        m = len(tab["snp"])
+        counts = [dev(torch.zeros(1, dtype=torch.int64)) for _ in range(world)]
+        dist.all_gather(counts, dev(torch.tensor([m], dtype=torch.int64)), group=self.pg)
+        counts = [int(c.item()) for c in counts]
+        buf = torch.zeros((max(max(counts), 1), 4), dtype=torch.float64)
+        buf[:m] = torch.from_numpy(np.column_stack([tab["snp"], tab["trait"], tab["ppi"], tab["beta"]]).astype(np.float64))
+        outs = [dev(torch.zeros_like(buf)) for _ in range(world)]
+        dist.all_gather(outs, dev(buf), group=self.pg)
+        outs = [o.cpu().numpy()[:c] for o, c in zip(outs, counts)]
+        return [dict(snp=o[:, 0].astype(np.int32), trait=o[:, 1].astype(np.int32), ppi=o[:, 2].copy(), beta=o[:, 3].copy())
+                for o in outs]
 
     def _max_over_ranks(self, v):
         import torch
@@ -400,8 +474,11 @@ class VbRun:
         check(lib().aq_vb_get_residual(self.h, as_dp(R)), "aq_vb_get_residual")
         return R
 
-    def result(self, full_output=False):
+    def result(self, full_output=False, dense=True):
+        """dense=False skips the p x q matrices (beta_vb, gam_vb, mu_beta_vb): aq_vb_get_result gets NULL for them."""
         p, q = self.p, self.q
+        if not dense:
+            return self._result_vectors(full_output)
         beta = np.zeros((p, q), order="F"); gam = np.zeros((p, q), order="F")
         theta = np.zeros(p); zeta = np.zeros(q)
         mu = np.zeros((p, q), order="F") if full_output else None
@@ -417,6 +494,17 @@ class VbRun:
         out = dict(beta_vb=beta, gam_vb=gam, theta_vb=theta, zeta_vb=zeta)
         if full_output:
             out.update(mu_beta_vb=mu, lam2_inv_vb=lam, sig2_theta_vb=s2t, tau_vb=tau, sig2_beta_vb=s2b)
+        return out
+
+    def _result_vectors(self, full_output):
+        out = dict(theta_vb=np.zeros(self.p), zeta_vb=np.zeros(self.q))
+        if full_output:
+            out.update(lam2_inv_vb=np.zeros(self.p), sig2_theta_vb=np.zeros(self.p), tau_vb=np.zeros(self.q),
+                       sig2_beta_vb=np.zeros(self.q))
+        nul = C.cast(None, _lib.dp)
+        ptr = lambda k: as_dp(out[k]) if k in out else nul
+        check(lib().aq_vb_get_result(self.h, nul, nul, nul, ptr("theta_vb"), ptr("zeta_vb"), ptr("lam2_inv_vb"),
+                                     ptr("sig2_theta_vb"), ptr("tau_vb"), ptr("sig2_beta_vb")), "aq_vb_get_result")
         return out
 
 
@@ -494,6 +582,69 @@ def hotspot_sizes(gam_vb, thres=0.5, fdr_adjust=False, device=0):
     return rs, int(tot.value)
 
 
+def merge_pair_tables(tables, p, max_pairs=None, n_pairs=None):
+    """One table from several (the trait shards' own): rows ordered by (-ppi, position j + p k of the whole matrix, i.e.
+    `trait` global) as order(as.vector(gam_vb), decreasing = TRUE) orders them, and fdr = cumsum(1 - ppi) / (1:N) along
+    it -- assign_bFDR (R/summarise_output.R:207-223) at those entries, because the union of the tables is a prefix of
+    that order.  n_pairs: the full count when the tables were already cut to max_pairs rows each."""
+    snp = np.concatenate([np.asarray(t["snp"], dtype=np.int32) for t in tables])
+    trait = np.concatenate([np.asarray(t["trait"], dtype=np.int32) for t in tables])
+    ppi = np.concatenate([np.asarray(t["ppi"], dtype=np.float64) for t in tables])
+    beta = np.concatenate([np.asarray(t["beta"], dtype=np.float64) for t in tables])
+    order = np.lexsort((snp.astype(np.int64) + int(p) * trait.astype(np.int64), -ppi))
+    snp, trait, ppi, beta = snp[order], trait[order], ppi[order], beta[order]
+    fdr = np.cumsum(1 - ppi) / np.arange(1, ppi.size + 1)
+    m = ppi.size if max_pairs is None else min(ppi.size, int(max_pairs))
+    return dict(snp=snp[:m], trait=trait[:m], ppi=ppi[:m], beta=beta[:m], fdr=fdr[:m],
+                n_pairs=int(ppi.size if n_pairs is None else n_pairs))
+
+
+def associations(gam_vb, beta_vb=None, thres=0.5, fdr_adjust=False, max_pairs=None, device=0):
+    """The table of VbRun.associations from host matrices (gam_vb, and beta_vb for the effect sizes; without it the table
+    has no `beta`): summary.atlasqtl's gam_vb > thres / assign_bFDR(gam_vb) < thres (R/summarise_output.R:99-106)."""
+    m = np.asfortranarray(gam_vb, dtype=np.float64)
+    p, q = m.shape
+    b = None
+    if beta_vb is not None:
+        b = np.asfortranarray(beta_vb, dtype=np.float64)
+        if b.shape != m.shape:
+            raise ValueError("beta_vb must have the shape of gam_vb")
+    if max_pairs is not None and int(max_pairs) < 0:
+        raise ValueError("max_pairs must be None or >= 0")
+    args = (as_dp(m), C.cast(None, _lib.dp) if b is None else as_dp(b), p, q, float(thres), int(bool(fdr_adjust)))
+    return _fetch_pairs(lambda cap, *out: lib().aq_select_pairs(*args, cap, *out, int(device)), "aq_select_pairs",
+                        b is not None, max_pairs)
+
+
+def _fetch_pairs(call, what, with_beta, max_pairs):
+    """Drive aq_select_pairs / aq_vb_select_pairs: call(cap, snp, trait, ppi, beta, fdr, n_pairs).  The count is not known
+    beforehand, so without max_pairs the first call offers room for 65 536 rows and only a longer table costs a second call."""
+    cap = (1 << 16) if max_pairs is None else int(max_pairs)
+    n = C.c_int64(0)
+    while True:
+        tab = dict(snp=np.zeros(cap, dtype=np.int32), trait=np.zeros(cap, dtype=np.int32), ppi=np.zeros(cap), fdr=np.zeros(cap))
+        if with_beta:
+            tab["beta"] = np.zeros(cap)
+        check(call(cap, as_ip(tab["snp"]), as_ip(tab["trait"]), as_dp(tab["ppi"]),
+                   as_dp(tab["beta"]) if with_beta else C.cast(None, _lib.dp), as_dp(tab["fdr"]), C.byref(n)), what)
+        if n.value <= cap or max_pairs is not None:
+            break
+        cap = int(n.value)
+    tab = {k: v[:min(cap, n.value)].copy() for k, v in tab.items()}
+    tab["n_pairs"] = int(n.value)
+    return tab
+
+
+SPARSE_OUTPUT_DEFAULTS = {"thres": 0.5, "fdr_adjust": False, "max_pairs": None}
+
+
+def sparse_output_options(sparse_output):
+    """The `sparse_output` argument of atlasqtl() / atlasqtl_global_local_core_ with its defaults filled in."""
+    if not isinstance(sparse_output, dict) or set(sparse_output) - set(SPARSE_OUTPUT_DEFAULTS):
+        raise ValueError("sparse_output must be None or a dict with keys among 'thres', 'fdr_adjust', 'max_pairs'")
+    return {**SPARSE_OUTPUT_DEFAULTS, **sparse_output}
+
+
 def _run_with_checkpoints(run, checkpoint_path, rate, maxit):
     """checkpoint_ / checkpoint_clean_up_ (R/utils.R:571-627, R/atlasqtl_global_local_core.R:379,388): every `rate`
     iterations write the reference's temporary output list (tmp_output_it_<it>.npz: beta_vb, gam_vb, theta_vb, zeta_vb,
@@ -536,7 +687,7 @@ def _run_with_checkpoints(run, checkpoint_path, rate, maxit):
 def atlasqtl_global_local_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, verbose, list_hyper, list_init,
                                 checkpoint_path=None, trace_path=None, full_output=False, thinned_elbo_eval=True,
                                 debug=False, batch="y", device=0, process_group=None, resume_from=None,
-                                checkpoint_rate=100, trait_offset=None, scheme="global_local"):
+                                checkpoint_rate=100, trait_offset=None, scheme="global_local", sparse_output=None):
     """R/atlasqtl_global_local_core.R:8-433 on the GPU.  Returns the reference's list
     (:426-428): beta_vb, gam_vb, theta_vb, zeta_vb, n, p, q, anneal, converged, it, maxit,
     tol, lb_opt, diff_lb (+ the variational parameters with full_output).
@@ -544,7 +695,12 @@ def atlasqtl_global_local_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, verbo
     shr_fac_inv is the total number of traits (R/atlasqtl.R:218); with a process group each
     rank passes its own trait columns and shr_fac_inv = q of the whole problem.  trait_offset = global index of
     this rank's first trait: required with a process group when the p x q initial values are drawn on the device
-    (the Philox counters are (SNP, global trait), so a sharded run reproduces the single-GPU draws)."""
+    (the Philox counters are (SNP, global trait), so a sharded run reproduces the single-GPU draws).
+
+    sparse_output = {"thres": 0.5, "fdr_adjust": False, "max_pairs": None} (missing keys take these values) returns the
+    thresholded result instead of the p x q matrices: `assoc` (VbRun.associations), `rs_thres` and `nb_pairwise`
+    (VbRun.hotspot_sizes), theta_vb, zeta_vb and the scalars -- no gam_vb / beta_vb / mu_beta_vb, which stay on the device."""
+    sparse = None if sparse_output is None else sparse_output_options(sparse_output)
     if df not in (1, 3, 5, 7):
         raise NotImplementedError("df must be 1, 3, 5 or 7 (compute_integral_hs_, R/utils.R:425-568, is unstable from df = 9 on)")
     if batch != "y":
@@ -573,7 +729,10 @@ def atlasqtl_global_local_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, verbo
             else:
                 import warnings
                 warnings.warn("Maximal number of iterations reached before convergence. Exit.")   # :397
-        res = run.result(full_output=full_output)
+        res = run.result(full_output=full_output, dense=sparse is None)
+        if sparse is not None:
+            res["assoc"] = run.associations(sparse["thres"], sparse["fdr_adjust"], sparse["max_pairs"])
+            res["rs_thres"], res["nb_pairwise"] = run.hotspot_sizes(sparse["thres"], sparse["fdr_adjust"])
         its, lbs = run.elbo_trace()
         res.update(n=run.n, p=run.p, q=run.q, anneal=anneal, converged=bool(st["converged"]), it=int(st["it"]),
                    maxit=maxit, tol=tol, lb_opt=st["lb_opt"], diff_lb=st["diff_lb"])

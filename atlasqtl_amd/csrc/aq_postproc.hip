@@ -190,3 +190,294 @@ int aq_row_count_device(const double *d_m, int64_t *d_rs, int p, int q, double t
   if (e != hipSuccess) return aq_fail_ext(AQ_ERR_DEVICE, std::string("aq_k_row_count: ") + hipGetErrorString(e));
   return AQ_OK;
 }
+
+// ---- sparse table of associations --------------------------------------------------------------------------------------
+// What summary.atlasqtl / plot.atlasqtl do with gam_vb is threshold it (R/summarise_output.R:99-106): gam_vb > thres, or
+// assign_bFDR(gam_vb) < thres.  A few thousand to a few million pairs survive out of 5e8 ... 4e9, so the table
+//     (snp, trait, ppi, beta = gam_vb mu_beta_vb, fdr),   rows in the order of order(as.vector(gam_vb), decreasing = TRUE)
+// is built here and the p x q matrices stay on the device.  In both modes the selected set is a prefix of that order (PPI
+// mode: a tie block is in or out as a whole; FDR mode: the running mean of 1 - PPI never decreases along it), so the FDR of
+// a row is cumsum(1 - ppi) / (1:N) along the table itself.
+//   selection   two passes over the storage, one wave per AQ_SEL_ITEMS consecutive elements: count (ballot + popcount) ->
+//               exclusive scan of the wave counts -> write (key, value) at base + rank inside the ballot.  Order-preserving.
+//   PPI mode    reads the PPIs where they are -- the trait-tiled gam of a handle [(tile p_pad + j) 16 + k % 16], or a column-
+//               major matrix -- and sorts only the selected rows: by position (tiled storage is not in position order), then
+//               stably by decreasing PPI.  Scratch: 16 B per wave + 32 B per selected row + the sort's.  Nothing of size p q.
+//   FDR mode    aq_sort_ppi as assign_bFDR, then the same selection over the sorted order with the flag
+//               csum[i] / (i + 1) < thres: exactly the entries aq_bfdr_device would give an FDR below thres.
+#define AQ_SEL_ITEMS 2048   // elements per wave: 32 coalesced reads of 64 doubles
+
+struct aq_pair_src {
+  const double *ppi;   // tiled gam, or p x q column-major PPIs
+  const double *mul;   // tiled mu_beta_vb (beta = ppi * mul), or p x q column-major beta (copied), or NULL
+  int p, q, p_pad, tiled;
+};
+// storage element e -> column-major position j + p k; false for the padding rows / traits of a tiled array
+__device__ inline bool aq_src_pos(const aq_pair_src &s, size_t e, uint64_t *pos) {
+  if (!s.tiled) { *pos = e; return true; }
+  const size_t row = e >> 4, tile = row / (size_t)s.p_pad, j = row - tile * (size_t)s.p_pad, kk = tile * 16 + (e & 15);
+  if (j >= (size_t)s.p || kk >= (size_t)s.q) return false;
+  *pos = j + (size_t)s.p * kk;
+  return true;
+}
+__device__ inline double aq_src_beta(const aq_pair_src &s, uint64_t pos, double ppi) {
+  if (!s.mul) return 0.0;
+  if (!s.tiled) return s.mul[pos];
+  const size_t kk = pos / (size_t)s.p, j = pos - kk * (size_t)s.p;
+  return ppi * s.mul[((kk >> 4) * (size_t)s.p_pad + j) * 16 + (kk & 15)];      // gam_vb * mu_beta_vb, R/update_vb.R:17
+}
+
+struct aq_sel_ppi {     // gam_vb > thres, R/summarise_output.R:104; value = position
+  aq_pair_src s;
+  double thres;
+  __device__ bool operator()(size_t e, double *key, uint64_t *val) const {
+    if (!aq_src_pos(s, e, val)) return false;
+    *key = s.ppi[e];
+    return *key > thres;
+  }
+};
+struct aq_sel_fdr {     // assign_bFDR(gam_vb) < thres, :100-101, along the sorted order; value = sorted position
+  const double *keys, *csum;
+  double thres;
+  __device__ bool operator()(size_t e, double *key, uint64_t *val) const {
+    *key = keys[e];
+    *val = e;
+    return csum[e] / (double)(e + 1) < thres;
+  }
+};
+
+template <typename F>
+__global__ void aq_k_sel_count(F f, size_t n, unsigned long long *cnt) {
+  const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  const size_t e0 = wave * AQ_SEL_ITEMS;
+  if (e0 >= n) return;
+  unsigned long long c = 0;
+  for (int it = 0; it < AQ_SEL_ITEMS / 64; it++) {
+    const size_t e = e0 + (size_t)it * 64 + lane;
+    double k;
+    uint64_t v;
+    const bool sel = e < n && f(e, &k, &v);
+    c += __popcll(__ballot(sel));
+  }
+  if (lane == 0) cnt[wave] = c;
+}
+// rows below `limit` only (the FDR table needs no more than the rows that are returned)
+template <typename F>
+__global__ void aq_k_sel_write(F f, size_t n, const unsigned long long *__restrict__ off, size_t limit,
+                               double *__restrict__ okey, uint64_t *__restrict__ oval) {
+  const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  const size_t e0 = wave * AQ_SEL_ITEMS;
+  if (e0 >= n) return;
+  size_t base = off[wave];
+  for (int it = 0; it < AQ_SEL_ITEMS / 64 && base < limit; it++) {
+    const size_t e = e0 + (size_t)it * 64 + lane;
+    double k = 0.0;
+    uint64_t v = 0;
+    const bool sel = e < n && f(e, &k, &v);
+    const unsigned long long b = __ballot(sel);
+    const size_t at = base + __popcll(b & ((1ull << lane) - 1ull));
+    if (sel && at < limit) { okey[at] = k; oval[at] = v; }
+    base += __popcll(b);
+  }
+}
+// table rows from the selected (key, value) pairs.  idx == NULL: value = position, cs[r] the running sum along the table;
+// idx != NULL: value = sorted position i, position = idx[i], cs[i] the running sum along the whole order.
+template <typename I>
+__global__ void aq_k_pairs_gather(aq_pair_src s, const double *__restrict__ key, const uint64_t *__restrict__ val,
+                                  const I *__restrict__ idx, const double *__restrict__ cs, size_t m, int32_t *__restrict__ snp,
+                                  int32_t *__restrict__ trait, double *__restrict__ beta, double *__restrict__ fdr) {
+  const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= m) return;
+  const size_t i = idx ? (size_t)val[r] : r;
+  const uint64_t pos = idx ? (uint64_t)idx[i] : val[r];
+  snp[r] = (int32_t)(pos % (uint64_t)s.p);
+  trait[r] = (int32_t)(pos / (uint64_t)s.p);
+  beta[r] = aq_src_beta(s, pos, key[r]);
+  fdr[r] = cs[i] / (double)(i + 1);
+}
+
+// count -> scan -> *n_sel; then the first min(limit, *n_sel) selected pairs into *okey / *oval (allocated here)
+template <typename F>
+static int aq_select_compact(F f, size_t n, int64_t limit, int64_t *n_sel, double **okey, uint64_t **oval) {
+  int rc = AQ_OK;
+  const size_t nw = (n + AQ_SEL_ITEMS - 1) / AQ_SEL_ITEMS;
+  const unsigned grid = (unsigned)((nw + 3) / 4);
+  unsigned long long *cnt = nullptr, *off = nullptr, last[2] = {0, 0};
+  void *tmp = nullptr;
+  size_t tb = 0, m = 0;
+  *okey = nullptr; *oval = nullptr; *n_sel = 0;
+  AQP_HIP(hipMalloc((void **)&cnt, nw * sizeof(unsigned long long)));
+  AQP_HIP(hipMalloc((void **)&off, nw * sizeof(unsigned long long)));
+  hipLaunchKernelGGL((aq_k_sel_count<F>), dim3(grid), dim3(256), 0, 0, f, n, cnt);
+  AQP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, off, (int64_t)nw));
+  AQP_HIP(hipMalloc(&tmp, tb));
+  AQP_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, off, (int64_t)nw));
+  AQP_HIP(hipMemcpy(&last[0], cnt + (nw - 1), sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  AQP_HIP(hipMemcpy(&last[1], off + (nw - 1), sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  *n_sel = (int64_t)(last[0] + last[1]);
+  m = (size_t)(limit < *n_sel ? limit : *n_sel);
+  if (m > 0) {
+    AQP_HIP(hipMalloc((void **)okey, m * sizeof(double)));
+    AQP_HIP(hipMalloc((void **)oval, m * sizeof(uint64_t)));
+    hipLaunchKernelGGL((aq_k_sel_write<F>), dim3(grid), dim3(256), 0, 0, f, n, off, m, *okey, *oval);
+    AQP_HIP(hipGetLastError());
+    AQP_HIP(hipDeviceSynchronize());
+  }
+done:
+  if (cnt) hipFree(cnt);
+  if (off) hipFree(off);
+  if (tmp) hipFree(tmp);
+  if (rc != AQ_OK) {
+    if (*okey) hipFree(*okey);
+    if (*oval) hipFree(*oval);
+    *okey = nullptr; *oval = nullptr;
+  }
+  return rc;
+}
+
+// rows [0, m) of the table to the host arrays that were asked for (key = the PPIs in table order)
+template <typename I>
+static int aq_pairs_emit(const aq_pair_src &src, const double *key, const uint64_t *val, const I *idx, const double *cs, size_t m,
+                         int32_t *snp, int32_t *trait, double *ppi, double *beta, double *fdr) {
+  int rc = AQ_OK;
+  int32_t *d_i = nullptr;
+  double *d_d = nullptr;
+  AQP_HIP(hipMalloc((void **)&d_i, 2 * m * sizeof(int32_t)));
+  AQP_HIP(hipMalloc((void **)&d_d, 2 * m * sizeof(double)));
+  hipLaunchKernelGGL((aq_k_pairs_gather<I>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, src, key, val, idx, cs, m, d_i,
+                     d_i + m, d_d, d_d + m);
+  AQP_HIP(hipGetLastError());
+  if (snp) AQP_HIP(hipMemcpy(snp, d_i, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (trait) AQP_HIP(hipMemcpy(trait, d_i + m, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (ppi) AQP_HIP(hipMemcpy(ppi, key, m * sizeof(double), hipMemcpyDeviceToHost));
+  if (beta && src.mul) AQP_HIP(hipMemcpy(beta, d_d, m * sizeof(double), hipMemcpyDeviceToHost));
+  if (fdr) AQP_HIP(hipMemcpy(fdr, d_d + m, m * sizeof(double), hipMemcpyDeviceToHost));
+  AQP_HIP(hipDeviceSynchronize());
+done:
+  if (d_i) hipFree(d_i);
+  if (d_d) hipFree(d_d);
+  return rc;
+}
+
+static int aq_pairs_ppi(const aq_pair_src &src, double thres, int64_t cap, int32_t *snp, int32_t *trait, double *ppi, double *beta,
+                        double *fdr, int64_t *n_pairs) {
+  int rc = AQ_OK;
+  const size_t n_el = src.tiled ? (size_t)((src.q + 15) / 16) * src.p_pad * 16 : (size_t)src.p * src.q;
+  double *ka = nullptr, *kb = nullptr;
+  uint64_t *va = nullptr, *vb = nullptr;
+  void *tmp = nullptr;
+  size_t tb = 0, tb2 = 0, m = 0, N = 0;
+  int pos_bits = 1;
+  aq_sel_ppi f{src, thres};
+  // cap = 0 counts only: nothing is written
+  rc = aq_select_compact(f, n_el, cap > 0 ? INT64_MAX : 0, n_pairs, &ka, &va);
+  if (rc != AQ_OK) return rc;
+  N = (size_t)*n_pairs;
+  m = (size_t)((int64_t)N < cap ? (int64_t)N : cap);
+  if (m == 0) goto done;
+  while (pos_bits < 64 && ((uint64_t)src.p * (uint64_t)src.q) >> pos_bits) pos_bits++;
+  AQP_HIP(hipMalloc((void **)&kb, N * sizeof(double)));
+  AQP_HIP(hipMalloc((void **)&vb, N * sizeof(uint64_t)));
+  AQP_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, va, vb, ka, kb, (int64_t)N, 0, pos_bits));
+  AQP_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb2, kb, ka, vb, va, (int64_t)N));
+  if (tb2 > tb) tb = tb2;
+  AQP_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb2, kb, kb, (int64_t)m));
+  if (tb2 > tb) tb = tb2;
+  AQP_HIP(hipMalloc(&tmp, tb));
+  if (src.tiled) {   // the tiled storage is not in position order: order(decreasing = TRUE) breaks ties by position
+    AQP_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, va, vb, ka, kb, (int64_t)N, 0, pos_bits));
+    AQP_HIP(hipcub::DeviceRadixSort::SortPairsDescending(tmp, tb, kb, ka, vb, va, (int64_t)N));
+  } else {
+    AQP_HIP(hipcub::DeviceRadixSort::SortPairsDescending(tmp, tb, ka, kb, va, vb, (int64_t)N));
+    { double *t = ka; ka = kb; kb = t; }
+    { uint64_t *t = va; va = vb; vb = t; }
+  }
+  // (ka, va) = the table order; kb, vb are free: 1 - ppi and its running sum over the rows that are returned
+  hipLaunchKernelGGL(aq_k_one_minus, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, ka, kb, m);
+  AQP_HIP(hipcub::DeviceScan::InclusiveSum(tmp, tb, kb, (double *)vb, (int64_t)m));
+  AQP_HIP(hipGetLastError());
+  rc = aq_pairs_emit<uint64_t>(src, ka, va, nullptr, (const double *)vb, m, snp, trait, ppi, beta, fdr);
+done:
+  if (ka) hipFree(ka);
+  if (kb) hipFree(kb);
+  if (va) hipFree(va);
+  if (vb) hipFree(vb);
+  if (tmp) hipFree(tmp);
+  return rc;
+}
+
+template <typename I>
+static int aq_pairs_fdr(const double *d_cm, const aq_pair_src &src, double thres, int64_t cap, int32_t *snp, int32_t *trait,
+                        double *ppi, double *beta, double *fdr, int64_t *n_pairs) {
+  double *keys = nullptr, *csum = nullptr, *sk = nullptr;
+  uint64_t *sv = nullptr;
+  I *idx = nullptr;
+  int rc = aq_sort_ppi<I>(d_cm, (size_t)src.p * src.q, &keys, &csum, &idx);
+  if (rc != AQ_OK) return rc;
+  aq_sel_fdr f{keys, csum, thres};
+  rc = aq_select_compact(f, (size_t)src.p * src.q, cap, n_pairs, &sk, &sv);
+  if (rc == AQ_OK && sk) {
+    const size_t m = (size_t)(*n_pairs < cap ? *n_pairs : cap);
+    rc = aq_pairs_emit<I>(src, sk, sv, idx, csum, m, snp, trait, ppi, beta, fdr);
+  }
+  hipFree(keys); hipFree(csum); hipFree(idx);
+  if (sk) hipFree(sk);
+  if (sv) hipFree(sv);
+  return rc;
+}
+
+// src_ppi / src_mul: the storage the table's ppi and beta are read from (tiled != 0: trait-tiled with p_pad rows per tile);
+// d_cm: the same PPIs p x q column-major, needed in FDR mode only (the full sort works on as.vector(gam_vb)).
+int aq_pairs_device(const double *d_cm, const double *src_ppi, const double *src_mul, int p, int q, int p_pad, int tiled, double thres,
+                    int fdr_adjust, int64_t cap, int32_t *snp, int32_t *trait, double *ppi, double *beta, double *fdr,
+                    int64_t *n_pairs) {
+  aq_pair_src src{src_ppi, src_mul, p, q, p_pad, tiled};
+  if (!fdr_adjust) return aq_pairs_ppi(src, thres, cap, snp, trait, ppi, beta, fdr, n_pairs);
+  if ((uint64_t)p * (uint64_t)q < (1ull << 32) && !aq_force_idx64())
+    return aq_pairs_fdr<uint32_t>(d_cm, src, thres, cap, snp, trait, ppi, beta, fdr, n_pairs);
+  return aq_pairs_fdr<uint64_t>(d_cm, src, thres, cap, snp, trait, ppi, beta, fdr, n_pairs);
+}
+
+// rows of a sorted shard (aq_shard_rows' arguments): its first `upto` entries, then `take` entries from sorted position t0
+template <typename I>
+__global__ void aq_k_shard_pairs(aq_pair_src s, const double *__restrict__ keys, const I *__restrict__ idx, size_t upto, size_t t0,
+                                 size_t m, int32_t *__restrict__ snp, int32_t *__restrict__ trait, double *__restrict__ ppi,
+                                 double *__restrict__ beta) {
+  const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= m) return;
+  const size_t i = r < upto ? r : t0 + (r - upto);
+  const uint64_t pos = (uint64_t)idx[i];
+  snp[r] = (int32_t)(pos % (uint64_t)s.p);
+  trait[r] = (int32_t)(pos / (uint64_t)s.p);
+  ppi[r] = keys[i];
+  beta[r] = aq_src_beta(s, pos, keys[i]);
+}
+int aq_shard_pairs(const aq_shard_sorted *sh, int64_t upto, int64_t t0, int64_t take, const double *gam_tile, const double *mu_tile,
+                   int p, int q, int p_pad, int32_t *snp, int32_t *trait, double *ppi, double *beta) {
+  int rc = AQ_OK;
+  const size_t m = (size_t)upto + (size_t)take;
+  int32_t *d_i = nullptr;
+  double *d_d = nullptr;
+  aq_pair_src src{gam_tile, mu_tile, p, q, p_pad, 1};
+  if (m == 0) return AQ_OK;
+  AQP_HIP(hipMalloc((void **)&d_i, 2 * m * sizeof(int32_t)));
+  AQP_HIP(hipMalloc((void **)&d_d, 2 * m * sizeof(double)));
+  if (sh->idx32)
+    hipLaunchKernelGGL((aq_k_shard_pairs<uint32_t>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, src, sh->keys, sh->idx32,
+                       (size_t)upto, (size_t)t0, m, d_i, d_i + m, d_d, d_d + m);
+  else
+    hipLaunchKernelGGL((aq_k_shard_pairs<uint64_t>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, src, sh->keys, sh->idx64,
+                       (size_t)upto, (size_t)t0, m, d_i, d_i + m, d_d, d_d + m);
+  AQP_HIP(hipGetLastError());
+  if (snp) AQP_HIP(hipMemcpy(snp, d_i, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (trait) AQP_HIP(hipMemcpy(trait, d_i + m, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (ppi) AQP_HIP(hipMemcpy(ppi, d_d, m * sizeof(double), hipMemcpyDeviceToHost));
+  if (beta) AQP_HIP(hipMemcpy(beta, d_d + m, m * sizeof(double), hipMemcpyDeviceToHost));
+  AQP_HIP(hipDeviceSynchronize());
+done:
+  if (d_i) hipFree(d_i);
+  if (d_d) hipFree(d_d);
+  return rc;
+}

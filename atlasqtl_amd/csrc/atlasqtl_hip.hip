@@ -36,6 +36,11 @@ int aq_shard_sort(const double *d_ppi, int64_t len, aq_shard_sorted **out);
 int aq_shard_query(const aq_shard_sorted *s, double c, double out[5]);
 int aq_shard_rows(const aq_shard_sorted *s, int64_t upto, int64_t t0, int64_t take, int p, int64_t *rs_host);
 void aq_shard_free(aq_shard_sorted *s);
+int aq_shard_pairs(const aq_shard_sorted *sh, int64_t upto, int64_t t0, int64_t take, const double *gam_tile, const double *mu_tile,
+                   int p, int q, int p_pad, int32_t *snp, int32_t *trait, double *ppi, double *beta);
+int aq_pairs_device(const double *d_cm, const double *src_ppi, const double *src_mul, int p, int q, int p_pad, int tiled, double thres,
+                    int fdr_adjust, int64_t cap, int32_t *snp, int32_t *trait, double *ppi, double *beta, double *fdr,
+                    int64_t *n_pairs);
 #define AQ_HIP(call)                                                                                   \
   do {                                                                                                 \
     hipError_t e_ = (call);                                                                            \
@@ -1355,6 +1360,58 @@ extern "C" int aq_vb_bfdr_rows(aq_vb_handle s, int64_t upto, int64_t tie_first, 
 }
 extern "C" void aq_vb_bfdr_end(aq_vb_handle s) {
   if (s && s->bf) { hipSetDevice(s->device); aq_shard_free(s->bf); s->bf = nullptr; }
+}
+
+// Sparse table of associations (aq_postproc.hip): which (SNP, trait) pairs pass the threshold, with their effect sizes, in
+// the order of order(as.vector(gam_vb), decreasing = TRUE) -- what summary.atlasqtl / plot.atlasqtl read off gam_vb
+// (R/summarise_output.R:99-106) -- without a p x q matrix leaving the device.  Argument errors come before any device call.
+static int aq_pairs_args(const char *who, bool ok, double thres, int64_t cap, const int64_t *n_pairs) {
+  if (!ok || !n_pairs || thres != thres || cap < 0)
+    return aq_fail(AQ_ERR_ARG, std::string(who) + ": bad argument (NULL handle / matrix / n_pairs, NaN thres or cap < 0)");
+  return AQ_OK;
+}
+extern "C" int aq_vb_select_pairs(aq_vb_handle s, double thres, int32_t fdr_adjust, int64_t cap, int32_t *snp, int32_t *trait,
+                                  double *ppi, double *beta, double *fdr, int64_t *n_pairs) {
+  AQ_TRY(aq_pairs_args("aq_vb_select_pairs", s != nullptr, thres, cap, n_pairs));
+  AQ_HIP(hipSetDevice(s->device));
+  AQ_HIP(hipDeviceSynchronize());
+  AQ_TRY(aq_check_chain_error(s));
+  if (!fdr_adjust)     // reads the trait-tiled gam / mu where they are: nothing of size p q is allocated
+    return aq_pairs_device(nullptr, s->gam, s->mu, s->p, s->q, s->p_pad, 1, thres, 0, cap, snp, trait, ppi, beta, fdr, n_pairs);
+  double *d_m = nullptr;   // assign_bFDR ranks as.vector(gam_vb): the column-major copy aq_vb_hotspot_sizes makes as well
+  AQ_HIP(hipMalloc((void **)&d_m, (size_t)s->p * s->q * sizeof(double)));
+  hipLaunchKernelGGL(aq_k_colmajor_from_tile, dim3((s->p_pad + 63) / 64, s->ntile), dim3(256), 0, 0, s->gam, (const double *)nullptr,
+                     d_m, s->p, s->q, s->p_pad);
+  int rc = aq_pairs_device(d_m, s->gam, s->mu, s->p, s->q, s->p_pad, 1, thres, 1, cap, snp, trait, ppi, beta, fdr, n_pairs);
+  hipFree(d_m);
+  return rc;
+}
+extern "C" int aq_select_pairs(const double *mat_ppi, const double *mat_beta, int32_t p, int32_t q, double thres, int32_t fdr_adjust,
+                               int64_t cap, int32_t *snp, int32_t *trait, double *ppi, double *beta, double *fdr, int64_t *n_pairs,
+                               int32_t device) {
+  AQ_TRY(aq_pairs_args("aq_select_pairs", mat_ppi != nullptr && p > 0 && q > 0, thres, cap, n_pairs));
+  AQ_TRY(aq_need_device(device));
+  const size_t pq = (size_t)p * q;
+  double *d_m = nullptr, *d_b = nullptr;
+  AQ_HIP(hipMalloc((void **)&d_m, pq * sizeof(double)));
+  hipError_t e = hipMemcpy(d_m, mat_ppi, pq * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess && mat_beta) {
+    e = hipMalloc((void **)&d_b, pq * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(d_b, mat_beta, pq * sizeof(double), hipMemcpyHostToDevice);
+  }
+  int rc = e == hipSuccess ? aq_pairs_device(d_m, d_m, d_b, p, q, p, 0, thres, fdr_adjust, cap, snp, trait, ppi, beta, fdr, n_pairs)
+                           : aq_fail(AQ_ERR_DEVICE, std::string("aq_select_pairs: ") + hipGetErrorString(e));
+  hipFree(d_m);
+  if (d_b) hipFree(d_b);
+  return rc;
+}
+extern "C" int aq_vb_bfdr_pairs(aq_vb_handle s, int64_t upto, int64_t tie_first, int64_t take, int32_t *snp, int32_t *trait,
+                                double *ppi, double *beta) {
+  if (!s || !s->bf) return aq_fail(AQ_ERR_ARG, "aq_vb_bfdr_pairs: call aq_vb_bfdr_begin first");
+  if (upto < 0 || take < 0 || tie_first < 0 || upto > (int64_t)s->p * s->q || tie_first + take > (int64_t)s->p * s->q)
+    return aq_fail(AQ_ERR_ARG, "aq_vb_bfdr_pairs: positions out of range");
+  AQ_HIP(hipSetDevice(s->device));
+  return aq_shard_pairs(s->bf, upto, tie_first, take, s->gam, s->mu, s->p, s->q, s->p_pad, snp, trait, ppi, beta);
 }
 
 // ------------------------------------------------------ checkpoint / resume ----

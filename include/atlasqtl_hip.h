@@ -296,6 +296,34 @@ int aq_vb_bfdr_rows(aq_vb_handle h, int64_t upto, int64_t tie_first, int64_t tak
 void aq_vb_bfdr_end(aq_vb_handle h);
 
 /* ------------------------------------------------------------------------------------------
+ * Sparse table of associations: what summary.atlasqtl / plot.atlasqtl read off gam_vb (R/summarise_output.R:99-106),
+ *     fdr_adjust = 0   { (j,k) : gam_vb[j,k] > thres }                      (:104)
+ *     fdr_adjust = 1   { (j,k) : assign_bFDR(gam_vb)[j,k] < thres }         (:100-101)
+ * as rows (snp j, trait k, ppi, beta = gam_vb mu_beta_vb (R/update_vb.R:17), fdr), 0-based, in the order of
+ * order(as.vector(gam_vb), decreasing = TRUE): decreasing PPI, ties by increasing column-major position j + p k.  In
+ * both modes the set is a prefix of that order, so fdr = cumsum(1 - ppi) / (1:N) along the table equals assign_bFDR at
+ * those entries.  The p x q matrices never leave the device; in PPI mode on a handle nothing of size p q is allocated
+ * (the trait-tiled state is read in place and only the selected rows are sorted).
+ *   aq_vb_select_pairs  from the gam_vb / mu_beta_vb resident in a handle (trait = index local to the handle).  Writes
+ *                       the first min(cap, *n_pairs) rows; *n_pairs is always the full count.  cap = 0 with NULL arrays
+ *                       counts only.  Any output array may be NULL.  Synchronises and reports an expired in-kernel wait
+ *                       (AQ_ERR_DEVICE) as aq_vb_get_result does.
+ *   aq_select_pairs     the same on host matrices (p x q column-major); mat_beta may be NULL (beta is then not written).
+ *   aq_vb_bfdr_pairs    trait-sharded FDR mode, between aq_vb_bfdr_begin and aq_vb_bfdr_end, with the arguments of
+ *                       aq_vb_bfdr_rows: this shard's first `upto` sorted entries plus `take` entries of the tie block
+ *                       at tie_first, as rows (snp, local trait, ppi, beta).  The caller merges the shards' rows by
+ *                       (-ppi, global position) and takes the running mean (atlasqtl_amd/core.py::VbRun.associations).
+ * NaN thres, cap < 0, NULL n_pairs / handle / mat_ppi: AQ_ERR_ARG before any device call.
+ * ---------------------------------------------------------------------------------------- */
+int aq_vb_select_pairs(aq_vb_handle h, double thres, int32_t fdr_adjust, int64_t cap, int32_t *snp, int32_t *trait,
+                       double *ppi, double *beta, double *fdr, int64_t *n_pairs);
+int aq_select_pairs(const double *mat_ppi, const double *mat_beta, int32_t p, int32_t q, double thres,
+                    int32_t fdr_adjust, int64_t cap, int32_t *snp, int32_t *trait, double *ppi, double *beta,
+                    double *fdr, int64_t *n_pairs, int32_t device);
+int aq_vb_bfdr_pairs(aq_vb_handle h, int64_t upto, int64_t tie_first, int64_t take, int32_t *snp, int32_t *trait,
+                     double *ppi, double *beta);
+
+/* ------------------------------------------------------------------------------------------
  * Checkpoint / resume.  The reference's checkpoint_ (R/utils.R:571-611, called at
  * R/atlasqtl_global_local_core.R:379) only writes outputs every 100 iterations and cannot resume; these
  * entries capture and restore the COMPLETE loop state between two sweeps (valid after aq_vb_run /
