@@ -53,6 +53,14 @@ class AqVbMultiOut(C.Structure):
     ]
 
 
+class AqMoments(C.Structure):
+    _fields_ = [("count", C.c_int64), ("n_nan", C.c_int64), ("min", C.c_double), ("max", C.c_double), ("sum", C.c_double)]
+
+
+AQ_RSEL_BITS = 8          # digit width of the radix select (include/atlasqtl_hip.h)
+AQ_RSEL_MAX_PREFIX = 16
+
+
 class AqVbStatus(C.Structure):
     _fields_ = [
         ("it", C.c_int32), ("converged", C.c_int32), ("lb_opt", C.c_double), ("diff_lb", C.c_double),
@@ -108,6 +116,10 @@ SYMBOLS = {
     "aq_select_pairs": (C.c_int, [dp, dp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, ip, ip, dp, dp, dp,
                                   C.POINTER(C.c_int64), C.c_int32]),
     "aq_vb_bfdr_pairs": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, ip, ip, dp, dp]),
+    "aq_vb_radix_hist": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_int64)]),
+    "aq_vb_moments": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(AqMoments)]),
+    "aq_vb_order_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), dp, C.POINTER(AqMoments)]),
+    "aq_order_stats": (C.c_int, [dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), dp, C.POINTER(AqMoments), C.c_int32]),
     "aq_vb_state_bytes": (C.c_int64, [C.c_void_p]),
     "aq_vb_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "aq_vb_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

@@ -6,11 +6,12 @@ variational loop runs on the GPU through core.atlasqtl_global_local_core_.
 """
 from __future__ import annotations
 
+import sys
 import warnings
 
 import numpy as np
 
-from .core import atlasqtl_global_local_core_, sparse_output_options
+from .core import (atlasqtl_global_local_core_, hotspot_sizes, six_numbers_host_, sparse_output_options, value_summary)
 from .hyper_init import prepare_list_hyper_, prepare_list_init_
 from .prepare import check_annealing_, check_positive_, check_vector_, check_verbose_, prepare_data_
 
@@ -68,12 +69,18 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
     sparse_output = {"thres": 0.5, "fdr_adjust": False, "max_pairs": None} (missing keys take these values): instead of
     the p x q gam_vb / beta_vb, return what summary.atlasqtl reads off them (R/summarise_output.R:99-106) -- `assoc`, the
     table of pairs with gam_vb > thres (or assign_bFDR(gam_vb) < thres) with snp / trait indices and names, ppi, beta and
-    fdr; `rs_thres` and `nb_pairwise` -- so that the matrices never leave the GPU.  None: the dense result."""
+    fdr; `rs_thres` and `nb_pairwise` -- so that the matrices never leave the GPU.  With "summary": True also
+    `value_summary`, the quartiles and means of all p q PPIs and effect sizes that summary() prints (computed on the GPU,
+    core.VbRun.value_summary).  None: the dense result."""
     sparse = None if sparse_output is None else sparse_output_options(sparse_output)
     if sparse is not None and add_collinear_back and sparse["fdr_adjust"]:
         raise ValueError("add_collinear_back=True cannot be combined with sparse_output in FDR mode: the re-inserted copies "
                          "would take part in the FDR ranking, which changes the selected set and cannot be derived from the "
                          "table.  Use the PPI mode (fdr_adjust=False) or the dense output.")
+    if sparse is not None and add_collinear_back and sparse["summary"]:
+        raise ValueError('add_collinear_back=True cannot be combined with sparse_output={"summary": True}: the re-inserted '
+                         "copies would enter the quartiles of gam_vb and beta_vb, which the six numbers of the fitted matrix "
+                         "cannot reproduce.  Use the dense output.")
     check_verbose_(verbose)
     check_annealing_(anneal)
     dat = prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path)
@@ -107,6 +114,8 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
     res["names_x"], res["names_y"] = dat["names_x"], dat["names_y"]
     names_snp = dat["names_x"]
     if sparse is not None:
+        if sparse["summary"]:
+            res["sparse_output"] = dict(sparse)
         if add_collinear_back:
             if dat["rmvd_coll_x"]:
                 res["assoc"], res["rs_thres"], res["theta_vb"] = add_collinear_back_pairs_(
@@ -114,6 +123,7 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
                     dat["names_x"], sparse["max_pairs"])
                 res["nb_pairwise"] = res["assoc"]["n_pairs"]
                 names_snp = dat["initial_colnames_X"]
+                res["names_x_all"] = list(names_snp)              # the rows of rs_thres / theta_vb, for summary()
             elif sparse["max_pairs"] is not None:
                 res["assoc"] = {k: (v if k == "n_pairs" else v[:int(sparse["max_pairs"])]) for k, v in res["assoc"].items()}
         res["assoc"]["snp_name"] = np.asarray(names_snp, dtype=object)[res["assoc"]["snp"]]
@@ -122,8 +132,149 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
         res["beta_vb"], res["gam_vb"], res["theta_vb"] = add_collinear_back_(
             res["beta_vb"], res["gam_vb"], res["theta_vb"], dat["initial_colnames_X"], dat["rmvd_coll_x"],
             dat["names_x"])
+        res["names_x_all"] = list(dat["initial_colnames_X"])      # the rows of gam_vb / theta_vb, for summary()
     if save_hyper:
         res["list_hyper"] = list_hyper
     if save_init:
         res["list_init"] = list_init
     return res
+
+
+# ---- S3 methods of the reference: print.atlasqtl and summary.atlasqtl (R/summarise_output.R) ----
+def _rchar(x):
+    """as.character of a number as paste0 writes it: 15 significant digits, integers without a decimal point."""
+    if isinstance(x, (bool, np.bool_)):
+        return "TRUE" if x else "FALSE"
+    if isinstance(x, (int, np.integer)):
+        return str(int(x))
+    return f"{float(x):.15g}"
+
+
+def _rformat(x, digits):
+    """format(x, digits = d) of one number: d significant digits, but never fewer than the integer part has."""
+    x = float(x)
+    if np.isfinite(x) and abs(x) >= 10 ** digits:
+        return f"{x:.0f}"
+    return f"{x:.{digits}g}"
+
+
+_SIX = (("min", "Min."), ("q1", "1st Qu."), ("median", "Median"), ("mean", "Mean"), ("q3", "3rd Qu."), ("max", "Max."))
+
+
+def _print_six(six, file):
+    """print(summary(x)): R's labels over the six numbers, four significant digits (summary.default's default)."""
+    vals = [("NaN" if lab == "Mean" else "NA") if six is None else _rformat(six[k], 4) for k, lab in _SIX]
+    width = [max(len(lab), len(v)) + 1 for (_, lab), v in zip(_SIX, vals)]
+    print("".join(lab.rjust(w) for (_, lab), w in zip(_SIX, width)) + " ", file=file)
+    print("".join(v.rjust(w) for v, w in zip(vals, width)) + " ", file=file)
+
+
+def _only_six(d):
+    return {k: d[k] for k, _ in _SIX}
+
+
+def print_atlasqtl(x, file=None):
+    """print.atlasqtl, R/summarise_output.R:14-59: basic information about the run."""
+    file = sys.stdout if file is None else file
+    if x["converged"]:
+        file.write("****************************************************** \n"
+                   f"Successful convergence after {_rchar(x['it'])} iterations, using a\n"
+                   f"tolerance of {_rchar(x['tol'])} on the absolute changes in the ELBO.\n"
+                   "****************************************************** \n\n")
+        anneal = x.get("anneal")
+        if anneal is not None:
+            anneal_type = {1: "Geometric", 2: "Harmonic", 3: "Linear"}[int(anneal[0])]
+            default = tuple(float(a) for a in anneal) == (1.0, 2.0, 10.0)
+            file.write(f"{anneal_type} annealing on the inverse temperature was\n"
+                       f"applied for the first {_rchar(anneal[2])} iterations, with initial\n"
+                       f"temperature of {_rchar(anneal[1])}" + (" (default).\n\n" if default else ".\n\n"))
+        p0 = x.get("p0")
+        file.write(f"Number of samples: {_rchar(x['n'])};\n"
+                   f"Number of (non-redundant) candidate predictors: {_rchar(x['p'])};\n"
+                   f"Number of responses: {_rchar(x['q'])};\n"
+                   "Prior expectation for the number of predictors\n"
+                   f"associated with each response: {'NA' if p0 is None else _rchar(p0[0])} (sd: "
+                   f"{'NA' if p0 is None else _rformat(np.sqrt(p0[1]), 2)}).\n\n")
+        file.write("The posterior quantities inferred by ATLASQTL can\n"
+                   "be accessed as list elements from the `atlasqtl` S3\n"
+                   "object, and a summary can obtained using the\n"
+                   "`summary` function.\n\n")
+    else:
+        file.write("************************************************ \n"
+                   f"Unsuccessful convergence after {_rchar(x['maxit'])} iterations. \n"
+                   "Difference between last two consecutive values\n"
+                   f"of the ELBO: {_rformat(x['diff_lb'], 3)}.\n\n"
+                   "Try increasing:\n"
+                   "- the maximum number of iterations (maxit) or\n"
+                   "- the convergence threshold (tol). \n"
+                   "************************************************ \n\n")
+
+
+def summary(object, thres=0.5, fdr_adjust=False, full_summary=True, file=None, device=0):
+    """summary.atlasqtl, R/summarise_output.R:83-137: prints the posterior summary for variable selection to `file`
+    (default sys.stdout) and returns what it printed: gam_vb, beta_vb, theta_vb (Min., 1st Qu., Median, Mean, 3rd Qu., Max. as
+    dicts; with full_summary only), nb_pairwise, n_active, hotspot_sizes (the six numbers of the active predictors' sizes,
+    None when there is none), top (up to six (name, size) by decreasing size) and rs_thres.
+
+    A dense result (gam_vb, beta_vb present) is summarised here, the p q quartiles by value_summary on the GPU `device`.
+    A sparse result must come from sparse_output={..., "summary": True} and the same (thres, fdr_adjust): its matrices
+    never left the GPU, the numbers were taken there."""
+    file = sys.stdout if file is None else file
+    thres, fdr_adjust = float(thres), bool(fdr_adjust)
+    dense = "gam_vb" in object and "beta_vb" in object
+    if not dense:
+        if "value_summary" not in object:
+            raise ValueError('summary() of a sparse result needs the quartiles taken on the GPU: run atlasqtl with '
+                             'sparse_output={..., "summary": True}')
+        used = object["sparse_output"]
+        if (float(used["thres"]), bool(used["fdr_adjust"])) != (thres, fdr_adjust):
+            raise ValueError(f"summary(thres={thres}, fdr_adjust={fdr_adjust}) of a sparse result computed with thres="
+                             f"{used['thres']}, fdr_adjust={used['fdr_adjust']}: the p x q matrices are gone, only the run's "
+                             "own threshold can be summarised")
+    out = {}
+    file.write("****************************************************** \n"
+               "* ATLASQTL: posterior summary for variable selection *\n"
+               "****************************************************** \n\n")
+    if full_summary:
+        if dense:
+            out["gam_vb"] = _only_six(value_summary(object["gam_vb"], device))
+            out["beta_vb"] = _only_six(value_summary(object["beta_vb"], device))
+        else:
+            out["gam_vb"] = _only_six(object["value_summary"]["gam_vb"])
+            out["beta_vb"] = _only_six(object["value_summary"]["beta_vb"])
+        out["theta_vb"] = _only_six(six_numbers_host_(object["theta_vb"]))
+        file.write("Posterior probabilities pairwise association, pr(gamma_st = 1 | y)\n")
+        _print_six(out["gam_vb"], file)
+        file.write("\nPosterior mean of pairwise regression coefficients, E(beta_st | y)\n")
+        _print_six(out["beta_vb"], file)
+        file.write("\nPosterior mean of hotspot propensities, E(theta_s | y)\n ")
+        _print_six(out["theta_vb"], file)
+        file.write("\n\n")
+    if dense:
+        rs_thres, nb_pairwise = hotspot_sizes(object["gam_vb"], thres, fdr_adjust, device)
+    else:
+        rs_thres, nb_pairwise = np.asarray(object["rs_thres"], dtype=np.int64), int(object["nb_pairwise"])
+    if fdr_adjust:
+        file.write(f"Using a {_rchar(100 * thres)}% FDR control:\n-----------------------\n")
+    else:
+        file.write(f"Using a PPI threshold of {_rchar(thres)}:\n------------------------------\n")
+    active = rs_thres > 0
+    n_active = int(active.sum())
+    file.write(f"\nNb of pairwise (predictor-response) associations: {nb_pairwise} \n")
+    file.write("\nNb of predictors associated with at least one response \n"
+               f"(active predictors): {n_active} \n")
+    file.write("\nHotspot sizes (nb of responses associated with each \nactive predictor):\n")
+    sizes = _only_six(six_numbers_host_(rs_thres[active])) if n_active else None
+    _print_six(sizes, file)
+    names = object.get("names_x_all", object.get("names_x"))
+    if names is None or len(names) != rs_thres.size:
+        names = [str(j + 1) for j in range(rs_thres.size)]
+    order = np.argsort(-rs_thres, kind="stable")[:min(n_active, 6)]     # sort(decreasing = TRUE) keeps ties in predictor order
+    top = [(names[j], int(rs_thres[j])) for j in order]
+    if top:
+        label = [f"{nm} (size {sz})" for nm, sz in top]
+        file.write("\nTop hotspots: \n" + ", ".join(label[:3]) + (", " if len(top) > 3 else ". ") + "\n")
+        if len(top) > 3:
+            file.write(", ".join(label[3:]))
+    out.update(nb_pairwise=int(nb_pairwise), n_active=n_active, hotspot_sizes=sizes, top=top, rs_thres=rs_thres)
+    return out

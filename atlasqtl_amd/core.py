@@ -435,6 +435,59 @@ class VbRun:
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.pg)
         return float(t.item())
 
+    def value_summary(self, which):
+        """Min., 1st Qu., Median, Mean, 3rd Qu., Max. of all p q entries of "gam_vb" or "beta_vb" (= gam_vb * mu_beta_vb), as
+        summary(as.vector(object$gam_vb)) / summary(as.vector(object$beta_vb)) of summary.atlasqtl print them
+        (R/summarise_output.R:89-93), plus count and n_nan -- from the state resident on the device: a radix select
+        (aq_vb_order_stats), no p x q copy and no p x q scratch.  With a process group the numbers cover the traits of ALL
+        ranks: the digit histograms of the shards (aq_vb_radix_hist) are summed over the ranks, one small all-reduce per
+        digit, and every rank returns the same dict."""
+        L = lib()
+        w = {"gam_vb": 0, "beta_vb": 1}.get(which)
+        if w is None:
+            raise ValueError('which must be "gam_vb" or "beta_vb"')
+        mom = _lib.AqMoments()
+        if self.pg is None:
+            check(L.aq_vb_moments(self.h, w, C.byref(mom)), "aq_vb_moments")
+            ranks = quantile_ranks_(mom.count)
+            r = np.asarray(ranks, dtype=np.int64)
+            out = np.zeros(r.size)
+            check(L.aq_vb_order_stats(self.h, w, r.size, r.ctypes.data_as(C.POINTER(C.c_int64)), as_dp(out), C.byref(mom)),
+                  "aq_vb_order_stats")
+            return six_numbers_(mom.count, dict(zip(ranks, out.tolist())), mom.sum, mom.n_nan)
+        check(L.aq_vb_moments(self.h, w, C.byref(mom)), "aq_vb_moments")
+        count, n_nan = (int(v) for v in self._sum_over_ranks(np.array([mom.count, mom.n_nan], dtype=np.int64)))
+        total = self._sum_in_rank_order(mom.sum)
+        lo, hi = -self._max_over_ranks(-mom.min), self._max_over_ranks(mom.max)
+
+        def hist_fn(prefixes, shift):
+            pre = np.asarray(prefixes, dtype=np.uint64)
+            hist = np.zeros((pre.size, 1 << _lib.AQ_RSEL_BITS), dtype=np.int64)
+            check(L.aq_vb_radix_hist(self.h, w, pre.size, pre.ctypes.data_as(C.POINTER(C.c_uint64)), int(shift),
+                                     hist.ctypes.data_as(C.POINTER(C.c_int64))), "aq_vb_radix_hist")
+            return self._sum_over_ranks(hist)
+
+        ranks = quantile_ranks_(count)
+        stat = dict(zip(ranks, radix_select_(hist_fn, ranks, _lib.AQ_RSEL_BITS)))
+        out = six_numbers_(count, stat, total, n_nan)
+        if out["min"] != lo or out["max"] != hi:
+            raise _lib.AtlasqtlHipError("value_summary: the select's extremes differ from the moments pass's")
+        return out
+
+    def _sum_in_rank_order(self, v):
+        """Sum of one double per rank, added in rank order on every rank: the same bits everywhere (an all-reduce may add
+        in another order on another rank)."""
+        import torch
+        import torch.distributed as dist
+        world = dist.get_world_size(self.pg)
+        dev = (lambda t: t) if dist.get_backend(self.pg) == "gloo" else (lambda t: t.cuda())
+        parts = [dev(torch.zeros(1, dtype=torch.float64)) for _ in range(world)]
+        dist.all_gather(parts, dev(torch.tensor([float(v)], dtype=torch.float64)), group=self.pg)
+        total = 0.0
+        for t in parts:
+            total += float(t.item())
+        return total
+
     def get_state(self):
         """The complete loop state between two sweeps as one uint8 array (aq_vb_get_state): unlike the reference's
         write-only checkpoint_ (R/utils.R:571-611), `set_state` on a handle created for the same problem continues
@@ -582,6 +635,110 @@ def hotspot_sizes(gam_vb, thres=0.5, fdr_adjust=False, device=0):
     return rs, int(tot.value)
 
 
+def _key_to_double(key):
+    """Inverse of the order-preserving key map of aq_summary.hip (negative: all bits flipped; otherwise: sign bit set)."""
+    import struct
+    bits = key ^ (1 << 63) if key >> 63 else ~key & ((1 << 64) - 1)
+    return struct.unpack("<d", struct.pack("<Q", bits))[0]
+
+
+def radix_select_(hist_fn, ranks, bits=_lib.AQ_RSEL_BITS):
+    """The digit loop of the radix select, for values held elsewhere (on the device, or spread over trait shards): the
+    ranks[i]-th smallest values (0-based, ranks ascending), as a list of floats.
+    hist_fn(prefixes, shift) -> n_prefix x 2^bits counts: for every prefix (sorted, distinct; a prefix is key >> (shift +
+    bits)), the histogram of the digit (key >> shift) & (2^bits - 1) among the values with that prefix; at the top digit
+    (shift + bits == 64) prefixes is [0] and all values count.  Per wanted rank the state is (prefix, rank left inside the
+    prefix); per digit the bin where the cumulative count first exceeds the rank left is appended to the prefix and the
+    count below it subtracted.  After the last digit the prefix is the key.  Counts are Python integers: no 2^32 limit."""
+    if 64 % bits:
+        raise ValueError("bits must divide 64")
+    ranks = [int(r) for r in ranks]
+    if any(r < 0 for r in ranks) or any(b < a for a, b in zip(ranks, ranks[1:])):
+        raise ValueError("ranks must be non-negative and ascending")
+    pre, rem = [0] * len(ranks), list(ranks)
+    for shift in range(64 - bits, -1, -bits):
+        prefixes = sorted(set(pre))
+        hist = np.asarray(hist_fn(prefixes, shift))
+        if hist.shape != (len(prefixes), 1 << bits):
+            raise ValueError(f"hist_fn must return {len(prefixes)} x {1 << bits} counts")
+        row = {pf: [int(c) for c in hist[i]] for i, pf in enumerate(prefixes)}
+        for i in range(len(ranks)):
+            below = 0
+            for d, c in enumerate(row[pre[i]]):
+                if below + c > rem[i]:
+                    break
+                below += c
+            else:
+                raise ValueError(f"rank {ranks[i]} is not below the number of values")
+            rem[i] -= below
+            pre[i] = (pre[i] << bits) | d
+    return [_key_to_double(k) for k in pre]
+
+
+_QUARTILES = (("q1", 0.25), ("median", 0.5), ("q3", 0.75))
+
+
+def quantile_ranks_(count):
+    """The order statistics (0-based ranks, sorted, distinct) that min, max and the type-7 quartiles of `count` values
+    need: {0, N - 1} and floor / ceil of (N - 1) {1/4, 1/2, 3/4}."""
+    N = int(count)
+    if N < 1:
+        raise ValueError("no value to summarise (all entries are NaN)")
+    want = {0, N - 1}
+    for _, prob in _QUARTILES:
+        index = (N - 1) * prob
+        want.update((int(np.floor(index)), int(np.ceil(index))))
+    return sorted(want)
+
+
+def six_numbers_(count, stat, total, n_nan=0):
+    """R's summary.default from order statistics: stat[rank] = the rank-th smallest of the `count` values, total their
+    sum.  Quartiles as stats::quantile.default, type 7 (third-party arithmetic restated): index = (N - 1) prob, lo = floor,
+    hi = ceil; x[lo], unless index > lo and x[hi] != x[lo]: then (1 - h) x[lo] + h x[hi] with h = index - lo."""
+    N = int(count)
+    out = {"min": float(stat[0])}
+    for name, prob in _QUARTILES:
+        index = (N - 1) * prob
+        lo, hi = int(np.floor(index)), int(np.ceil(index))
+        qs = float(stat[lo])
+        if index > lo and float(stat[hi]) != qs:
+            h = index - lo
+            qs = (1 - h) * qs + h * float(stat[hi])
+        out[name] = qs
+    out["mean"] = float(total) / N
+    out["max"] = float(stat[N - 1])
+    out.update(count=N, n_nan=int(n_nan))
+    return {k: out[k] for k in ("min", "q1", "median", "mean", "q3", "max", "count", "n_nan")}
+
+
+def six_numbers_host_(x):
+    """six_numbers_ of a short host vector (theta_vb, the hotspot sizes: p entries), NaN left out as R leaves out NA."""
+    import math
+    v = np.asarray(x, dtype=np.float64).reshape(-1)
+    nan = np.isnan(v)
+    s = np.sort(v[~nan])
+    return six_numbers_(s.size, {r: s[r] for r in quantile_ranks_(s.size)}, math.fsum(s), int(nan.sum()))
+
+
+def value_summary(x, device=0):
+    """Min., 1st Qu., Median, Mean, 3rd Qu., Max. (R's summary.default; plus count and n_nan) of the entries of a host
+    array of any shape -- summary(as.vector(x)) -- by the radix select on the GPU (aq_order_stats)."""
+    v = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
+    if v.size < 1:
+        raise ValueError("x has no entry")
+    # NaN is left out on the device; its count is not known beforehand, so the ranks are asked for once it is
+    n_nan = int(np.isnan(v).sum())
+    ranks = quantile_ranks_(v.size - n_nan)
+    r = np.asarray(ranks, dtype=np.int64)
+    out = np.zeros(r.size)
+    mom = _lib.AqMoments()
+    check(lib().aq_order_stats(as_dp(v), v.size, r.size, r.ctypes.data_as(C.POINTER(C.c_int64)), as_dp(out), C.byref(mom),
+                               int(device)), "aq_order_stats")
+    if mom.n_nan != n_nan:
+        raise _lib.AtlasqtlHipError(f"aq_order_stats counted {mom.n_nan} NaN, the host {n_nan}")
+    return six_numbers_(mom.count, dict(zip(ranks, out.tolist())), mom.sum, mom.n_nan)
+
+
 def merge_pair_tables(tables, p, max_pairs=None, n_pairs=None):
     """One table from several (the trait shards' own): rows ordered by (-ppi, position j + p k of the whole matrix, i.e.
     `trait` global) as order(as.vector(gam_vb), decreasing = TRUE) orders them, and fdr = cumsum(1 - ppi) / (1:N) along
@@ -635,13 +792,14 @@ def _fetch_pairs(call, what, with_beta, max_pairs):
     return tab
 
 
-SPARSE_OUTPUT_DEFAULTS = {"thres": 0.5, "fdr_adjust": False, "max_pairs": None}
+SPARSE_OUTPUT_DEFAULTS = {"thres": 0.5, "fdr_adjust": False, "max_pairs": None, "summary": False}
 
 
 def sparse_output_options(sparse_output):
     """The `sparse_output` argument of atlasqtl() / atlasqtl_global_local_core_ with its defaults filled in."""
     if not isinstance(sparse_output, dict) or set(sparse_output) - set(SPARSE_OUTPUT_DEFAULTS):
-        raise ValueError("sparse_output must be None or a dict with keys among 'thres', 'fdr_adjust', 'max_pairs'")
+        raise ValueError("sparse_output must be None or a dict with keys among 'thres', 'fdr_adjust', 'max_pairs', "
+                         "'summary'")
     return {**SPARSE_OUTPUT_DEFAULTS, **sparse_output}
 
 
@@ -699,7 +857,10 @@ def atlasqtl_global_local_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, verbo
 
     sparse_output = {"thres": 0.5, "fdr_adjust": False, "max_pairs": None} (missing keys take these values) returns the
     thresholded result instead of the p x q matrices: `assoc` (VbRun.associations), `rs_thres` and `nb_pairwise`
-    (VbRun.hotspot_sizes), theta_vb, zeta_vb and the scalars -- no gam_vb / beta_vb / mu_beta_vb, which stay on the device."""
+    (VbRun.hotspot_sizes), theta_vb, zeta_vb and the scalars -- no gam_vb / beta_vb / mu_beta_vb, which stay on the device.
+    With "summary": True (default False) the result also holds `value_summary` = {"gam_vb": ..., "beta_vb": ...}, the six
+    numbers of VbRun.value_summary that summary() prints for the p q PPIs and effect sizes, and `sparse_output`, the
+    options used."""
     sparse = None if sparse_output is None else sparse_output_options(sparse_output)
     if df not in (1, 3, 5, 7):
         raise NotImplementedError("df must be 1, 3, 5 or 7 (compute_integral_hs_, R/utils.R:425-568, is unstable from df = 9 on)")
@@ -733,6 +894,9 @@ def atlasqtl_global_local_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, verbo
         if sparse is not None:
             res["assoc"] = run.associations(sparse["thres"], sparse["fdr_adjust"], sparse["max_pairs"])
             res["rs_thres"], res["nb_pairwise"] = run.hotspot_sizes(sparse["thres"], sparse["fdr_adjust"])
+            if sparse["summary"]:
+                res["value_summary"] = {"gam_vb": run.value_summary("gam_vb"), "beta_vb": run.value_summary("beta_vb")}
+                res["sparse_output"] = dict(sparse)
         its, lbs = run.elbo_trace()
         res.update(n=run.n, p=run.p, q=run.q, anneal=anneal, converged=bool(st["converged"]), it=int(st["it"]),
                    maxit=maxit, tol=tol, lb_opt=st["lb_opt"], diff_lb=st["diff_lb"])

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string>
 #include "../../include/atlasqtl_hip.h"
+#include "aq_pair_src.h"   // aq_pair_src, aq_src_pos
 
 int aq_fail_ext(int code, const std::string &msg);   // atlasqtl_hip.hip
 
@@ -207,19 +208,6 @@ int aq_row_count_device(const double *d_m, int64_t *d_rs, int p, int q, double t
 //               csum[i] / (i + 1) < thres: exactly the entries aq_bfdr_device would give an FDR below thres.
 #define AQ_SEL_ITEMS 2048   // elements per wave: 32 coalesced reads of 64 doubles
 
-struct aq_pair_src {
-  const double *ppi;   // tiled gam, or p x q column-major PPIs
-  const double *mul;   // tiled mu_beta_vb (beta = ppi * mul), or p x q column-major beta (copied), or NULL
-  int p, q, p_pad, tiled;
-};
-// storage element e -> column-major position j + p k; false for the padding rows / traits of a tiled array
-__device__ inline bool aq_src_pos(const aq_pair_src &s, size_t e, uint64_t *pos) {
-  if (!s.tiled) { *pos = e; return true; }
-  const size_t row = e >> 4, tile = row / (size_t)s.p_pad, j = row - tile * (size_t)s.p_pad, kk = tile * 16 + (e & 15);
-  if (j >= (size_t)s.p || kk >= (size_t)s.q) return false;
-  *pos = j + (size_t)s.p * kk;
-  return true;
-}
 __device__ inline double aq_src_beta(const aq_pair_src &s, uint64_t pos, double ppi) {
   if (!s.mul) return 0.0;
   if (!s.tiled) return s.mul[pos];

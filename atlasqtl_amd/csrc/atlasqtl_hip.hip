@@ -20,6 +20,7 @@
 #include "aq_trait_wave.h"
 #include "aq_core_sweep_mis.h"
 #include "aq_vec_kernels.h"
+#include "aq_pair_src.h"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -41,6 +42,11 @@ int aq_shard_pairs(const aq_shard_sorted *sh, int64_t upto, int64_t t0, int64_t 
 int aq_pairs_device(const double *d_cm, const double *src_ppi, const double *src_mul, int p, int q, int p_pad, int tiled, double thres,
                     int fdr_adjust, int64_t cap, int32_t *snp, int32_t *trait, double *ppi, double *beta, double *fdr,
                     int64_t *n_pairs);
+// aq_summary.hip (radix select and moments of the p x q values)
+int aq_moments_device(const aq_pair_src &src, size_t n_el, aq_moments *out);
+int aq_rsel_hist_device(const aq_pair_src &src, size_t n_el, int n_prefix, const uint64_t *prefix, int shift, int64_t *hist);
+int aq_order_stats_device(const aq_pair_src &src, size_t n_el, int n_ranks, const int64_t *ranks, double *out, aq_moments *mom,
+                          const char *who);
 #define AQ_HIP(call)                                                                                   \
   do {                                                                                                 \
     hipError_t e_ = (call);                                                                            \
@@ -1412,6 +1418,66 @@ extern "C" int aq_vb_bfdr_pairs(aq_vb_handle s, int64_t upto, int64_t tie_first,
     return aq_fail(AQ_ERR_ARG, "aq_vb_bfdr_pairs: positions out of range");
   AQ_HIP(hipSetDevice(s->device));
   return aq_shard_pairs(s->bf, upto, tie_first, take, s->gam, s->mu, s->p, s->q, s->p_pad, snp, trait, ppi, beta);
+}
+
+// Order statistics and moments of gam_vb / beta_vb (aq_summary.hip): the six numbers of summary(as.vector(gam_vb)) and
+// summary(as.vector(beta_vb)), R/summarise_output.R:89-93, from the trait-tiled state where it lies.  Argument errors come
+// before any device call.
+static int aq_ranks_args(const char *who, bool ok, int32_t n_ranks, const int64_t *ranks, const double *out) {
+  bool good = ok && ranks && out && n_ranks >= 1 && n_ranks <= AQ_RSEL_MAX_PREFIX;
+  for (int i = 0; good && i < n_ranks; i++) good = ranks[i] >= 0 && (i == 0 || ranks[i] >= ranks[i - 1]);
+  if (!good)
+    return aq_fail(AQ_ERR_ARG, std::string(who) + ": bad argument (NULL handle / array / ranks / out, which not 0 / 1, n_ranks "
+                                                  "outside 1 ... 16, ranks negative or not ascending, or len < 1)");
+  return AQ_OK;
+}
+static aq_pair_src aq_summary_src(const aq_vb *s, int which) {
+  return aq_pair_src{s->gam, which ? s->mu : nullptr, s->p, s->q, s->p_pad, 1};
+}
+// results are about to leave the library: wait for the sweeps and poll the bounded-wait flag, as aq_vb_get_result does
+static int aq_summary_ready(aq_vb *s) {
+  AQ_HIP(hipSetDevice(s->device));
+  AQ_HIP(hipDeviceSynchronize());
+  return aq_check_chain_error(s);
+}
+extern "C" int aq_vb_radix_hist(aq_vb_handle s, int32_t which, int32_t n_prefix, const uint64_t *prefix, int32_t shift,
+                                int64_t *hist) {
+  const bool top = shift + AQ_RSEL_BITS == 64;
+  bool good = s && hist && (which == 0 || which == 1) && shift >= 0 && shift < 64 && shift % AQ_RSEL_BITS == 0 && n_prefix >= 1 &&
+              n_prefix <= (top ? 1 : AQ_RSEL_MAX_PREFIX) && (top || prefix);
+  for (int i = 1; good && !top && i < n_prefix; i++) good = prefix[i] > prefix[i - 1];
+  if (!good)
+    return aq_fail(AQ_ERR_ARG, "aq_vb_radix_hist: bad argument (NULL handle / prefix / hist, which not 0 / 1, shift not a multiple of "
+                               "AQ_RSEL_BITS in [0, 64), n_prefix outside 1 ... 16 (1 at the top digit), or prefixes not ascending)");
+  AQ_TRY(aq_summary_ready(s));
+  const aq_pair_src src = aq_summary_src(s, which);
+  return aq_rsel_hist_device(src, aq_src_elements(src, 0), n_prefix, prefix, shift, hist);
+}
+extern "C" int aq_vb_moments(aq_vb_handle s, int32_t which, aq_moments *out) {
+  if (!s || !out || (which != 0 && which != 1))
+    return aq_fail(AQ_ERR_ARG, "aq_vb_moments: bad argument (NULL handle / out, or which not 0 / 1)");
+  AQ_TRY(aq_summary_ready(s));
+  const aq_pair_src src = aq_summary_src(s, which);
+  return aq_moments_device(src, aq_src_elements(src, 0), out);
+}
+extern "C" int aq_vb_order_stats(aq_vb_handle s, int32_t which, int32_t n_ranks, const int64_t *ranks, double *out, aq_moments *mom) {
+  AQ_TRY(aq_ranks_args("aq_vb_order_stats", s != nullptr && (which == 0 || which == 1), n_ranks, ranks, out));
+  AQ_TRY(aq_summary_ready(s));
+  const aq_pair_src src = aq_summary_src(s, which);
+  return aq_order_stats_device(src, aq_src_elements(src, 0), n_ranks, ranks, out, mom, "aq_vb_order_stats");
+}
+extern "C" int aq_order_stats(const double *x, int64_t len, int32_t n_ranks, const int64_t *ranks, double *out, aq_moments *mom,
+                              int32_t device) {
+  AQ_TRY(aq_ranks_args("aq_order_stats", x != nullptr && len >= 1, n_ranks, ranks, out));
+  AQ_TRY(aq_need_device(device));
+  double *d_x = nullptr;
+  AQ_HIP(hipMalloc((void **)&d_x, (size_t)len * sizeof(double)));
+  hipError_t e = hipMemcpy(d_x, x, (size_t)len * sizeof(double), hipMemcpyHostToDevice);
+  const aq_pair_src src{d_x, nullptr, 0, 0, 0, 0};
+  int rc = e == hipSuccess ? aq_order_stats_device(src, (size_t)len, n_ranks, ranks, out, mom, "aq_order_stats")
+                           : aq_fail(AQ_ERR_DEVICE, std::string("aq_order_stats: ") + hipGetErrorString(e));
+  hipFree(d_x);
+  return rc;
 }
 
 // ------------------------------------------------------ checkpoint / resume ----

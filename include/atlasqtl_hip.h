@@ -324,6 +324,45 @@ int aq_vb_bfdr_pairs(aq_vb_handle h, int64_t upto, int64_t tie_first, int64_t ta
                      double *ppi, double *beta);
 
 /* ------------------------------------------------------------------------------------------
+ * Order statistics and moments of the p x q posterior values, computed where they lie: the first block of
+ * summary.atlasqtl (R/summarise_output.R:89-97), summary(as.vector(gam_vb)) and summary(as.vector(beta_vb)) -- minimum,
+ * quartiles, mean, maximum -- without a p x q array leaving the device or being allocated on it.
+ *   which = 0   gam_vb of the handle (trait-tiled storage read in place; padding rows and traits are not values)
+ *   which = 1   beta_vb = gam_vb * mu_beta_vb (R/update_vb.R:17), one fp64 product per element formed on the fly
+ * Order: a double maps to a 64-bit key whose unsigned order is the order of the values (negative: all bits flipped;
+ * otherwise: sign bit set; -0.0 sorts just below +0.0).  NaN is not a value: it is counted in n_nan and left out of every
+ * histogram, order statistic and moment, as R's summary.default does with NA.
+ * The select is a radix select on AQ_RSEL_BITS-wide digits of the key, 64 / AQ_RSEL_BITS passes over the storage; its
+ * scratch is the histogram and one record per workgroup, nothing that grows with p q.
+ *   aq_vb_radix_hist   one step, the primitive a trait-sharded driver needs (histograms of disjoint shards add): for each
+ *                      of n_prefix (1 ... AQ_RSEL_MAX_PREFIX) prefixes, strictly ascending, the histogram of the digit at
+ *                      bit `shift` among the values whose key satisfies key >> (shift + AQ_RSEL_BITS) == prefix[i].
+ *                      shift + AQ_RSEL_BITS == 64: all values, n_prefix must be 1 and prefix is not read.
+ *                      hist: n_prefix x 2^AQ_RSEL_BITS counts, host.  One pass over the storage serves all prefixes.
+ *   aq_vb_moments      count, n_nan, min, max, sum over the non-NaN values in one pass.  sum is reproducible: fixed-order
+ *                      partial sums, no floating atomics -- two calls on one handle return the same bits.  No value:
+ *                      count = 0, min = +Inf, max = -Inf (the neutral elements, so that shards combine by min / max).
+ *   aq_vb_order_stats  the whole select: out[i] = the ranks[i]-th smallest value (0-based; ranks ascending, equal ones
+ *                      allowed; 1 <= n_ranks <= AQ_RSEL_MAX_PREFIX; each rank < count); mom may be NULL.
+ *   aq_order_stats     the same on a host array of len doubles (copied to the device as aq_assign_bfdr does).
+ * All four synchronise; the handle entries report an expired in-kernel wait (AQ_ERR_DEVICE) as aq_vb_get_result does.
+ * NULL handle / array / output, which not 0 / 1, n_ranks or n_prefix out of range, ranks negative or not ascending,
+ * prefixes not ascending, len < 1, shift not a multiple of AQ_RSEL_BITS in [0, 64): AQ_ERR_ARG, with the entry's name in
+ * aq_last_error(), before any device call; a rank >= count is AQ_ERR_ARG once the count is known.
+ * ---------------------------------------------------------------------------------------- */
+#define AQ_RSEL_BITS 8          /* digit width; divides 64.  8 passes, 256 bins x 8 B x 16 prefixes = 32 KB of LDS */
+#define AQ_RSEL_MAX_PREFIX 16
+typedef struct aq_moments {
+  int64_t count, n_nan;
+  double min, max, sum;
+} aq_moments;
+int aq_vb_radix_hist(aq_vb_handle h, int32_t which, int32_t n_prefix, const uint64_t *prefix, int32_t shift, int64_t *hist);
+int aq_vb_moments(aq_vb_handle h, int32_t which, aq_moments *out);
+int aq_vb_order_stats(aq_vb_handle h, int32_t which, int32_t n_ranks, const int64_t *ranks, double *out, aq_moments *mom);
+int aq_order_stats(const double *x, int64_t len, int32_t n_ranks, const int64_t *ranks, double *out, aq_moments *mom,
+                   int32_t device);
+
+/* ------------------------------------------------------------------------------------------
  * Checkpoint / resume.  The reference's checkpoint_ (R/utils.R:571-611, called at
  * R/atlasqtl_global_local_core.R:379) only writes outputs every 100 iterations and cannot resume; these
  * entries capture and restore the COMPLETE loop state between two sweeps (valid after aq_vb_run /
