@@ -1151,9 +1151,10 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
         // the register sets at 2 x 22 and 2 x 44 VGPRs.
         constexpr int NC = AQ_PT_DEG + 1, S = AQ_PT_NI, F = NC * S;
         // interval and local variable of v = |x|: i = floor(2 v) (clamped: a lane outside the tables reads the last interval
-        // and is redone below), x = 2 (2 v - i) - 1
+        // and is redone below), x = 2 (2 v - i) - 1.  The clamp is the last double below NI: every v inside the tables keeps its
+        // own t (a clamp at NI - 0.5 moved the lanes with 11.75 <= v < 12 of a wave that is not redone to the interval's centre)
         auto locate = [&](double x, double *xloc) __attribute__((always_inline)) {
-          const double t = fmin(fabs(x) * (1.0 / AQ_PT_W), AQ_PT_NI - 0.5);
+          const double t = fmin(fabs(x) * (1.0 / AQ_PT_W), AQ_PT_NI * (1.0 - 0x1p-53));
           const int i = (int)t;
           *xloc = fma(2.0, t - (double)i, -1.0);
           return ptab + i;

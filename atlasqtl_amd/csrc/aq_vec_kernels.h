@@ -58,6 +58,20 @@ __global__ void aq_k_build_x_layouts(const double *__restrict__ X, double2 *__re
   }
 }
 
+// x' y over n samples with compensated (Kahan) summation: the error stays at a few ulp for any n.  A plain running sum loses about
+// sqrt(n) ulp -- 5e-14 relative in the worst of 9000 entries at n = 4000 -- and with missing values the diagonal of these blocks is
+// X_norm_sq(j, k), which goes into mu_beta_vb and tau_vb entry by entry (tests/test_gpu_link_range.py, wide-c12-na).  Once per handle.
+__device__ __forceinline__ double aq_dot_kahan(const double *__restrict__ x, const double *__restrict__ y, int n) {
+  double s = 0.0, c = 0.0;
+  for (int r = 0; r < n; r++) {
+    const double t = x[r] * y[r] - c;
+    const double u = s + t;
+    c = (u - s) - t;
+    s = u;
+  }
+  return s;
+}
+
 // diagonal Gram blocks G[b] = X_b' X_b and first off-diagonal blocks Gx[b] = X_b' X_{b-1} (16 x 16 each):
 // the only parts of cp_X (R/atlasqtl_global_local_core.R:41) the blocked recursion needs
 __global__ void aq_k_gram_blocks(const double *__restrict__ X, double *__restrict__ G, double *__restrict__ Gx, int n,
@@ -68,20 +82,13 @@ __global__ void aq_k_gram_blocks(const double *__restrict__ X, double *__restric
   {   // cross block with the previous SNP block: Gx[b][i][j] = x_{16b+i}' x_{16(b-1)+j}
     int jp = 16 * (b - 1) + j;
     double sx = 0.0;
-    if (b > 0 && ji < p && jp < p) {
-      const double *xi = X + (size_t)n * ji, *xj = X + (size_t)n * jp;
-      for (int r = 0; r < n; r++) sx += xi[r] * xj[r];
-    }
+    if (b > 0 && ji < p && jp < p) sx = aq_dot_kahan(X + (size_t)n * ji, X + (size_t)n * jp, n);
     Gx[(size_t)b * 256 + threadIdx.x] = sx;
   }
   double s = 0.0;
-  if (ji < p && jj < p) {
-    const double *xi = X + (size_t)n * ji, *xj = X + (size_t)n * jj;
-    if (i <= j) {
-      for (int r = 0; r < n; r++) s += xi[r] * xj[r];
-    } else {
-      for (int r = 0; r < n; r++) s += xj[r] * xi[r];
-    }
+  if (ji < p && jj < p) {     // (the smaller index first: G stays exactly symmetric)
+    const int lo = i <= j ? ji : jj, hi = i <= j ? jj : ji;
+    s = aq_dot_kahan(X + (size_t)n * lo, X + (size_t)n * hi, n);
   }
   G[(size_t)b * 256 + threadIdx.x] = s;
 }

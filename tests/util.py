@@ -22,6 +22,116 @@ def make_problem(n, p, q, p_act=10, seed=123, init_seed=456, maf=0.2, p0=(5, 25)
     return dict(X=X, Y=Y, list_hyper=lh, list_init=li, truth=d, n=n, p=pp, q=q)
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# Inputs that drive the probit link u = theta_j + zeta_k over its whole domain (tests/test_link_coverage_host.py asserts what
+# they cover, tests/test_gpu_link_range.py runs them).  The constants restate atlasqtl_amd/csrc/aq_probit_tab.h.
+LINK_W, LINK_NI, LINK_R = 0.5, 24, 12.0     # AQ_PT_W, AQ_PT_NI, AQ_PT_R: 24 intervals of width 1/2 on |u| < 12, a series beyond
+LINK_GROUP = 16                             # a helper wave stages 16 SNPs x 16 traits: the wave votes on "all lanes in the tables"
+LINK_EDGES = (0.5, 3.0, 6.5, 11.5, 12.0)    # interval boundaries that also get their two floating-point neighbours, on both signs
+
+
+def _link_coarse(m, spread, fine):
+    """m values in +-spread in groups of LINK_GROUP: groups whose every |value| <= 12 - fine - 1/16 (with a fine part in +-fine
+    every u is inside the tables, up to |u| = 12 - 1/16), groups that hold values on both sides of |u| = 12, groups whose every |value| >= 14, and the ragged
+    rest inside.  Neighbours inside the tables, and in the tail up to |u| = 21, are at most 2 fine apart, so that with the fine
+    part u leaves no gap there (21 = 12 / sqrt(1/3): sqrt(c) u of the ladders in use still meets every interval).  All values
+    are multiples of 1/64, so that value + fine part is exact."""
+    if spread < 14.0:
+        raise ValueError("make_link_problem: spread must be at least 14 (the tail groups start there)")
+    full = m // LINK_GROUP
+    if full < 3:
+        raise ValueError("make_link_problem: the spread axis needs at least three full groups of 16")
+    n_mix, n_out = max(1, full // 4), max(1, (full + 1) // 3)
+    n_in = m - LINK_GROUP * (n_out + n_mix)
+    n_neg = (3 * n_in + 2) // 5                       # the negative side gets the denser grid: A is odd, and gam_vb saturates at 1
+    top = LINK_R - fine - 1.0 / 16.0                   # an all-inside wave reaches |u| = 12 - 1/16: the last interval's upper half
+    inside = np.concatenate([[-top], np.linspace(-10.5, -0.5, n_neg - 1), np.linspace(0.0, 10.0, n_in - n_neg - 1), [top]])
+    mixed = np.array([-13.0, -12.5, -12.0, -11.5, -11.0, 11.0, 11.5, 12.0, 12.5, 13.0, -6.25, -2.75, 3.5, -8.75, -12.25, -11.75])
+    mixed = np.concatenate([mixed + g / 16.0 * np.sign(mixed) * (np.abs(mixed) < 11.0) for g in range(n_mix)])
+    nt = 8 * n_out
+    near = np.arange(14.0, 21.0 + 2.0 * fine, 2.0 * fine)
+    if spread >= near[-1] + 3.0 and nt >= near.size + 3:
+        mag = np.concatenate([near, np.linspace(near[-1] + 2.0, spread, nt - near.size)])
+    else:
+        mag = np.linspace(14.0, spread, nt)
+    tail = np.concatenate([np.concatenate([-mag[g::n_out], mag[g::n_out]]) for g in range(n_out)])
+    ragged = m - LINK_GROUP * full
+    v = np.concatenate([inside[:n_in - ragged], mixed, tail, inside[n_in - ragged:]])
+    assert v.size == m
+    v = np.round(v * 64.0) / 64.0
+    if np.max(np.diff(np.sort(v[np.abs(v) <= LINK_R]))) > 2.0 * fine:
+        raise ValueError("make_link_problem: too few entries on the spread axis to cover the tables with this fine range")
+    return v
+
+
+def _link_fine(m, coarse, fine, rng):
+    """m values in [-fine, fine]: the differences that put u exactly on every interval boundary k/2 (0 and +-12 among them) and
+    on the two floating-point neighbours of +-LINK_EDGES (so nextafter(+-12, 0) too), a dyadic grid, and seeded multiples
+    of 2^-10; shuffled, so that the special values are spread over the SNP blocks / trait tiles."""
+    targets = [k * LINK_W for k in range(-LINK_NI, LINK_NI + 1)]
+    targets += [np.nextafter(s * e, toward) for e in LINK_EDGES for s in (-1.0, 1.0) for toward in (-np.inf, np.inf)]
+    special = []
+    for t in targets:
+        c = coarse[np.argmin(np.abs(coarse - t))]
+        f = t - c
+        if abs(f) > fine or f + c != t:
+            raise ValueError(f"make_link_problem: cannot place u = {t!r} exactly")
+        special.append(f)
+    left = m - len(special)
+    step = next((s for s in (32, 16, 8, 4) if 2 * s + 1 <= left), None)
+    if step is None:
+        raise ValueError(f"make_link_problem: the fine axis needs at least {len(special) + 9} entries")
+    grid = np.arange(-step, step + 1) / float(step) * fine
+    rest = np.round(rng.integers(-1024, 1025, size=left - grid.size) * fine) / 1024.0
+    v = np.concatenate([special, grid, rest])
+    return v[rng.permutation(m)]
+
+
+def make_link_problem(n, p, q, spread_axis="zeta", spread=38.0, fine=0.5, fine_scale=1.0, link_seed=7, **kw):
+    """make_problem(n, p, q, **kw) with list_init["theta_vb"] and list_init["zeta_vb"] -- and nothing else -- replaced, so that
+    u = theta_j + zeta_k covers the whole domain of the probit link: every one of the 24 table intervals on both signs, the
+    boundaries k/2 exactly, +-12 and their neighbours, u = 0, and both tails out to +-(spread + fine).  spread_axis = "zeta":
+    the spread is in zeta (trait tiles of 16: inside the tables / mixed / outside) and |theta_j| <= fine, which the annealed
+    horseshoe update of the oracle needs; "theta": the spread is in theta (SNP blocks of 16) and
+    |zeta_k| <= fine.  fine_scale < 1 shrinks the fine part after it is laid out, for the drivers whose reference formulas
+    need a still smaller |theta_j|: u then misses most of the exact boundaries and leaves gaps between neighbours (what it
+    still covers is asserted case by case in tests/test_link_coverage_host.py)."""
+    if spread_axis not in ("zeta", "theta"):
+        raise ValueError("spread_axis must be 'zeta' or 'theta'")
+    prob = make_problem(n, p, q, **kw)
+    rng = np.random.default_rng(link_seed)
+    m_coarse, m_fine = (q, prob["p"]) if spread_axis == "zeta" else (prob["p"], q)
+    coarse = _link_coarse(m_coarse, float(spread), float(fine))
+    small = _link_fine(m_fine, coarse, float(fine), rng) * float(fine_scale)
+    li = dict(prob["list_init"])
+    li["zeta_vb"], li["theta_vb"] = (coarse, small) if spread_axis == "zeta" else (small, coarse)
+    prob["list_init"] = li
+    prob["spread_axis"] = spread_axis
+    return prob
+
+
+def link_interval(x):
+    """Signed index of the table interval that holds x: +-(1 + floor(2 |x|)) for |x| < 12, +-(LINK_NI + 1) for the tails, 0 for
+    x = 0 exactly -- locate() of aq_core_sweep_la.h, by sign."""
+    x = np.asarray(x, dtype=np.float64)
+    i = np.minimum(np.floor(np.abs(x) / LINK_W), LINK_NI).astype(np.int64) + 1
+    return np.where(x == 0.0, 0, np.sign(x).astype(np.int64) * i)
+
+
+def link_wave_classes(theta, zeta, sqrt_c=1.0):
+    """The vote of every helper wave (SNP block x trait tile): 0 = every lane inside the tables, 1 = mixed, 2 = every lane
+    outside.  Returns the (blocks x tiles) array."""
+    u = theta[:, None] + zeta[None, :]
+    inr = (np.abs(u) < LINK_R) & (np.abs(sqrt_c * u) < LINK_R)
+    nb, nt = -(-u.shape[0] // LINK_GROUP), -(-u.shape[1] // LINK_GROUP)
+    out = np.empty((nb, nt), dtype=np.int64)
+    for b in range(nb):
+        for t in range(nt):
+            w = inr[LINK_GROUP * b:LINK_GROUP * (b + 1), LINK_GROUP * t:LINK_GROUP * (t + 1)]
+            out[b, t] = 0 if w.all() else (2 if not w.any() else 1)
+    return out
+
+
 def operator_inputs(p, q, n=60, seed=0, mis=False, c=1.0):
     """Random but well-formed inputs of coreDualLoop / coreDualMisLoop (R layout)."""
     rng = np.random.default_rng(seed)
