@@ -44,6 +44,11 @@ class AqPrepInput(C.Structure):
                 ("device", C.c_int32)]
 
 
+class AqPrepBedInput(C.Structure):
+    _fields_ = [("n_file", C.c_int32), ("n", C.c_int32), ("p", C.c_int32), ("q", C.c_int32), ("bed", C.POINTER(C.c_uint8)),
+                ("sample_idx", ip), ("Y", dp), ("count_a2", C.c_int32), ("missing", C.c_int32), ("device", C.c_int32)]
+
+
 class AqVbMultiOut(C.Structure):
     _fields_ = [
         ("beta_vb", dp), ("gam_vb", dp), ("mu_beta_vb", dp), ("theta_vb", dp), ("zeta_vb", dp), ("lam2_inv_vb", dp),
@@ -127,6 +132,8 @@ SYMBOLS = {
     "aq_special_eval_device": (C.c_int, [C.c_int32, dp, dp, dp, C.c_int64, C.c_int32]),
     "aq_q_approx_vec": (C.c_int, [dp, dp, C.c_int64, ip]),
     "aq_vb_debug_raise_errflag": (C.c_int, [C.c_void_p]),
+    "aq_prepare_data_bed": (C.c_int, [C.POINTER(AqPrepBedInput), C.POINTER(C.c_void_p)]),
+    "aq_prep_genotype_counts": (C.c_int, [C.c_void_p, ip]),
 }
 
 _lib = None

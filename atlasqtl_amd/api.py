@@ -66,6 +66,10 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
              sparse_output=None):
     """R/atlasqtl.R:179-322.
 
+    X: a float64 matrix, int8 dosages, or a plink.PlinkBed (a PLINK 1 .bed / .bim / .fam fileset, unpacked on the GPU): the
+    predictors are then named by the .bim's variant IDs and the result carries `genotype_counts` (4 x p int32: homozygous
+    A1, heterozygous, homozygous A2, missing, per variant given, over the samples used).
+
     sparse_output = {"thres": 0.5, "fdr_adjust": False, "max_pairs": None} (missing keys take these values): instead of
     the p x q gam_vb / beta_vb, return what summary.atlasqtl reads off them (R/summarise_output.R:99-106) -- `assoc`, the
     table of pairs with gam_vb > thres (or assign_bFDR(gam_vb) < thres) with snp / trait indices and names, ppi, beta and
@@ -112,6 +116,8 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
     res["rmvd_cst_x"] = dat["rmvd_cst_x"]
     res["rmvd_coll_x"] = dat["rmvd_coll_x"]
     res["names_x"], res["names_y"] = dat["names_x"], dat["names_y"]
+    if dat["genotype_counts"] is not None:                # X = PlinkBed: 4 x p (hom A1, het, hom A2, missing), before removals
+        res["genotype_counts"] = dat["genotype_counts"]
     names_snp = dat["names_x"]
     if sparse is not None:
         if sparse["summary"]:

@@ -7,6 +7,8 @@
 // X arrives as fp64 or as int8 dosages (0 / 1 / 2 ...: 1 byte per genotype, "block-standardised genotype X" of BASELINE.json
 // configs[4]): at C5 that is 1 GB over PCIe instead of 8 GB, and the fp64 matrix never exists on the host.  The result stays
 // on the device (compact n x p_kept fp64 + centred Y) and is handed to aq_vb_create as device pointers.
+// aq_prepare_data_bed takes the genotypes as a PLINK 1 .bed stores them, 2 bits each: the packed blocks are uploaded (a
+// quarter of the int8 bytes) and one decode pass unpacks them into the int8 buffer that the same pipeline then reads.
 // All of it is HBM-bound streaming: one read of X for the column statistics, one read + one write for the standardised
 // matrix with its column hashes, one gather pass for the compaction.
 #include <hip/hip_runtime.h>
@@ -28,6 +30,7 @@ struct aq_prep {
   std::vector<uint8_t> bool_cst, bool_coll;   // p each (bool_coll in the ORIGINAL column numbering)
   std::vector<int32_t> dup_of;                // original index of the kept column a removed duplicate equals, else -1
   std::vector<double> mean, sd;               // p each
+  std::vector<int32_t> gcounts;               // 4 x p (hom A1, het, hom A2, missing): aq_prepare_data_bed only
 };
 
 #define AQR_HIP(call)                                                                                        \
@@ -166,12 +169,11 @@ __global__ __launch_bounds__(256) void aq_k_centre_y(const double *__restrict__ 
   if (threadIdx.x == 0) nobs[blockIdx.x] = (int)c;
 }
 
+// everything from a device-resident n x p matrix on: column statistics, hashes, duplicate confirmation, compact standardise
 template <typename T>
-static int aq_prepare_x(aq_prep *h, const T *X_host) {
+static int aq_prepare_x_device(aq_prep *h, const T *dX) {
   int rc = AQ_OK;
   const int n = h->n, p = h->p;
-  const size_t np = (size_t)n * p;
-  T *dX = nullptr;
   double *dmean = nullptr, *dsd = nullptr;
   uint8_t *dcst = nullptr;
   unsigned long long *dhash = nullptr;
@@ -179,8 +181,6 @@ static int aq_prepare_x(aq_prep *h, const T *X_host) {
   std::vector<unsigned long long> hash((size_t)2 * p);
   std::vector<int> dst(p, -1);
   {
-    AQR_HIP(hipMalloc((void **)&dX, np * sizeof(T)));
-    AQR_HIP(hipMemcpy(dX, X_host, np * sizeof(T), hipMemcpyHostToDevice));
     AQR_HIP(hipMalloc((void **)&dmean, (size_t)p * sizeof(double)));
     AQR_HIP(hipMalloc((void **)&dsd, (size_t)p * sizeof(double)));
     AQR_HIP(hipMalloc((void **)&dcst, (size_t)p));
@@ -262,7 +262,6 @@ static int aq_prepare_x(aq_prep *h, const T *X_host) {
     AQR_HIP(hipDeviceSynchronize());
   }
 done:
-  if (dX) hipFree(dX);
   if (dmean) hipFree(dmean);
   if (dsd) hipFree(dsd);
   if (dcst) hipFree(dcst);
@@ -270,6 +269,20 @@ done:
   if (ddst) hipFree(ddst);
   if (dpairs) hipFree(dpairs);
   if (dout) hipFree(dout);
+  return rc;
+}
+
+// brings the host matrix to the device and runs the pipeline on it
+template <typename T>
+static int aq_prepare_x(aq_prep *h, const T *X_host) {
+  int rc = AQ_OK;
+  const size_t np = (size_t)h->n * h->p;
+  T *dX = nullptr;
+  AQR_HIP(hipMalloc((void **)&dX, np * sizeof(T)));
+  AQR_HIP(hipMemcpy(dX, X_host, np * sizeof(T), hipMemcpyHostToDevice));
+  rc = aq_prepare_x_device<T>(h, dX);
+done:
+  if (dX) hipFree(dX);
   return rc;
 }
 
@@ -281,42 +294,38 @@ extern "C" void aq_prep_destroy(aq_prep_handle h) {
   delete h;
 }
 
-extern "C" int aq_prepare_data(const aq_prep_input *in, aq_prep_handle *out) {
-  if (!in || !out) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data: NULL argument");
-  *out = nullptr;
-  if (in->n < 2 || in->p < 1 || in->q < 1) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data: n >= 2, p >= 1, q >= 1 required");
-  if ((!in->X && !in->X_i8) || !in->Y) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data: NULL data pointer");
+static int aq_check_device(int device) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return aq_fail_ext(AQ_ERR_DEVICE, "no HIP device visible: libatlasqtl_hip has no CPU fallback (MI355X / gfx950 required)");
-  if (in->device < 0 || in->device >= ndev) return aq_fail_ext(AQ_ERR_ARG, "device ordinal out of range");
-  if (hipSetDevice(in->device) != hipSuccess) return aq_fail_ext(AQ_ERR_DEVICE, "hipSetDevice failed");
-  const size_t np = (size_t)in->n * in->p, nq = (size_t)in->n * in->q;
-  if (in->X)
-    for (size_t i = 0; i < np; i++)   // check_structure_(X, "matrix", "numeric"): no NA, finite (R/utils.R:34-100)
-      if (!std::isfinite(in->X[i])) return aq_fail_ext(AQ_ERR_ARG, "X must be a non-empty a numeric matrix, finite without missing value.");
-  aq_prep *h = new aq_prep();
-  h->n = in->n; h->p = in->p; h->q = in->q; h->device = in->device;
-  int rc = in->X ? aq_prepare_x<double>(h, in->X) : aq_prepare_x<int8_t>(h, in->X_i8);
+  if (device < 0 || device >= ndev) return aq_fail_ext(AQ_ERR_ARG, "device ordinal out of range");
+  if (hipSetDevice(device) != hipSuccess) return aq_fail_ext(AQ_ERR_DEVICE, "hipSetDevice failed");
+  return AQ_OK;
+}
+
+// Y <- scale(Y, center = TRUE, scale = FALSE) into h->Yc and the two missingness guards (R/prepare_atlasqtl.R:39-45, :83)
+static int aq_prepare_y(aq_prep *h, const double *Y_host) {
+  int rc = AQ_OK;
+  const int n = h->n, q = h->q;
+  const size_t nq = (size_t)n * q;
   double *dY = nullptr;
   int *dnobs = nullptr;
-  std::vector<int> nobs(in->q);
-  if (rc != AQ_OK) goto done;
+  std::vector<int> nobs(q);
   AQR_HIP(hipMalloc((void **)&dY, nq * sizeof(double)));
   AQR_HIP(hipMalloc((void **)&h->Yc, nq * sizeof(double)));
-  AQR_HIP(hipMalloc((void **)&dnobs, (size_t)in->q * sizeof(int)));
-  AQR_HIP(hipMemcpy(dY, in->Y, nq * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(aq_k_centre_y, dim3(in->q), dim3(256), 0, 0, dY, in->n, h->Yc, dnobs);
+  AQR_HIP(hipMalloc((void **)&dnobs, (size_t)q * sizeof(int)));
+  AQR_HIP(hipMemcpy(dY, Y_host, nq * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(aq_k_centre_y, dim3(q), dim3(256), 0, 0, dY, n, h->Yc, dnobs);
   AQR_HIP(hipGetLastError());
   AQR_HIP(hipMemcpy(nobs.data(), dnobs, nobs.size() * sizeof(int), hipMemcpyDeviceToHost));
   {
     long long tot = 0;
     std::string low;
-    for (int k = 0; k < in->q; k++) {
+    for (int k = 0; k < q; k++) {
       tot += nobs[k];
-      if ((double)nobs[k] / in->n < 0.025) low += (low.empty() ? "" : " ") + std::to_string(k + 1);
+      if ((double)nobs[k] / n < 0.025) low += (low.empty() ? "" : " ") + std::to_string(k + 1);
     }
-    if ((double)tot / ((double)in->n * in->q) < 0.05) { rc = aq_fail_ext(AQ_ERR_ARG, "Too few non-NA values in matrix Y. Exit."); goto done; }
+    if ((double)tot / ((double)n * q) < 0.05) { rc = aq_fail_ext(AQ_ERR_ARG, "Too few non-NA values in matrix Y. Exit."); goto done; }
     if (!low.empty()) {
       rc = aq_fail_ext(AQ_ERR_ARG, "Column(s) " + low + " of matrix Y have more than 97.5% missing values, and should be removed. Exit.");
       goto done;
@@ -325,8 +334,241 @@ extern "C" int aq_prepare_data(const aq_prep_input *in, aq_prep_handle *out) {
 done:
   if (dY) hipFree(dY);
   if (dnobs) hipFree(dnobs);
+  return rc;
+}
+
+extern "C" int aq_prepare_data(const aq_prep_input *in, aq_prep_handle *out) {
+  if (!in || !out) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data: NULL argument");
+  *out = nullptr;
+  if (in->n < 2 || in->p < 1 || in->q < 1) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data: n >= 2, p >= 1, q >= 1 required");
+  if ((!in->X && !in->X_i8) || !in->Y) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data: NULL data pointer");
+  if (int rc = aq_check_device(in->device)) return rc;
+  const size_t np = (size_t)in->n * in->p;
+  if (in->X)
+    for (size_t i = 0; i < np; i++)   // check_structure_(X, "matrix", "numeric"): no NA, finite (R/utils.R:34-100)
+      if (!std::isfinite(in->X[i])) return aq_fail_ext(AQ_ERR_ARG, "X must be a non-empty a numeric matrix, finite without missing value.");
+  aq_prep *h = new aq_prep();
+  h->n = in->n; h->p = in->p; h->q = in->q; h->device = in->device;
+  int rc = in->X ? aq_prepare_x<double>(h, in->X) : aq_prepare_x<int8_t>(h, in->X_i8);
+  if (rc == AQ_OK) rc = aq_prepare_y(h, in->Y);
   if (rc != AQ_OK) { aq_prep_destroy(h); return rc; }
   *out = h;
+  return AQ_OK;
+}
+
+// ---- PLINK 1 .bed input: 2 bits per genotype, unpacked on the device (include/atlasqtl_hip.h, aq_prepare_data_bed) ----
+#define AQ_BED_NA (-128)   // a missing genotype in the int8 dosage buffer (never a dosage)
+
+// four 2-bit codes (one .bed byte) -> four dosage bytes, the missing code (1) -> AQ_BED_NA
+__device__ __forceinline__ uint32_t aq_bed_dosage4(uint32_t b, int count_a2) {
+  uint32_t x = b & 0xffu;
+  x = (x | (x << 12)) & 0x000f000fu;
+  x = (x | (x << 6)) & 0x03030303u;            // code s in byte s
+  const uint32_t H = (x >> 1) & 0x01010101u, L = x & 0x01010101u;
+  const uint32_t M = L & ~H;                   // missing
+  uint32_t d = H + (H & L);                    // A2 dosage: 0 (hom A1), 1 (het), 2 (hom A2)
+  if (!count_a2) d = 0x02020202u - d;          // A1 dosage (every byte <= 2: no borrow between bytes)
+  return (d & ~(M * 0xffu)) | (M << 7);
+}
+
+__device__ __forceinline__ int8_t aq_bed_dosage1(uint32_t code, int count_a2) {
+  if (code == 1) return (int8_t)AQ_BED_NA;
+  const int a2 = (int)(code >> 1) + (int)(code == 3);
+  return (int8_t)(count_a2 ? a2 : 2 - a2);
+}
+
+__device__ __forceinline__ int aq_wave_sum(int v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Decode without sample selection: one wave per variant, four variants per workgroup.  The dosage column j starts at byte
+// j n of G, its packed block at byte j stride of bed: neither is aligned in general.  The column is cut where its OUTPUT is
+// 16-byte aligned: a lane takes 16 genotypes = 32 bits of the block, at any bit offset, out of two aligned dwords (the
+// buffer is padded so that both exist) and writes one aligned 16-byte vector; the up to 15 genotypes before the first and
+// after the last full vector go one per lane.  The four codes are counted on the packed words (popcount), summed over the
+// wave and written by one lane.  All offsets are 64-bit.
+__global__ __launch_bounds__(256) void aq_k_bed_decode(const uint32_t *__restrict__ bed32, long long stride, int n, int p,
+                                                      int count_a2, int8_t *__restrict__ G, int32_t *__restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  const long long j = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= p) return;
+  const uint8_t *bed8 = (const uint8_t *)bed32;
+  const long long out0 = j * (long long)n, in0 = j * stride;
+  const int lead = (int)min((long long)n, (16 - (out0 & 15)) & 15);
+  const int nvec = (n - lead) >> 4;
+  const int tail0 = lead + (nvec << 4);
+  int c_het = 0, c_hom2 = 0, c_mis = 0;
+  for (int k = lane; k < nvec; k += 64) {
+    const int s0 = lead + (k << 4);
+    const long long bit = (in0 << 3) + ((long long)s0 << 1);
+    const long long di = bit >> 5;
+    const int sh = (int)(bit & 31);
+    const unsigned long long ww = ((unsigned long long)bed32[di + 1] << 32) | bed32[di];
+    const uint32_t w = (uint32_t)(ww >> sh);
+    const uint32_t lo = w & 0x55555555u, hi = (w >> 1) & 0x55555555u;
+    c_mis += __popc(lo & ~hi);
+    c_het += __popc(hi & ~lo);
+    c_hom2 += __popc(hi & lo);
+    uint4 v;
+    v.x = aq_bed_dosage4(w, count_a2);
+    v.y = aq_bed_dosage4(w >> 8, count_a2);
+    v.z = aq_bed_dosage4(w >> 16, count_a2);
+    v.w = aq_bed_dosage4(w >> 24, count_a2);
+    *reinterpret_cast<uint4 *>(G + out0 + s0) = v;
+  }
+  const int nsingle = lead + (n - tail0);       // <= 30
+  if (lane < nsingle) {
+    const int s = lane < lead ? lane : tail0 + (lane - lead);
+    const uint32_t code = (bed8[in0 + (s >> 2)] >> (2 * (s & 3))) & 3u;
+    c_mis += (code == 1); c_het += (code == 2); c_hom2 += (code == 3);
+    G[out0 + s] = aq_bed_dosage1(code, count_a2);
+  }
+  c_mis = aq_wave_sum(c_mis); c_het = aq_wave_sum(c_het); c_hom2 = aq_wave_sum(c_hom2);
+  if (lane == 0) {
+    int32_t *c = counts + 4 * j;
+    c[0] = n - c_mis - c_het - c_hom2; c[1] = c_het; c[2] = c_hom2; c[3] = c_mis;
+  }
+}
+
+// Decode with sample selection: row i of the column is file sample idx[i], gathered bytewise out of the variant's block
+__global__ __launch_bounds__(256) void aq_k_bed_gather(const uint8_t *__restrict__ bed8, long long stride, int n, int p,
+                                                      const int32_t *__restrict__ idx, int count_a2, int8_t *__restrict__ G,
+                                                      int32_t *__restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  const long long j = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= p) return;
+  const long long out0 = j * (long long)n, in0 = j * stride;
+  int c_het = 0, c_hom2 = 0, c_mis = 0;
+  for (int i = lane; i < n; i += 64) {
+    const int s = idx[i];
+    const uint32_t code = (bed8[in0 + (s >> 2)] >> (2 * (s & 3))) & 3u;
+    c_mis += (code == 1); c_het += (code == 2); c_hom2 += (code == 3);
+    G[out0 + i] = aq_bed_dosage1(code, count_a2);
+  }
+  c_mis = aq_wave_sum(c_mis); c_het = aq_wave_sum(c_het); c_hom2 = aq_wave_sum(c_hom2);
+  if (lane == 0) {
+    int32_t *c = counts + 4 * j;
+    c[0] = n - c_mis - c_het - c_hom2; c[1] = c_het; c[2] = c_hom2; c[3] = c_mis;
+  }
+}
+
+// int8 dosages -> fp64 with the variant's own value (fill[j]) in place of a missing genotype
+__global__ __launch_bounds__(256) void aq_k_bed_impute(const int8_t *__restrict__ G, int n, const double *__restrict__ fill,
+                                                      double *__restrict__ X) {
+  const size_t base = (size_t)blockIdx.x * n;
+  const double f = fill[blockIdx.x];
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int8_t g = G[base + i];
+    X[base + i] = g == (int8_t)AQ_BED_NA ? f : (double)g;
+  }
+}
+
+// the decode pass: packed blocks -> *dG_out (n x p int8, AQ_BED_NA = missing) and h->gcounts
+static int aq_bed_decode(aq_prep *h, const aq_prep_bed_input *in, int8_t **dG_out) {
+  int rc = AQ_OK;
+  const int n = h->n, p = h->p;
+  const size_t stride = ((size_t)in->n_file + 3) / 4, nbytes = (size_t)p * stride;
+  uint32_t *dbed = nullptr;
+  int32_t *didx = nullptr, *dcnt = nullptr;
+  const unsigned grid = (unsigned)(((long long)p + 3) / 4);
+  // two dwords of padding: the aligned pair a lane reads may end one dword past the last block (those bits are shifted out)
+  AQR_HIP(hipMalloc((void **)&dbed, (nbytes / 4 + 3) * 4));
+  AQR_HIP(hipMemcpy(dbed, in->bed, nbytes, hipMemcpyHostToDevice));
+  AQR_HIP(hipMalloc((void **)dG_out, (size_t)n * p));
+  AQR_HIP(hipMalloc((void **)&dcnt, (size_t)4 * p * sizeof(int32_t)));
+  if (in->sample_idx) {
+    AQR_HIP(hipMalloc((void **)&didx, (size_t)n * sizeof(int32_t)));
+    AQR_HIP(hipMemcpy(didx, in->sample_idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(aq_k_bed_gather, dim3(grid), dim3(256), 0, 0, (const uint8_t *)dbed, (long long)stride, n, p, didx,
+                       in->count_a2, *dG_out, dcnt);
+  } else {
+    hipLaunchKernelGGL(aq_k_bed_decode, dim3(grid), dim3(256), 0, 0, dbed, (long long)stride, n, p, in->count_a2, *dG_out, dcnt);
+  }
+  AQR_HIP(hipGetLastError());
+  h->gcounts.resize((size_t)4 * p);
+  AQR_HIP(hipMemcpy(h->gcounts.data(), dcnt, h->gcounts.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+done:
+  if (dbed) hipFree(dbed);
+  if (didx) hipFree(didx);
+  if (dcnt) hipFree(dcnt);
+  return rc;
+}
+
+extern "C" int aq_prepare_data_bed(const aq_prep_bed_input *in, aq_prep_handle *out) {
+  if (!in || !out) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: NULL argument");
+  *out = nullptr;
+  if (in->n < 2 || in->p < 1 || in->q < 1) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: n >= 2, p >= 1, q >= 1 required");
+  if (!in->bed || !in->Y) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: NULL data pointer");
+  if (in->n > in->n_file)
+    return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: n = " + std::to_string(in->n) + " rows asked of a file with n_file = " +
+                                       std::to_string(in->n_file) + " samples");
+  if (!in->sample_idx && in->n != in->n_file)
+    return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: sample_idx is NULL, so n = " + std::to_string(in->n) +
+                                       " must equal n_file = " + std::to_string(in->n_file));
+  if (in->sample_idx)
+    for (int i = 0; i < in->n; i++)
+      if (in->sample_idx[i] < 0 || in->sample_idx[i] >= in->n_file)
+        return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: sample_idx[" + std::to_string(i) + "] = " +
+                                           std::to_string(in->sample_idx[i]) + " is out of range [0, " + std::to_string(in->n_file) + ")");
+  if ((in->count_a2 != 0 && in->count_a2 != 1) || (in->missing != 0 && in->missing != 1))
+    return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: count_a2 and missing must be 0 or 1");
+  if (int rc = aq_check_device(in->device)) return rc;
+  aq_prep *h = new aq_prep();
+  h->n = in->n; h->p = in->p; h->q = in->q; h->device = in->device;
+  int rc = AQ_OK;
+  int8_t *dG = nullptr;
+  double *dX = nullptr, *dfill = nullptr;
+  long long n_mis = 0, p_mis = 0, first_mis = -1;
+  rc = aq_bed_decode(h, in, &dG);
+  if (rc != AQ_OK) goto done;
+  for (int j = 0; j < in->p; j++) {
+    const int m = h->gcounts[4 * (size_t)j + 3];
+    if (m > 0) { n_mis += m; p_mis++; if (first_mis < 0) first_mis = j; }
+  }
+  if (n_mis == 0) {
+    rc = aq_prepare_x_device<int8_t>(h, dG);
+  } else if (!in->missing) {
+    rc = aq_fail_ext(AQ_ERR_ARG, "X must be a non-empty a numeric matrix, finite without missing value. " + std::to_string(n_mis) +
+                                     " genotype(s) in " + std::to_string(p_mis) + " variant(s) are missing among the " +
+                                     std::to_string(in->n) + " samples used; the first such variant has index " +
+                                     std::to_string(first_mis) + " (0-based, among the variants given). missing = \"mean\" replaces "
+                                     "a missing genotype by the mean of its variant's observed ones.");
+  } else {
+    std::vector<double> fill(in->p);
+    for (int j = 0; j < in->p; j++) {   // (n_het + 2 n_hom_counted) / n_obs: one fp64 division of exact integers
+      const int32_t *c = &h->gcounts[4 * (size_t)j];
+      const int n_obs = c[0] + c[1] + c[2];
+      fill[j] = n_obs > 0 ? (double)(c[1] + 2 * (long long)(in->count_a2 ? c[2] : c[0])) / (double)n_obs : 0.0;
+    }
+    AQR_HIP(hipMalloc((void **)&dfill, (size_t)in->p * sizeof(double)));
+    AQR_HIP(hipMemcpy(dfill, fill.data(), (size_t)in->p * sizeof(double), hipMemcpyHostToDevice));
+    AQR_HIP(hipMalloc((void **)&dX, (size_t)in->n * in->p * sizeof(double)));
+    hipLaunchKernelGGL(aq_k_bed_impute, dim3(in->p), dim3(256), 0, 0, dG, in->n, dfill, dX);
+    AQR_HIP(hipGetLastError());
+    AQR_HIP(hipDeviceSynchronize());
+    hipFree(dG); dG = nullptr;
+    rc = aq_prepare_x_device<double>(h, dX);
+  }
+  if (rc == AQ_OK) {
+    if (dG) { hipFree(dG); dG = nullptr; }
+    if (dX) { hipFree(dX); dX = nullptr; }
+    rc = aq_prepare_y(h, in->Y);
+  }
+done:
+  if (dG) hipFree(dG);
+  if (dX) hipFree(dX);
+  if (dfill) hipFree(dfill);
+  if (rc != AQ_OK) { aq_prep_destroy(h); return rc; }
+  *out = h;
+  return AQ_OK;
+}
+
+extern "C" int aq_prep_genotype_counts(aq_prep_handle h, int32_t *counts) {
+  if (!h || !counts) return aq_fail_ext(AQ_ERR_ARG, "aq_prep_genotype_counts: NULL argument");
+  if (h->gcounts.empty())
+    return aq_fail_ext(AQ_ERR_ARG, "aq_prep_genotype_counts: the handle was not made by aq_prepare_data_bed");
+  std::copy(h->gcounts.begin(), h->gcounts.end(), counts);
   return AQ_OK;
 }
 

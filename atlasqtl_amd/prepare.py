@@ -110,9 +110,10 @@ class PreparedData:
     """The standardised compact X (n x p) and the centred Y resident on the GPU (aq_prepare_data).  VbRun takes it in place
     of the X array; `Y` is the host copy of the centred responses (n x q, small) that the hyper-parameter rules need."""
 
-    def __init__(self, handle, n, p, q, Y, device):
+    def __init__(self, handle, n, p, q, Y, device, genotype_counts=None):
         self.handle, self.n, self.p, self.q, self.Y, self.device = handle, n, p, q, Y, device
         self.shape = (n, p)
+        self.genotype_counts = genotype_counts      # 4 x p_given int32 (hom A1, het, hom A2, missing): PlinkBed input only
 
     @property
     def x_ptr(self):
@@ -141,11 +142,16 @@ class PreparedData:
 
 def prepare_on_device(Y, X, device=0):
     """scale(X), constant / duplicate-column removal and the centring of Y on the GPU (R/prepare_atlasqtl.R:57-83).
-    X: float64 (n x p) or int8 dosages (1 byte per genotype: the fp64 matrix is then never formed on the host).
+    X: float64 (n x p), int8 dosages (1 byte per genotype: the fp64 matrix is then never formed on the host), or a
+    plink.PlinkBed (2 bits per genotype: the packed blocks of the .bed are uploaded and unpacked on the GPU; the returned
+    PreparedData then carries genotype_counts).
     Returns (PreparedData, bool_cst_x [p], bool_coll_x [p, original numbering], dup_of [p])."""
     import ctypes as C
+    from .plink import PlinkBed
     Y = np.asfortranarray(Y, dtype=np.float64)
     n, q = Y.shape
+    if isinstance(X, PlinkBed):
+        return _prepare_bed_on_device(Y, X, device)
     pin = _lib.AqPrepInput()
     if np.asarray(X).dtype == np.int8:
         Xa = np.asfortranarray(X)
@@ -159,31 +165,64 @@ def prepare_on_device(Y, X, device=0):
     pin.n, pin.p, pin.q, pin.Y, pin.device = n, p, q, _lib.as_dp(Y), int(device)
     h = C.c_void_p()
     rc = _lib.lib().aq_prepare_data(C.byref(pin), C.byref(h))
+    return _prepared_from_handle(rc, h, "aq_prepare_data", n, p, q, device)
+
+
+def _prepared_from_handle(rc, h, what, n, p, q, device, bed=False):
+    """The return value of prepare_on_device from the handle aq_prepare_data / aq_prepare_data_bed made (or their error)."""
+    import ctypes as C
     if rc != 0:
         msg = _lib.lib().aq_last_error().decode("utf-8", "replace")
         if rc == 1:
             raise AtlasqtlError(msg)                       # where the reference calls stop()
-        raise _lib.AtlasqtlHipError(f"aq_prepare_data: [{rc}] {msg}")
+        raise _lib.AtlasqtlHipError(f"{what}: [{rc}] {msg}")
     pk = C.c_int32(0)
     cst = np.zeros(p, dtype=np.uint8); coll = np.zeros(p, dtype=np.uint8); dup = np.zeros(p, dtype=np.int32)
     _lib.check(_lib.lib().aq_prep_info(h, C.byref(pk), cst.ctypes.data_as(C.POINTER(C.c_uint8)),
                                        coll.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.as_ip(dup), None, None), "aq_prep_info")
     Yc = np.empty((n, q), order="F")
     _lib.check(_lib.lib().aq_prep_get(h, None, _lib.as_dp(Yc)), "aq_prep_get")
-    return PreparedData(h, n, int(pk.value), q, Yc, int(device)), cst.astype(bool), coll.astype(bool), dup
+    counts = None
+    if bed:
+        counts = np.zeros((4, p), dtype=np.int32, order="F")
+        _lib.check(_lib.lib().aq_prep_genotype_counts(h, _lib.as_ip(counts)), "aq_prep_genotype_counts")
+    return (PreparedData(h, n, int(pk.value), q, Yc, int(device), genotype_counts=counts), cst.astype(bool),
+            coll.astype(bool), dup)
+
+
+def _prepare_bed_on_device(Y, bed, device):
+    """prepare_on_device for a plink.PlinkBed: the packed blocks go to aq_prepare_data_bed as they are."""
+    import ctypes as C
+    n, q = Y.shape
+    if bed.n != n:
+        raise AtlasqtlError("X and Y must have the same number of samples.")
+    blocks = bed.packed()                                  # p x stride uint8; a view of the memory map where it can be
+    pin = _lib.AqPrepBedInput()
+    pin.n_file, pin.n, pin.p, pin.q = bed.n_file, n, bed.p, q
+    pin.bed = C.cast(blocks.ctypes.data, C.POINTER(C.c_uint8))
+    pin.sample_idx = None if bed.sample_index is None else _lib.as_ip(bed.sample_index)
+    pin.Y, pin.device = _lib.as_dp(Y), int(device)
+    pin.count_a2, pin.missing = int(bed.count == "A2"), int(bed.missing == "mean")
+    h = C.c_void_p()
+    rc = _lib.lib().aq_prepare_data_bed(C.byref(pin), C.byref(h))
+    del blocks
+    return _prepared_from_handle(rc, h, "aq_prepare_data_bed", n, bed.p, q, device, bed=True)
 
 
 def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path,
                   names_x=None, names_y=None, device=0):
     """R/prepare_atlasqtl.R:8-87.  Returns dict(Y, X, bool_rmvd_x, initial_colnames_X,
-    rmvd_cst_x, rmvd_coll_x, names_x, names_y); X is a PreparedData (the standardised matrix lives on the GPU), Y the
-    centred responses on the host.  X may be float64 or int8 dosages."""
+    rmvd_cst_x, rmvd_coll_x, names_x, names_y, genotype_counts); X is a PreparedData (the standardised matrix lives on the
+    GPU), Y the centred responses on the host.  X may be float64, int8 dosages or a plink.PlinkBed, whose variant IDs are
+    the default names_x and whose per-variant genotype counts are returned as genotype_counts (None otherwise)."""
+    from .plink import PlinkBed
+    is_bed = isinstance(X, PlinkBed)
     check_vector_(user_seed, "user_seed", size=1, null_ok=True)
     check_vector_(tol, "tol", size=1)
     check_positive_(tol, "tol", eps=np.finfo(np.float64).eps)
     check_vector_(maxit, "maxit", size=1)
     check_natural_(maxit, "maxit")
-    if not (isinstance(X, np.ndarray) and X.dtype == np.int8 and X.ndim == 2 and X.size > 0):
+    if not is_bed and not (isinstance(X, np.ndarray) and X.dtype == np.int8 and X.ndim == 2 and X.size > 0):
         X = check_matrix_(X, "X")
     if checkpoint_path is not None and not os.path.isdir(checkpoint_path):
         raise AtlasqtlError("The directory specified in checkpoint_path does not exist. Please make sure to "
@@ -203,7 +242,7 @@ def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_p
         raise AtlasqtlError(f"Column(s) {list(np.where(ind_low)[0] + 1)} of matrix Y have more than 97.5% "
                             "missing values, and should be removed. Exit.")
     if names_x is None:
-        names_x = [f"Cov_x_{j + 1}" for j in range(p)]
+        names_x = list(X.snp_names) if is_bed else [f"Cov_x_{j + 1}" for j in range(p)]
     if names_y is None:
         names_y = [f"Resp_{k + 1}" for k in range(q)]
 
@@ -214,5 +253,5 @@ def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_p
     bool_rmvd_x = bool_cst_x | bool_coll_full
     rmvd_coll_x = {names_x[j]: names_x[dup_of[j]] for j in np.where(bool_coll_full)[0]} or None   # removed name -> kept name
     return dict(Y=prep.Y, X=prep, bool_rmvd_x=bool_rmvd_x, initial_colnames_X=names_after_cst,
-                rmvd_cst_x=rmvd_cst_x, rmvd_coll_x=rmvd_coll_x,
+                rmvd_cst_x=rmvd_cst_x, rmvd_coll_x=rmvd_coll_x, genotype_counts=prep.genotype_counts,
                 names_x=[nm for nm, b in zip(names_x, bool_rmvd_x) if not b], names_y=list(names_y))

@@ -398,6 +398,36 @@ int aq_vb_debug_raise_errflag(aq_vb_handle h);
  * host evaluation; writes the shared iteration count to *iters. */
 int aq_q_approx_vec(const double *x, double *out, int64_t len, int32_t *iters);
 
+/* ------------------------------------------------------------------------------------------
+ * aq_prepare_data from the variant blocks of a PLINK 1 .bed file (variant-major), 2 bits per genotype: the packed bytes
+ * are uploaded as they are and unpacked on the device into the column-major dosage buffer that the int8 path of
+ * aq_prepare_data reads, so only n p / 4 bytes cross PCIe.  Sample s of a variant is (block[s >> 2] >> (2 (s & 3))) & 3;
+ * 0 = homozygous A1, 1 = missing, 2 = heterozygous, 3 = homozygous A2; the padding bits of a block's last byte are never
+ * read as genotypes.  With no missing genotype among the n rows used the result is bit-identical to aq_prepare_data on the
+ * same dosages as int8.  missing = 1: a missing genotype takes (n_het + 2 n_hom_counted) / n_obs of its variant, ONE fp64
+ * division of the exact counts, and the result is bit-identical to aq_prepare_data on that fp64 matrix; a variant without an
+ * observed genotype becomes all 0.0 and is reported constant.  missing = 0: a missing genotype is AQ_ERR_ARG (the
+ * reference's message for a matrix X with NA, then how many and where).  Y as in aq_prepare_data.  The argument checks
+ * (NULL, n < 2, p < 1, q < 1, n > n_file, sample_idx NULL with n != n_file, an index out of range, count_a2 / missing not
+ * 0 or 1) come before any device call.  The handle is an aq_prep_handle like any other (aq_prep_info, aq_prep_get, ...).
+ *   aq_prep_genotype_counts   the counts the decode pass took per variant over the n rows used.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_prep_bed_input {
+  int32_t n_file;             /* samples in the file; stride = (n_file + 3) / 4 bytes per variant            */
+  int32_t n, p, q;            /* rows of X and Y, variants given, traits                                      */
+  const uint8_t *bed;         /* p x stride bytes: the variant blocks only, without the 3-byte header (host)  */
+  const int32_t *sample_idx;  /* n entries in [0, n_file): row i of X is file sample sample_idx[i];
+                                 NULL: n == n_file, identity                                                   */
+  const double *Y;            /* n x q column-major, NaN = missing                                            */
+  int32_t count_a2;           /* 0: dosage of A1, 1: dosage of A2                                             */
+  int32_t missing;            /* 0: a missing genotype is an error, 1: the column mean of the observed ones   */
+  int32_t device;
+} aq_prep_bed_input;
+int aq_prepare_data_bed(const aq_prep_bed_input *in, aq_prep_handle *out);
+int aq_prep_genotype_counts(aq_prep_handle h, int32_t *counts);   /* 4 x p column-major: hom A1, het, hom A2, missing,
+                                                                     over the n rows used; AQ_ERR_ARG for a handle that
+                                                                     aq_prepare_data made                              */
+
 #ifdef __cplusplus
 }
 #endif
