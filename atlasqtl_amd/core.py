@@ -571,6 +571,23 @@ def vb_partition(q, n_parts):
     return out
 
 
+PLAN_KEYS = ("core_kernel", "split_parts", "tiles_per_group", "chain_segments", "tiles_matrix", "tiles_matrix2", "tiles_recurrence",
+             "instance_flags", "n_pad")
+
+
+def plan_query(n, p, q, max_missing=0, max_short_list=0, ncu=256, total_bytes=-1, overrides=""):
+    """The launch plan a handle for this problem would get (aq_plan_query: no device, the environment is not read): the plan
+    keys of VbRun.status().  overrides: "NAME=value NAME=value" or a dict of hooks.  total_bytes: the device's memory size;
+    -1 = unknown, which is enough up to n = 10240 with complete Y (with missing values it rules the MASK instances out, and
+    the wide sample split beyond is refused without it)."""
+    if isinstance(overrides, dict):
+        overrides = " ".join(f"{k}={v}" for k, v in overrides.items())
+    st = AqVbStatus()
+    check(lib().aq_plan_query(int(n), int(p), int(q), int(max_missing), int(max_short_list), int(ncu), int(total_bytes),
+                              (overrides or "").encode(), C.byref(st)), "aq_plan_query")
+    return {k: getattr(st, k) for k in PLAN_KEYS}
+
+
 def run_multi(Y, X, list_hyper, list_init, anneal, tol, maxit, n_gpus, devices=None, transport=0, thinned_elbo_eval=True,
               debug=True, scheme="global_local", df=1, full_output=True):
     """aq_vb_run_multi: the whole run on n_gpus GPUs of this node from this one process (host threads + RCCL inside the

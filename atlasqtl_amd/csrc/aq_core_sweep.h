@@ -1,5 +1,7 @@
 // aq_core_sweep.h -- argument block, MFMA wrapper and layout notes shared by the blocked f64-MFMA sweep kernels
-// (aq_core_sweep_la.h: complete Y, n <= 1056; aq_core_sweep_mis.h: Y with missing values and larger n).
+// (aq_core_sweep_la.h: the look-ahead kernel -- complete Y or, in its MASK instances, Y with missing values; n <= 1056 in one
+// workgroup per trait group, up to AQ_N_MAX = 82 944 with the sample split; aq_core_sweep_mis.h: the masked two-barrier kernel,
+// the fallback for Y with missing values when the per-trait Gram blocks do not fit).  aq_plan.h chooses between them.
 //
 // One VB sweep of the spike-and-slab updates (reference src/coreLoop.cpp:38-86, called from
 // R/atlasqtl_global_local_core.R:167) fused with the column/row sums of the p x q passes that follow it in the
@@ -25,6 +27,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "aq_special.h"
+#include "aq_plan_const.h"   // AQ_GK_STRIDE, AQ_LA_CMAX, AQ_N_MAX, AQ_LA_WPC, aq_la_nt3: shared with the host's planner
 
 typedef double aq_d4 __attribute__((ext_vector_type(4)));
 
@@ -79,26 +82,6 @@ struct AqCoreArgs {
   int mprio;             // look-ahead kernel: matrix waves run their hand-offs (everything outside the MFMA stream) at raised priority
   int hprio;             // look-ahead kernel: s_setprio level of the helper wave (its fp64 VALU work shares SIMD 3 with the recurrence wave's MFMAs)
 };
-
-// Look-ahead kernel: 16-sample residual tiles owned by the RECURRENCE wave (on top of the 3 (NT + NT2) of the six matrix
-// waves).  With two trait tiles per workgroup a phase is long enough for that wave to run its chain and then some matrix
-// work on SIMD 3, which otherwise issues no MFMA at all.  Shared by the kernel template and the host's geometry.
-constexpr int AQ_GK_DIAG = 136 * 16, AQ_GK_STRIDE = 136 * 16 + 256 * 16;   // doubles per (tile, SNP block) of AqCoreArgs::GK
-// wide sample split of the look-ahead kernel (n > 10240): at most AQ_LA_CMAX parts per trait group, each holding at most 108
-// residual tiles of 16 samples (NT = NT2 = 18 on six matrix waves, the largest instance), so n <= AQ_N_MAX = 48 x 108 x 16 =
-// 82 944: the geometry is the limit (sample indices are int32 and every offset into R, mis and the X panels is 64-bit).
-// AQ_LA_WPC: most partner words one lane of split_exchange_wide sums, ceil(C / floor(64 / ceil(256 / C))) -- checked below for
-// every C the host can choose.
-constexpr int AQ_LA_CMAX = 48, AQ_N_MAX = AQ_LA_CMAX * 108 * 16, AQ_LA_WPC = 6;
-constexpr bool aq_la_wide_lanes_ok() {
-  for (int C = 9; C <= AQ_LA_CMAX; C++) {
-    const int cmax = (256 + C - 1) / C, nch = 64 / cmax, pc = (C + nch - 1) / nch;
-    if (nch < 1 || nch * cmax > 64 || pc > AQ_LA_WPC) return false;
-  }
-  return true;
-}
-static_assert(aq_la_wide_lanes_ok(), "split_exchange_wide: some C in 9..AQ_LA_CMAX needs more than AQ_LA_WPC partner words per lane");
-constexpr int aq_la_nt3(int NT, int NT2, int TT) { return (TT == 2 && NT >= 8) ? (NT2 == NT ? 3 : 6) : 0; }
 
 __device__ __forceinline__ aq_d4 aq_mfma(double a, double b, aq_d4 c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);

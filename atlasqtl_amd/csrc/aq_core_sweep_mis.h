@@ -29,7 +29,7 @@
 #include "aq_vec_kernels.h"
 #include "aq_core_sweep_la.h"   // aq_static_for, aq_row16_sum
 
-#define AQ_MIS_MMAX 1024  // most missing samples of one trait the LDS index lists hold (16-bit indices, padded to 16)
+// AQ_MIS_MMAX (most missing samples of one trait the LDS index lists hold): aq_plan_const.h, through aq_core_sweep.h
 
 struct AqMisArgs {
   const double2 *XA, *XU;  // MFMA operand layouts of X (aq_core_sweep.h)

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/atlasqtl_hip.h"
+#include "aq_plan.h"
 #include "aq_core_sweep.h"
 #include "aq_launch_la.h"
 #include "aq_gram_loop.h"
@@ -135,8 +136,10 @@ static int aq_upload_padded(double *dst, const double *src, size_t n, size_t n_p
 }
 
 // ------------------------------------------------------------------ state ----
-struct aq_vb {
-  int n, p, q, q_total, p_pad, q_pad, n_pad, nb, ntile, NT, NW, dmode, device, world, trait_offset = 0;
+// The launch plan (aq_plan.h: kernel, geometry, padded sizes; fixed when the handle is created) is the base; everything declared
+// here is the problem, the device buffers and the run state.
+struct aq_vb : AqPlan {
+  int n, p, q, q_total, dmode, device, world, trait_offset = 0;
   // hyper / control
   double A2_inv, m0, nu, rho, t02, t02_inv, shr;
   bool has_anneal;
@@ -154,36 +157,13 @@ struct aq_vb {
   double *zeta = nullptr, *tau = nullptr, *sig2b = nullptr, *log_tau = nullptr, *eta_vb = nullptr, *kappa_vb = nullptr;
   double *coef = nullptr, *inv2s = nullptr, *cst = nullptr, *sums = nullptr, *rowA = nullptr, *rowGB = nullptr;
   double *Aarr = nullptr, *Barr = nullptr, *colApart = nullptr;
-  bool use_la = false;   // look-ahead kernel (aq_core_sweep_la.h)
-  int laC = 1;           // look-ahead kernel: workgroups (sample parts) per trait group, n > 1056
-  int max_missing = 0;   // most missing samples of one trait
-  bool la_mask = false;  // look-ahead kernel, MASK instances: Y with missing values, per-trait Gram blocks precomputed into GK
-  bool la_wide = false;  // look-ahead kernel, wide sample split (9 <= laC <= AQ_LA_CMAX; n > 10240 or AQ_LA_C >= 9)
   double *GK = nullptr;  // [ntile][nb][AQ_GK_STRIDE]
-  int TT = 1;            // look-ahead kernel: 16-trait tiles per workgroup (2 when there are enough tiles to fill the chip)
-  int stagger = 0;       // look-ahead kernel: tile at which a matrix wave releases its SIMD partner into the phase (0 = off)
-  int NT2 = 0;           // look-ahead kernel: tiles of matrix waves 4,5,6 (NT: waves 0,1,2)
-  bool use_tw = false;   // generic wave-per-trait kernel (aq_trait_wave.h): missing Y, or n beyond the MFMA kernels
-  int NE = 0;            // samples per lane of the generic kernel
-  int WPT = 1;           // generic kernel: waves (and workgroups) sharing one trait (tile); also rowGB rows per tile
-  int tw_ns = 4;         // generic kernel: SNP columns staged in LDS at a time
-  bool use_mis = false;  // masked blocked MFMA kernel (aq_core_sweep_mis.h): missing Y, n <= 2048
   double *XR = nullptr;  // [nb][NR][16] row-major SNP panels (gather source of the per-trait Gram corrections)
   int *midx = nullptr, *mcnt4 = nullptr;   // per-trait lists of missing samples
   int *mobs = nullptr;   // wide split: 1 = the trait's list holds its observed samples (the shorter list), aq_k_gk_blocks_g
-  int Mmax = 0, NR = 0;
-  int misC = 1;          // masked kernel: workgroups (sample parts) per trait tile
   double *Pbuf = nullptr, *rnpart = nullptr;
   int *pflag = nullptr;
   double *Xcm = nullptr, *mis = nullptr, *XN = nullptr;
-  int ncu = 256;
-  int la_xtouch = 1;        // helper waves warm the L2 with the next phase's X operand panels (AQ_XTOUCH=0 switches it off)
-  bool la_nt3_pinned = false;   // AQ_NT3 given: the annealed sweeps keep the geometry as well
-  int NT3x = -1;                // look-ahead kernel, two-tile instances: 9 residual tiles on the recurrence wave (geometry NT / NT / 9), -1 = aq_la_nt3
-  int la_mprio = 1;         // matrix waves: hand-offs at raised priority (AQ_MPRIO=0 switches it off): C3 34.84 -> 34.67 ms, C3 + 5 % NA 49.9 -> 47.1
-  int la_hprio = 0;         // s_setprio level of the helper wave (AQ_HPRIO; 1 for the unsplit MASK instances, see below)
-  int la_xhelper = 0;       // sample split of the look-ahead kernel: exchange on the helper wave (long matrix phases) or on the recurrence wave
-  int chain = 0;            // > 1: chained-segment launch with that many SNP segments (aq_core_sweep_la.h, SEG)
   int *done = nullptr, *errflag = nullptr;
   bool pre_done = false;
   bool fused = false;    // look-ahead kernel: the pre-pass (A, b, sums of a) is computed inside the sweep kernel
@@ -214,19 +194,18 @@ struct aq_vb {
   std::string fail_msg;
   bool errflag_forced = false;   // test hook aq_vb_debug_raise_errflag
   int budget = -1;
-  std::string overrides;   // "NAME=value ..." of the AQ_* environment hooks that were set when the handle was created
+  std::string overrides;   // "NAME=value ..." of the AQ_* hooks the plan consulted and found set when the handle was created
 };
 
-// Environment overrides of the launch plan (test and experiment hooks: AQ_TT, AQ_CHAIN, AQ_LA_C, ...).  Every one that is SET when a
-// handle is created is recorded in the handle and reported by aq_vb_get_overrides, so that a host which inherits such a variable
-// from its environment -- an R session, a batch script -- can see that the plan is not the library's own.
-static const char *aq_env(aq_vb *s, const char *name) {
-  const char *v = getenv(name);
-  if (v && s) {
-    const std::string item = std::string(name) + "=" + v;
-    if (s->overrides.find(item) == std::string::npos) s->overrides += (s->overrides.empty() ? "" : " ") + item;
-  }
-  return v;
+// Environment overrides of the launch plan (test and experiment hooks: AQ_TT, AQ_CHAIN, AQ_LA_C, ...).  Every one the planner
+// finds SET when a handle is created is recorded in the handle and reported by aq_vb_get_overrides, so that a host which
+// inherits such a variable from its environment -- an R session, a batch script -- can see that the plan is not the library's own.
+static AqEnv aq_env_recorder(std::string *found) {
+  return [found](const char *name) {
+    const char *v = getenv(name);
+    if (v) *found += (found->empty() ? "" : " ") + std::string(name) + "=" + v;
+    return v;
+  };
 }
 
 static void aq_free_all(aq_vb *s) {
@@ -473,308 +452,46 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
     for (size_t i = 0; i < np; i++)
       if (!(pr->X[i] == pr->X[i])) return aq_fail(AQ_ERR_ARG, "X must be a non-empty a numeric matrix, finite without missing value.");
   }
-  bool has_missing = false;
-  for (size_t i = 0; i < nq && !has_missing; i++) has_missing = !(Yh[i] == Yh[i]);
-  if (pr->n > AQ_N_MAX)
-    return aq_fail(AQ_ERR_UNSUPPORTED, "n = " + std::to_string(pr->n) + " exceeds the largest supported sample count, n <= " +
-                                           std::to_string(AQ_N_MAX) + " (AQ_N_MAX, the wide sample split)");
+  // the one pass over Y for missing values: per trait the count, from which the planner's inputs, nobs and the index lists derive
+  std::vector<int> nmiss(pr->q, 0);
+  AqPlanInput in;
+  in.n = pr->n; in.p = pr->p; in.q = pr->q;
+  for (int k = 0; k < pr->q; k++) {
+    const double *yk = Yh + (size_t)pr->n * k;
+    int m = 0;
+    for (int i = 0; i < pr->n; i++) m += !(yk[i] == yk[i]);
+    nmiss[k] = m;
+    in.max_missing = std::max(in.max_missing, m);
+    in.max_short_list = std::max(in.max_short_list, std::min(m, pr->n - m));
+  }
+  in.has_missing = in.max_missing > 0;
+  {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, pr->device) == hipSuccess && prop.multiProcessorCount > 0) in.ncu = prop.multiProcessorCount;
+    size_t free_b = 0, tot_b = 0;
+    const hipError_t mrc = hipMemGetInfo(&free_b, &tot_b);
+    if (mrc == hipSuccess) in.total_bytes = (long long)tot_b;
+    else in.mem_error = hipGetErrorString(mrc);
+  }
+  std::string overrides;
+  AqPlan plan;
+  {
+    std::string err;
+    const int rc = aq_make_plan(in, aq_env_recorder(&overrides), &plan, &err);
+    if (rc != AQ_OK) return aq_fail(rc, err);
+  }
+  int dmode = 0;
+  AQ_TRY(aq_probe_dmode(&dmode));
+  if ((plan.use_la || plan.use_mis) && dmode != 0)   // the MFMA sweep kernels are written for gfx950's accumulator map (row = 4 reg + lane / 16)
+    return aq_fail(AQ_ERR_UNSUPPORTED, "this device reports an f64 MFMA accumulator layout the sweep kernels are not written for");
 
   aq_vb *s = new aq_vb();
+  static_cast<AqPlan &>(*s) = plan;
+  s->overrides = overrides;
+  s->dmode = dmode;
   s->device = pr->device;
   s->n = pr->n; s->p = pr->p; s->q = pr->q; s->q_total = pr->q_total; s->world = pr->world_size;
   s->trait_offset = pr->trait_offset;
-  s->p_pad = (pr->p + 15) / 16 * 16;
-  s->q_pad = (pr->q + 15) / 16 * 16;
-  s->nb = s->p_pad / 16;
-  s->ntile = s->q_pad / 16;
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, pr->device) == hipSuccess && prop.multiProcessorCount > 0) s->ncu = prop.multiProcessorCount;
-    if (const char *e = aq_env(s, "AQ_NCU")) s->ncu = atoi(e) > 0 ? atoi(e) : s->ncu;
-  }
-  {
-    // default: look-ahead kernel (complete Y, n <= 1056); AQ_KERNEL=2 forces the generic wave-per-trait kernel
-    const char *ek = aq_env(s, "AQ_KERNEL");
-    // missing values: masked blocked MFMA kernel while n fits 8 waves x 16 residual tiles and no trait misses more
-    // than AQ_MIS_MMAX samples; otherwise (and with AQ_KERNEL=2) the generic kernel
-    int max_missing = 0;
-    if (has_missing) {
-      for (int k = 0; k < pr->q; k++) {
-        int m = 0;
-        for (int i = 0; i < pr->n; i++) m += !(Yh[(size_t)i + (size_t)pr->n * k] == Yh[(size_t)i + (size_t)pr->n * k]);
-        if (m > max_missing) max_missing = m;
-        s->max_missing = max_missing;
-      }
-    }
-    // the masked MFMA kernel also serves complete Y beyond the look-ahead kernel's n (all-ones mask, empty lists)
-    // Y with missing values: the look-ahead kernel's MASK instances when the per-trait Gram blocks (50 KB per trait tile and
-    // SNP block, computed once) fit next to the rest of the state in HBM; else the masked two-barrier kernel (AQ_KERNEL=3
-    // forces that one), which recomputes them every sweep.  Complete Y beyond n = 1056: look-ahead kernel with a sample split.
-    const bool n_la_ok = pr->n <= 8 * 16 * 105;
-    // n > 10240 (or AQ_LA_C = 9 ... AQ_LA_CMAX, test hook): the look-ahead kernel's wide sample split, complete Y or MASK with the
-    // Gram blocks of aq_k_gk_blocks_g (any missingness); no other kernel serves this n
-    const char *ecw = aq_env(s, "AQ_LA_C");
-    const bool wide = pr->n > 10240 || (ecw && atoi(ecw) >= 9);
-    if (wide && ecw && (atoi(ecw) > AQ_LA_CMAX || (pr->n > 10240 && atoi(ecw) < 9))) {
-      delete s;
-      return aq_fail(AQ_ERR_ARG, "AQ_LA_C: the wide sample split takes 9 ... " + std::to_string(AQ_LA_CMAX) + " parts");
-    }
-    if (wide && ek && atoi(ek) >= 2) { delete s; return aq_fail(AQ_ERR_UNSUPPORTED, "AQ_KERNEL: only the look-ahead kernel serves n > 10240"); }
-    bool la_mask_ok = has_missing && n_la_ok && max_missing <= AQ_MIS_MMAX && !(ek && atoi(ek) >= 2);
-    if (wide) la_mask_ok = has_missing;
-    if (la_mask_ok) {
-      size_t free_b = 0, tot_b = 0;
-      const size_t ntile_ = (size_t)(pr->q + 15) / 16, nb_ = (size_t)(pr->p + 15) / 16;
-      const size_t gk_b = ntile_ * nb_ * AQ_GK_STRIDE * sizeof(double);
-      const size_t rest_b = 2 * ntile_ * nb_ * 256 * sizeof(double) + 3 * (size_t)(pr->n + 64) * nb_ * 16 * sizeof(double) * 2 +
-                            3 * ntile_ * (size_t)(pr->n + 64) * 16 * sizeof(double);
-      // decided on the device's TOTAL memory (minus a tenth), not on what happens to be free: the same problem gets the same
-      // kernel on every rank and in every run, so a checkpoint of one is accepted by the other.  Should the allocation then fail
-      // because other processes hold memory, aq_vb_create reports the out-of-memory error (AQ_GK_MAX_GB lowers the limit).
-      const hipError_t mrc = hipMemGetInfo(&free_b, &tot_b);
-      if (wide && mrc != hipSuccess) {
-        delete s;
-        return aq_fail(AQ_ERR_DEVICE, std::string("hipMemGetInfo: ") + hipGetErrorString(mrc));
-      }
-      // (the wide split sizes its whole budget, with its own n_pad, before allocating: see "device memory of the wide split" below)
-      if (mrc != hipSuccess || (!wide && (double)(gk_b + rest_b) * 1.05 > 0.9 * (double)tot_b)) la_mask_ok = false;
-      if (const char *e = aq_env(s, "AQ_GK_MAX_GB")) if ((double)gk_b > atof(e) * 1e9) la_mask_ok = false;   // test hook: force the fallback
-      if (wide && !la_mask_ok) {   // AQ_GK_MAX_GB: no fallback kernel at this n
-        char msg[256];
-        snprintf(msg, sizeof msg, "Y with missing values at n = %d: the per-trait Gram blocks need %.1f GB of device memory, which does not "
-                 "fit; shard the traits (fewer traits per device)", pr->n, (double)gk_b / 1e9);
-        delete s;
-        return aq_fail(AQ_ERR_UNSUPPORTED, msg);
-      }
-    }
-    const bool la_split_ok = (!has_missing && pr->n > 1056 && n_la_ok && !(ek && atoi(ek) >= 2)) || (wide && !has_missing);   // complete Y, large n
-    if (!wide && !la_mask_ok && (has_missing || (pr->n > 1056 && !la_split_ok)) && pr->n <= 16384 && max_missing <= AQ_MIS_MMAX && !(ek && atoi(ek) == 2)) {
-      s->use_mis = true;
-      s->NW = 8;
-      // n_pad = 128 NT C: C workgroups per trait tile, NT in {1,2,4,8,16} residual tiles per wave.  Model of a sweep:
-      // whole rounds of workgroups (one per CU) x time per SNP block (4.5 + 0.94 NT us, + 6 us for the exchange)
-      {
-        const int ntile_ = (pr->q + 15) / 16;
-        double best = 1e300;
-        for (int C = 1; C <= 8; C++)
-          for (int NT = 1; NT <= 16; NT *= 2) {
-            if (128 * NT * C < pr->n) continue;
-            double rounds = (double)(((long long)ntile_ * C + s->ncu - 1) / s->ncu);
-            double cost = rounds * (4.5 + 0.94 * NT + (C > 1 ? 6.0 : 0.0));
-            if (cost < best - 1e-9) { best = cost; s->misC = C; s->NT = NT; }
-          }
-      }
-      if (const char *e = aq_env(s, "AQ_MIS_C")) {   // test hook: force the sample split at small n
-        int C = atoi(e);
-        if (C >= 1 && C <= 8) {
-          s->misC = C;
-          s->NT = 16;
-          for (int NT = 16; NT >= 1; NT /= 2) if (128 * NT * C >= pr->n) s->NT = NT;
-        }
-      }
-      s->Mmax = (max_missing + 15) / 16 * 16;
-      if (s->Mmax < 16) s->Mmax = 16;
-    } else if (!wide && ((has_missing && !la_mask_ok) || (ek && atoi(ek) == 2) || (pr->n > 1056 && !la_split_ok && !la_mask_ok))) {
-      // generic kernel geometry: n_pad = 64 * NE * WPT samples, WPT waves (and workgroups) per trait (tile)
-      s->use_tw = true;
-      s->WPT = pr->n <= 2048 ? 1 : pr->n <= 5120 ? 2 : 4;
-      if (const char *e = aq_env(s, "AQ_TW_WPT")) { int v = atoi(e); if ((v == 2 || v == 4) && v > s->WPT) s->WPT = v; }   // test hook
-      const int per_lane = (pr->n + 64 * s->WPT - 1) / (64 * s->WPT);
-      s->NE = per_lane <= 4 ? 4 : per_lane <= 8 ? 8 : per_lane <= 16 ? 16 : per_lane <= 32 ? 32 : 40;
-    }
-    if (!s->use_tw && !s->use_mis) {
-      // 6 matrix waves (NT tiles on waves 0-2, NT2 = NT or NT - 1 on waves 4-6: NT + NT2 per SIMD) + the recurrence wave,
-      // which owns aq_la_nt3(NT, TT) tiles of its own when two trait tiles share a workgroup
-      s->use_la = true;
-      s->la_mask = la_mask_ok;
-      const int ntiles = (pr->n + 15) / 16;
-      s->NW = 6;
-      // two trait tiles per workgroup once that still gives every CU a workgroup (C3: 625 tiles -> 313 workgroups of 32
-      // traits): X operands shared by two MFMAs, one chain evaluation per 32 traits, half the per-phase overhead.
-      // q is then padded to a multiple of 32 (the extra tile is all padding: zero residual, masked sums).
-      // (Crossover measured at n = 1000, 256 CUs: 448 tiles -- one round of two-tile workgroups, 27.4 ms, against 1.75 rounds of
-      // one-tile workgroups; q = 8000: 27.5 vs 31.1 ms, q = 6144: 27.5 vs 23.4.)
-      s->TT = (4LL * s->ntile >= 7LL * s->ncu) ? 2 : 1;
-      if (const char *e = aq_env(s, "AQ_TT")) s->TT = atoi(e) == 2 ? 2 : 1;
-      if (s->la_mask) s->TT = 1;   // 16 per-trait Gram blocks per trait tile in LDS: one tile per workgroup
-      if (s->TT == 2) {
-        s->q_pad = (pr->q + 31) / 32 * 32;
-        s->ntile = s->q_pad / 16;
-        // (waves 4-6 then enter a phase when their SIMD partner is a third of the way through it -- stagger, set below -- so
-        // that one wave's hand-off gap is covered by the other's MFMAs)
-      }
-      {
-        // smallest geometry that holds ntiles: NT in 1..11, NT2 in {NT, NT - 1}, plus the recurrence wave's aq_la_nt3 tiles;
-        // among equals the one with more tiles on the recurrence wave (AQ_NT3=0/3/6 pins its tile count for experiments)
-        const char *e3 = aq_env(s, "AQ_NT3");
-        auto fit = [&](int tiles_needed, int nt_max, int *NTo, int *NT2o, int *N3xo) {
-          int best_tiles = 1 << 30, best_nt3 = -1;
-          for (int NT = 1; NT <= nt_max; NT++)
-            for (int NT2 = NT; NT2 >= (NT > 1 ? NT - 1 : NT); NT2--) {
-              // x9: the instance NT / NT / 9 -- nine residual tiles on the recurrence wave, 18 instead of 19 per matrix SIMD at
-              // n = 1000.  While the recurrence wave's MFMAs hold SIMD 3's datapath the helper wave's fp64 work crawls (38.4 ms at C3
-              // against 34.3 for 10 / 9 / 6), so it comes with the helper wave one priority level up (set below): 33.9 ms
-              // (profiles/r03_nt9_stagger.txt).  AQ_NT3 pins another count; the diagnostic build, whose NT / NT / 9 instances do not
-              // pass the ISA proof, takes it only on request.
-#ifdef AQ_DIAG_TIME
-              const bool x9_ok = s->TT == 2 && NT >= 8 && NT2 == NT && e3 && atoi(e3) == 9;
-#else
-              // (by default from NT = 9 on: 8 / 8 / 9 -- n around 900 -- loses to 9 / 8 / 6, 8.68 against 8.42 us per phase; measured per
-              // geometry in profiles/r03_nt9_stagger.txt: a phase takes max(matrix SIMDs, SIMD 3) with SIMD 3 at 7.6 - 7.7 us for three or
-              // six tiles and 8.7 for nine, the matrix SIMDs at 7.6 / 7.7 / 8.4 / 8.4 / 8.9 / 9.3 / 9.7 / 10.3 us for (8,7) ... (11,11))
-              const bool x9_ok = s->TT == 2 && NT2 == NT && (e3 ? (NT >= 8 && atoi(e3) == 9) : NT >= 9);
-#endif
-              for (int x9 = 0; x9 <= (x9_ok ? 1 : 0); x9++) {
-                int nt3 = x9 ? 9 : aq_la_nt3(NT, NT2, s->TT);
-                // one tile per workgroup, unsplit (the trait shards of N = 2, 4: MFMA-bound on three SIMDs while SIMD 3 only runs
-                // the chain): three residual tiles on the recurrence wave by default -- q = 5000: 19.55 -> 18.78 ms, q = 2500:
-                // 15.48 -> 14.83; six or nine make its chain + tiles the bound (30 and 33 ms).  AQ_NT3 = 0 / 3 / 6 / 9 pins the count.
-                int x1 = -1;
-                bool second = false;
-                if (s->TT == 1 && !s->la_mask && NT >= 8 && nt_max <= 11) {
-                  const int w = e3 ? atoi(e3) : 3;
-                  if ((w == 3 || w == 9) && NT2 == NT) x1 = w;
-                  else if (w == 6 && NT2 == NT - 1) x1 = w;
-                  else if (e3 && w != 0) continue;
-                  if (x1 > 0) nt3 = x1;
-                  second = !e3 && x1 > 0;        // by default the plain geometry competes as well (it wins when it needs fewer tiles)
-                }
-                if (second) {
-                  const int tiles0 = 3 * (NT + NT2);
-                  if (tiles0 >= tiles_needed && tiles0 < best_tiles) { best_tiles = tiles0; best_nt3 = 0; *NTo = NT; *NT2o = NT2; *N3xo = -1; }
-                }
-                const int tiles = 3 * (NT + NT2) + nt3;
-                if (tiles < tiles_needed || (e3 && atoi(e3) != nt3 && s->TT == 2 && NT >= 8)) continue;
-                if (tiles < best_tiles || (tiles == best_tiles && nt3 > best_nt3)) { best_tiles = tiles; best_nt3 = nt3; *NTo = NT; *NT2o = NT2; *N3xo = x9 ? 9 : x1; }
-              }
-            }
-          return best_tiles;
-        };
-        if (pr->n <= 1056 && !aq_env(s, "AQ_LA_C")) {
-          s->laC = 1;
-          const int tiles = fit(ntiles, 11, &s->NT, &s->NT2, &s->NT3x);    // n <= 1056 always fits (11, 11) ...
-          if (tiles >= (1 << 30)) { delete s; return aq_fail(AQ_ERR_ARG, "AQ_NT3 excludes every look-ahead geometry for this n"); }   // ... unless the test hook forbids it
-          s->n_pad = 16 * tiles;
-          // Few trait groups (a trait shard of a multi-GPU run, a small q): the CUs left idle share the samples.  Per SNP block an
-          // unsplit workgroup needs its MFMA stream (0.213 us per residual tile of one SIMD + 1.0 of hand-offs; n = 1000: 5.46 us
-          // measured) or, for small n, the chain (3.3 us); a part of a split group needs its shorter stream or chain + exchange
-          // (4.5 us with two parts, measured at n = 1000: 4.53; + 0.2 per further part).  All parts must run at once.
-          // (Not with missing values: there the chain is longer and the helper wave loaded -- q = 1250 with 5 % NA: 19.3 ms unsplit,
-          // 20.1 split.  AQ_LA_NOSPLIT=1 keeps one workgroup per group: experiments.)
-          if (s->TT == 1 && !s->la_mask && !aq_env(s, "AQ_LA_NOSPLIT")) {
-            double best = std::max(0.213 * (s->NT + s->NT2) + 1.0, 3.3) * 0.95;   // a split must win by 5 %
-            for (int C = 2; C <= 8 && (long long)s->ntile * C <= s->ncu; C++) {
-              int NT = 0, NT2 = 0, N3x = -1;
-              const int tiles_c = fit((ntiles + C - 1) / C, 18, &NT, &NT2, &N3x);
-              if (tiles_c >= (1 << 30)) continue;
-              const double cost = std::max(0.213 * (NT + NT2) + 1.0, 4.5 + 0.2 * (C - 2));
-              if (cost < best - 1e-9) { best = cost; s->laC = C; s->NT = NT; s->NT2 = NT2; s->NT3x = N3x; s->n_pad = 16 * tiles_c * C; }
-            }
-          }
-        } else {
-          // n beyond one workgroup's registers: C workgroups share a trait group (sample split, one tile per workgroup).  Cost of
-          // a sweep ~ rounds of workgroups x time per SNP block: the MFMA stream of one SIMD (0.213 us per residual tile) or the
-          // exchange + chain (4.5 us with two parts, + 0.2 per further part), whichever is longer.  (AQ_LA_C forces the split at small n: test hook.)
-          s->TT = 1; s->q_pad = (pr->q + 15) / 16 * 16; s->ntile = s->q_pad / 16; s->stagger = 0;
-          double best = 1e300;
-          const char *ec = aq_env(s, "AQ_LA_C");
-          for (int C = 2; C <= 8 && !wide; C++) {
-            if (ec && atoi(ec) != C) continue;
-            int NT = 0, NT2 = 0, N3x = -1;
-            const int tiles = fit((ntiles + C - 1) / C, 18, &NT, &NT2, &N3x);
-            if (tiles >= (1 << 30)) continue;
-            const double rounds = (double)(((long long)s->ntile * C + s->ncu - 1) / s->ncu);
-            const double cost = rounds * std::max(0.213 * (NT + NT2) + 1.0, 4.5 + 0.2 * (C - 2));
-            if (cost < best - 1e-9) { best = cost; s->laC = C; s->NT = NT; s->NT2 = NT2; s->NT3x = N3x; s->n_pad = 16 * tiles * C; }
-          }
-          if (wide) {
-            // the wide split (aq_launch_la1w.hip): C = 9 ... AQ_LA_CMAX parts of 6 NT residual tiles (NT2 = NT, none on the recurrence
-            // wave), the exchange a block ahead on the helper wave.  Same model: rounds of workgroups x time per SNP block, here
-            // max(MFMA stream of one SIMD, helper wave), because the exchange runs on the helper wave next to its own per-block work
-            // (staging, column sums) and adds to it.  Measured (timelines of workgroup 0, profiles/large_n_timeline.txt, n = 20 480):
-            // helper period 8.5 us at C = 12, 10.9 us at C = 29 (exchange 3.7 -> 6.3 us, the rest 4.6 - 4.9 us) -> 8.5 + 0.14 (C - 12).
-            // (Not modelled: at n = 50 000 the operand stream of the matrix waves and the exchange are both slower)
-            auto helper_us = [](int C) { return 8.5 + 0.14 * (C - 12); };
-            s->la_wide = true;
-            const int cf = ec ? atoi(ec) : 0;
-            for (int C = 9; C <= AQ_LA_CMAX && C <= s->ncu; C++) {
-              if (cf >= 9 && C != cf) continue;
-              const int NT = ((ntiles + C - 1) / C + 5) / 6;
-              if (NT > 18) continue;
-              const double rounds = (double)(((long long)s->ntile * C + s->ncu - 1) / s->ncu);
-              const double cost = rounds * std::max(0.213 * 2 * NT + 1.0, helper_us(C));
-              if (cost < best - 1e-9) { best = cost; s->laC = C; s->NT = NT; s->NT2 = NT; s->NT3x = -1; s->n_pad = 16 * 6 * NT * C; }
-            }
-            s->la_xhelper = 1;
-          }
-          if (best >= 1e300) { delete s; return aq_fail(AQ_ERR_UNSUPPORTED, "no look-ahead geometry for this n"); }
-          // Who exchanges the partial S': the recurrence wave at the start of its chain.  The helper wave can do it a block ahead
-          // (AQ_LA_XHELPER=1); that paid at n = 5000 while an exchange was three trips through the shared cache (236 vs 225 ms),
-          // with self-validating words it no longer does (222.5 vs 222.0; n = 1500: 58.3 vs 64.5).
-          if (!wide) s->la_xhelper = 0;
-        }
-        if (const char *e = aq_env(s, "AQ_LA_XHELPER")) s->la_xhelper = atoi(e) != 0;   // test hook
-        if (const char *e = aq_env(s, "AQ_XTOUCH")) s->la_xtouch = atoi(e) != 0;
-        // helper wave one priority level above the recurrence wave it shares SIMD 3 with -- only where its iteration is on the
-        // critical cycle: the unsplit MASK instances (single cross-block buffer; C3 + 5 % NA 49.9 -> 48.6 ms on one box, 48.4 -> 47.4
-        // on another; the split C5 shard 241.1 -> 242.0, complete Y the same within noise: profiles/r03_hprio_na.txt)
-        if (s->la_mask && s->laC <= 1) s->la_hprio = 1;
-        // six or nine tiles on the recurrence wave of a two-tile workgroup: see fit() (n = 800, geometry 8 / 7 / 6: 33.5 -> 29.6 ms)
-        if (s->TT == 2 && s->NT >= 8 && (s->NT3x == 9 || (s->NT3x < 0 && s->NT2 == s->NT - 1))) s->la_hprio = 1;
-        if (const char *e = aq_env(s, "AQ_MPRIO")) s->la_mprio = atoi(e) != 0;
-        if (const char *e = aq_env(s, "AQ_HPRIO")) s->la_hprio = atoi(e) >= 0 && atoi(e) <= 3 ? atoi(e) : 0;
-        s->la_nt3_pinned = aq_env(s, "AQ_NT3") != nullptr;
-        if (s->TT == 2) s->stagger = (s->NT + 2) / 3;
-      }
-      if (const char *e = aq_env(s, "AQ_STAGGER")) s->stagger = atoi(e) >= 0 ? atoi(e) : 0;
-      // more workgroups than CUs: chained SNP segments even out the last round (3 rounds -> ~2.5 for 625 workgroups)
-      const int nwg = s->ntile / s->TT;
-      if (nwg > s->ncu && s->laC == 1) {
-        // cost of a sweep in phases: rounds of workgroups x (SNP blocks of a segment + 2 phases of pipeline fill + ~1.7 of start-up:
-        // fitted to C3 at S = 4, 8, 13, 16, 26, profiles/r03_chain_segments.txt).  C3: 313 groups -> S = 13 (16 rounds of 241 blocks:
-        // 34.43 ms against 34.61 with S = 4); C3 with NA: 625 groups -> S = 9.
-        double best = 1e30;
-        for (int S = 2; S <= 32 && S <= s->nb; S++) {
-          const long long wg = (long long)nwg * S;
-          const double cost = (double)((wg + s->ncu - 1) / s->ncu) * ((s->nb + S - 1) / S + 3.7);
-          if (cost < best - 1e-9) { best = cost; s->chain = S; }
-        }
-        if (best >= (double)((nwg + s->ncu - 1) / s->ncu) * (s->nb + 3.7)) s->chain = 0;   // no gain over whole tiles
-      }
-      if (const char *e = aq_env(s, "AQ_CHAIN")) s->chain = atoi(e) > 1 ? atoi(e) : 0;
-      if (s->chain > s->nb) s->chain = s->nb;
-      if (s->chain > 32) s->chain = 32;
-      if (s->laC > 1) s->chain = 0;   // the parts of a group must be co-resident: no chained segments
-    }
-  }
-  if (s->use_mis && s->misC == 1) {   // same chained-segment choice as for the look-ahead kernel
-    if (s->ntile > s->ncu) {
-      double best = 1e30;
-      for (int S = 2; S <= 16; S++) {
-        long long wg = (long long)s->ntile * S;
-        double cost = (double)((wg + s->ncu - 1) / s->ncu) / S * (1.0 + 0.002 * S);
-        if (cost < best - 1e-12) { best = cost; s->chain = S; }
-      }
-      if (best >= (double)((s->ntile + s->ncu - 1) / s->ncu)) s->chain = 0;
-    }
-    if (const char *e = aq_env(s, "AQ_CHAIN")) s->chain = atoi(e) > 1 ? atoi(e) : 0;
-    if (s->chain > s->nb) s->chain = s->nb;
-    if (s->chain > 32) s->chain = 32;
-  }
-  if (s->use_mis) { s->n_pad = 128 * s->NT * s->misC; s->NR = s->n_pad + 8; }
-  if (s->use_tw) {
-    s->n_pad = 64 * s->NE * s->WPT;
-    // SNP columns staged in LDS at a time: ns * n_pad doubles next to 18 KB of block scalars, within 160 KB
-    s->tw_ns = 4;
-    while (s->tw_ns > 1 && (size_t)(s->tw_ns * s->n_pad + 8 * 256 + 32) * sizeof(double) > 150 * 1024) s->tw_ns /= 2;
-  }
-  int rc = aq_probe_dmode(&s->dmode);
-  if (rc != AQ_OK) { delete s; return rc; }
-  if ((s->use_la || s->use_mis) && s->dmode != 0) {   // the MFMA sweep kernels are written for gfx950's accumulator map (row = 4 reg + lane / 16)
-    delete s;
-    return aq_fail(AQ_ERR_UNSUPPORTED, "this device reports an f64 MFMA accumulator layout the sweep kernels are not written for");
-  }
-
   s->A2_inv = pr->A2_inv; s->m0 = pr->m0; s->nu = pr->nu; s->rho = pr->rho; s->t02 = pr->t02;
   s->t02_inv = 1.0 / pr->t02;
   s->shr = (double)pr->q_total;   // shr_fac_inv <- q, R/atlasqtl.R:218
@@ -782,41 +499,12 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
   s->scheme = pr->scheme; s->df = pr->scheme == 1 ? 1 : (pr->df == 0 ? 1 : pr->df);
   std::memcpy(s->anneal, pr->anneal, sizeof(s->anneal));
   s->tol = pr->tol; s->maxit = pr->maxit; s->thinned = pr->thinned_elbo_eval != 0; s->debug = pr->debug != 0;
-  s->has_missing = has_missing || s->use_mis || s->la_mask;   // the masked kernel produces the NA forms of the column sums (identical for complete Y)
+  s->has_missing = in.has_missing || s->use_mis || s->la_mask;   // the masked kernel produces the NA forms of the column sums (identical for complete Y)
 
   auto fail = [&](int code) { aq_free_all(s); return code; };
 #define AQ_TRYF(x) do { int rc2_ = (x); if (rc2_ != AQ_OK) return fail(rc2_); } while (0)
 #define AQ_HIPF(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { aq_fail(AQ_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); return fail(AQ_ERR_DEVICE); } } while (0)
 
-  if (s->la_wide) {
-    if (s->la_mask) {   // aq_k_gk_blocks_g: per trait the shorter of the missing and the observed list
-      int mm = 0;
-      for (int k = 0; k < s->q; k++) {
-        int m = 0;
-        for (int i = 0; i < s->n; i++) m += !(Yh[(size_t)i + (size_t)s->n * k] == Yh[(size_t)i + (size_t)s->n * k]);
-        mm = std::max(mm, std::min(m, s->n - m));
-      }
-      s->Mmax = (mm + 15) / 16 * 16;
-    }
-    if (s->Mmax < 16) s->Mmax = 16;
-    // device memory of the wide split: the X operand panels (XA, XU: n_pad p 8 B each), residual and mask tiles, and with missing
-    // values the Gram blocks plus, while they are built, the row panels XR and the index lists.  No other kernel serves this n:
-    // fail here, before anything is allocated, when it cannot fit.
-    size_t free_b = 0, tot_b = 0;
-    const double xb = 2.0 * (double)s->nb * (s->n_pad / 16) * 128 * sizeof(double);
-    const double rb = (s->la_mask ? 2.0 : 1.0) * (double)s->ntile * s->n_pad * 16 * sizeof(double);
-    const double gb = s->la_mask ? (double)s->ntile * s->nb * AQ_GK_STRIDE * sizeof(double) + (double)s->nb * (s->n_pad + 8) * 16 * sizeof(double) +
-                                       (double)s->ntile * 16 * s->Mmax * sizeof(int)
-                                 : 0.0;
-    if (hipMemGetInfo(&free_b, &tot_b) != hipSuccess) { delete s; return aq_fail(AQ_ERR_DEVICE, "hipMemGetInfo failed"); }
-    if ((xb + rb + gb) * 1.05 > 0.9 * (double)tot_b) {
-      char msg[256];
-      snprintf(msg, sizeof msg, "n = %d, p = %d, q = %d: the wide sample split needs %.1f GB of device memory, more than the device holds; "
-               "shard the traits (fewer traits per device)", s->n, s->p, s->q, (xb + rb + gb) * 1.05 / 1e9);
-      delete s;
-      return aq_fail(AQ_ERR_UNSUPPORTED, msg);
-    }
-  }
   const int NTT = s->n_pad / 16;
   size_t xelems = s->use_tw ? 1 : (size_t)s->nb * NTT * 128;
   AQ_TRYF(aq_dalloc(&s->XA, xelems));
@@ -826,11 +514,6 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
   if (s->use_tw) {
     AQ_TRYF(aq_dalloc(&s->mis, (size_t)s->ntile * s->n_pad * 16));
     AQ_TRYF(aq_dalloc(&s->XN, (size_t)s->ntile * s->p_pad * 16));
-  }
-  if (s->la_mask) {
-    if (!s->la_wide) s->Mmax = (s->max_missing + 15) / 16 * 16;
-    if (s->Mmax < 16) s->Mmax = 16;
-    s->NR = s->n_pad + 8;
   }
   if (s->use_mis || s->la_mask) {
     AQ_TRYF(aq_dalloc(&s->mis, (size_t)s->ntile * s->n_pad * 16));
@@ -848,16 +531,10 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
       int m = 0;
       int *dst = idx.data() + (size_t)k * s->Mmax;      // trait k = tile (k / 16), slot (k % 16): contiguous
       const double *yk = Yh + (size_t)s->n * k;
-      int mk = 0;
-      if (s->la_wide) for (int i = 0; i < s->n; i++) mk += !(yk[i] == yk[i]);
-      if (s->la_wide && 2 * mk > s->n) {   // wide split: more missing than observed -- list the observed samples
-        obs[k] = 1;
-        for (int i = 0; i < s->n; i++)
-          if (yk[i] == yk[i]) dst[m++] = i;
-      } else {
-        for (int i = 0; i < s->n; i++)
-          if (!(yk[i] == yk[i])) dst[m++] = i;
-      }
+      const bool list_obs = s->la_wide && 2 * nmiss[k] > s->n;   // wide split: more missing than observed -- list the observed samples
+      obs[k] = list_obs ? 1 : 0;
+      for (int i = 0; i < s->n; i++)
+        if ((yk[i] == yk[i]) == list_obs) dst[m++] = i;
       cnt[k] = (m + 15) / 16 * 4;
     }
     if (s->la_wide) {
@@ -997,11 +674,7 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
   AQ_TRYF(aq_upload_padded(s->sig2b, pr->sig2_beta_vb, s->q, s->q_pad));
   {
     std::vector<double> nobs(s->q_pad, 0.0);
-    for (int k = 0; k < s->q; k++) {                          // colSums(mis_pat), R/update_vb.R:132
-      double cnt = 0;
-      for (int i = 0; i < s->n; i++) cnt += (Yh[(size_t)i + (size_t)s->n * k] == Yh[(size_t)i + (size_t)s->n * k]) ? 1.0 : 0.0;
-      nobs[k] = cnt;
-    }
+    for (int k = 0; k < s->q; k++) nobs[k] = (double)(s->n - nmiss[k]);   // colSums(mis_pat), R/update_vb.R:132
     AQ_HIPF(hipMemcpy(s->nobs, nobs.data(), nobs.size() * sizeof(double), hipMemcpyHostToDevice));
     // padded traits need valid constants for the init-mode core kernel (coef/inv2s/cst unused there)
     std::vector<double> ones(s->q_pad, 1.0);
@@ -1505,8 +1178,6 @@ static std::vector<AqStateSeg> aq_state_segments(aq_vb *s) {
       {s->coef, Q}, {s->inv2s, Q}, {s->cst, Q}, {s->sums, 6 * Q}, {s->sc, sizeof(AqScalars)}};
   return v;
 }
-static int aq_core_kernel_id(const aq_vb *s) { return s->use_mis ? 3 : s->use_tw ? 2 : 0; }
-
 extern "C" int64_t aq_vb_state_bytes(aq_vb_handle s) {
   if (!s) return -1;
   size_t tot = sizeof(AqStateHeader) + s->trace_it.size() * (sizeof(int32_t) + sizeof(double));
@@ -1525,7 +1196,7 @@ extern "C" int aq_vb_get_state(aq_vb_handle s, void *buf, int64_t cap) {
   std::memset(&h, 0, sizeof(h));
   h.magic = AQ_STATE_MAGIC;
   h.n = s->n; h.p = s->p; h.q = s->q; h.q_total = s->q_total; h.p_pad = s->p_pad; h.q_pad = s->q_pad; h.n_pad = s->n_pad;
-  h.core_kernel = aq_core_kernel_id(s); h.trait_offset = s->trait_offset; h.scheme_df = s->scheme + 16 * s->df;
+  h.core_kernel = aq_core_kernel_id(*s); h.trait_offset = s->trait_offset; h.scheme_df = s->scheme + 16 * s->df;
   h.it = s->it; h.converged = s->converged; h.annealing = s->annealing; h.ind_batch_conv = s->ind_batch_conv;
   h.batch_conv = s->batch_conv; h.failed = s->failed; h.n_trace = (int32_t)s->trace_it.size(); h.has_missing = s->has_missing;
   h.c = s->c; h.c_s = s->c_s; h.sig2_zeta = s->sig2_zeta; h.lb_new = s->lb_new; h.lb_old = s->lb_old;
@@ -1549,9 +1220,9 @@ extern "C" int aq_vb_set_state(aq_vb_handle s, const void *buf, int64_t len) {
   if (h.magic != AQ_STATE_MAGIC) return aq_fail(AQ_ERR_ARG, "aq_vb_set_state: not an atlasqtl-hip state blob");
   if (h.n != s->n || h.p != s->p || h.q != s->q || h.q_total != s->q_total || h.has_missing != (int)s->has_missing)
     return aq_fail(AQ_ERR_ARG, "aq_vb_set_state: the state was saved for a different problem shape");
-  if (h.core_kernel != aq_core_kernel_id(s))
+  if (h.core_kernel != aq_core_kernel_id(*s))
     return aq_fail(AQ_ERR_ARG, "aq_vb_set_state: the state was saved by core kernel " + std::to_string(h.core_kernel) + ", this handle runs kernel " +
-                                   std::to_string(aq_core_kernel_id(s)) + " (0 look-ahead MFMA, 2 generic, 3 masked two-barrier): create the handle with AQ_KERNEL / "
+                                   std::to_string(aq_core_kernel_id(*s)) + " (0 look-ahead MFMA, 2 generic, 3 masked two-barrier): create the handle with AQ_KERNEL / "
                                    "AQ_GK_MAX_GB set as for the run that saved it");
   if (h.p_pad != s->p_pad || h.q_pad != s->q_pad || h.n_pad != s->n_pad)
     return aq_fail(AQ_ERR_ARG, "aq_vb_set_state: same problem, different kernel geometry (padding " + std::to_string(h.n_pad) + " / " + std::to_string(h.q_pad) +
@@ -1601,16 +1272,7 @@ extern "C" int aq_vb_get_status(aq_vb_handle s, aq_vb_status *st) {
   st->sig02_inv_vb = h.sig02_inv;
   st->sig2_inv_vb = h.sig2_inv;
   st->lentz_iters = h.lentz_iters;
-  st->core_kernel = aq_core_kernel_id(s);
-  st->split_parts = s->use_la ? s->laC : s->use_mis ? s->misC : 1;
-  st->tiles_per_group = s->use_la ? s->TT : 1;
-  st->chain_segments = s->chain > 1 ? s->chain : 0;
-  // the instance aq_launch_core dispatches to (aq_launch_la.h): a wide instance has NT2 == NT and no tiles on the recurrence wave
-  st->tiles_matrix = (s->use_la || s->use_mis) ? s->NT : 0;
-  st->tiles_matrix2 = s->use_la ? s->NT2 : 0;
-  st->tiles_recurrence = (s->use_la && !s->la_wide) ? (s->NT3x > 0 ? s->NT3x : aq_la_nt3(s->NT, s->NT2, s->TT)) : 0;
-  st->instance_flags = s->use_la ? (s->la_mask ? 1 : 0) | (s->la_wide ? 2 : 0) | (s->chain > 1 ? 4 : 0) : 0;
-  st->n_pad = s->n_pad;
+  aq_plan_to_status(*s, st);
   return AQ_OK;
 }
 
@@ -1623,6 +1285,46 @@ extern "C" int32_t aq_vb_get_overrides(aq_vb_handle s, char *buf, int32_t cap) {
     buf[m] = 0;
   }
   return n;
+}
+
+// The planner without a device: the plan fields of aq_vb_status for given sizes, missingness counts, CU count and memory, with
+// the hooks taken from `overrides` ("NAME=value NAME=value") and never from the process environment.
+extern "C" int aq_plan_query(int32_t n, int32_t p, int32_t q, int32_t max_missing, int32_t max_short_list, int32_t ncu, int64_t total_bytes,
+                             const char *overrides, aq_vb_status *out) {
+  if (!out) return aq_fail(AQ_ERR_ARG, "aq_plan_query: NULL argument");
+  std::memset(out, 0, sizeof(*out));
+  if (n < 2 || p < 1 || q < 1) return aq_fail(AQ_ERR_ARG, "aq_plan_query: n >= 2, p >= 1, q >= 1 required");
+  if (ncu < 1 || max_short_list < 0 || max_short_list > max_missing || max_missing > n)
+    return aq_fail(AQ_ERR_ARG, "aq_plan_query: ncu >= 1 and 0 <= max_short_list <= max_missing <= n required");
+  std::vector<std::pair<std::string, std::string>> hooks;
+  const std::string ov = overrides ? overrides : "";
+  for (size_t a = 0; a < ov.size();) {
+    size_t b = ov.find(' ', a);
+    if (b == std::string::npos) b = ov.size();
+    const size_t eq = ov.find('=', a);
+    if (b > a) {
+      if (eq == std::string::npos || eq >= b || eq == a) return aq_fail(AQ_ERR_ARG, "aq_plan_query: overrides must read \"NAME=value NAME=value\"");
+      hooks.push_back({ov.substr(a, eq - a), ov.substr(eq + 1, b - eq - 1)});
+    }
+    a = b + 1;
+  }
+  const AqEnv env = [&hooks](const char *name) -> const char * {
+    for (auto &hk : hooks)
+      if (hk.first == name) return hk.second.c_str();
+    return nullptr;
+  };
+  AqPlanInput in;
+  in.n = n; in.p = p; in.q = q;
+  in.has_missing = max_missing > 0; in.max_missing = max_missing; in.max_short_list = max_short_list;
+  in.ncu = ncu; in.total_bytes = total_bytes;
+  AqPlan plan;
+  std::string err;
+  const int rc = aq_make_plan(in, env, &plan, &err);
+  if (rc == AQ_ERR_DEVICE)   // the planner's only device error: the memory size is unknown where the wide split needs it
+    return aq_fail(AQ_ERR_ARG, "aq_plan_query: the wide sample split (n > 10240 or AQ_LA_C >= 9) needs total_bytes, the device's memory size");
+  if (rc != AQ_OK) return aq_fail(rc, err);
+  aq_plan_to_status(plan, out);
+  return AQ_OK;
 }
 
 extern "C" int32_t aq_vb_get_elbo_trace(aq_vb_handle s, int32_t *it_out, double *lb_out, int32_t cap) {

@@ -222,6 +222,16 @@ int aq_vb_get_status(aq_vb_handle h, aq_vb_status *st);
  * length of the full string (buf may be NULL).  A host that inherits its environment (an R session) can check it here. */
 int32_t aq_vb_get_overrides(aq_vb_handle h, char *buf, int32_t cap);
 
+/* The launch plan aq_vb_create would make, without a device: the same planner, fed with the problem sizes, the most missing
+ * samples of one trait (0 = complete Y), the largest over traits of min(missing, observed), the device's CU count and total
+ * memory (negative = unknown), and the hooks as "NAME=value NAME=value" (the format of aq_vb_get_overrides; NULL or "" = none).
+ * The process environment is never read: the result is a function of the arguments alone.  Fills the plan fields of *out
+ * (core_kernel, split_parts, tiles_per_group, chain_segments, tiles_matrix, tiles_matrix2, tiles_recurrence, instance_flags,
+ * n_pad) and zeroes the rest; a problem aq_vb_create would refuse gets the same code and message, except that an unknown
+ * memory size where the wide sample split needs it is AQ_ERR_ARG here.  No GPU needed. */
+int aq_plan_query(int32_t n, int32_t p, int32_t q, int32_t max_missing, int32_t max_short_list, int32_t ncu, int64_t total_bytes,
+                  const char *overrides, aq_vb_status *out);
+
 /* ELBO trace: up to cap (iteration, value) pairs in evaluation order; returns the count. */
 int32_t aq_vb_get_elbo_trace(aq_vb_handle h, int32_t *it_out, double *lb_out, int32_t cap);
 
