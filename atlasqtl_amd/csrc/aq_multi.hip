@@ -25,15 +25,13 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/atlasqtl_hip.h"
-
-int aq_fail_ext(int code, const std::string &msg);   // atlasqtl_hip.hip: sets this thread's aq_last_error()
+#include "aq_internal.h"   // aq_fail: sets this thread's aq_last_error()
 
 // ---- trait partition: whole 16-trait tiles, as even as tiles allow -------------------------------------------------------
 extern "C" int aq_vb_partition(int32_t q, int32_t n_parts, int32_t part, int32_t *k0, int32_t *k1) {
-  if (q < 1 || n_parts < 1 || part < 0 || part >= n_parts || !k0 || !k1) return aq_fail_ext(AQ_ERR_ARG, "aq_vb_partition: bad argument");
+  if (q < 1 || n_parts < 1 || part < 0 || part >= n_parts || !k0 || !k1) return aq_fail(AQ_ERR_ARG, "aq_vb_partition: bad argument");
   const long long ntile = ((long long)q + 15) / 16;
-  if (n_parts > ntile) return aq_fail_ext(AQ_ERR_ARG, "aq_vb_partition: more parts than 16-trait tiles");
+  if (n_parts > ntile) return aq_fail(AQ_ERR_ARG, "aq_vb_partition: more parts than 16-trait tiles");
   const long long t0 = ntile * part / n_parts, t1 = ntile * (part + 1) / n_parts;
   *k0 = (int32_t)(16 * t0);
   *k1 = (int32_t)std::min<long long>(q, 16 * t1);
@@ -194,26 +192,26 @@ void aq_rank_main(AqShared &sh, int r, const AqRankJob &job, const aq_vb_multi_o
 
 extern "C" int aq_vb_run_multi(const aq_vb_problem *prob, int32_t n_gpus, const int32_t *devices, int32_t transport,
                                aq_vb_multi_out *out) {
-  if (!prob || !out) return aq_fail_ext(AQ_ERR_ARG, "aq_vb_run_multi: NULL argument");
-  if (n_gpus < 1 || n_gpus > 64) return aq_fail_ext(AQ_ERR_ARG, "aq_vb_run_multi: n_gpus must be in 1 .. 64");
-  if (transport != 0 && transport != 1) return aq_fail_ext(AQ_ERR_ARG, "aq_vb_run_multi: transport must be 0 (RCCL) or 1 (host-staged)");
-  if (prob->q != prob->q_total) return aq_fail_ext(AQ_ERR_ARG, "aq_vb_run_multi: give the whole problem (q == q_total); the library shards it");
+  if (!prob || !out) return aq_fail(AQ_ERR_ARG, "aq_vb_run_multi: NULL argument");
+  if (n_gpus < 1 || n_gpus > 64) return aq_fail(AQ_ERR_ARG, "aq_vb_run_multi: n_gpus must be in 1 .. 64");
+  if (transport != 0 && transport != 1) return aq_fail(AQ_ERR_ARG, "aq_vb_run_multi: transport must be 0 (RCCL) or 1 (host-staged)");
+  if (prob->q != prob->q_total) return aq_fail(AQ_ERR_ARG, "aq_vb_run_multi: give the whole problem (q == q_total); the library shards it");
   if (prob->world_size > 1 || prob->ext_reduce_main || prob->ext_reduce_elbo)
-    return aq_fail_ext(AQ_ERR_ARG, "aq_vb_run_multi: world_size / ext_reduce_* belong to the aq_vb_advance protocol");
+    return aq_fail(AQ_ERR_ARG, "aq_vb_run_multi: world_size / ext_reduce_* belong to the aq_vb_advance protocol");
   if (n_gpus > 1 && (prob->init_on_device || prob->xy_on_device))
-    return aq_fail_ext(AQ_ERR_ARG, "aq_vb_run_multi: device pointers live on one GPU; pass host pointers (or init_generate) for n_gpus > 1");
+    return aq_fail(AQ_ERR_ARG, "aq_vb_run_multi: device pointers live on one GPU; pass host pointers (or init_generate) for n_gpus > 1");
   if (!prob->Y || !prob->eta || !prob->kappa || !prob->n0 || !prob->sig2_beta_vb || !prob->tau_vb || !prob->zeta_vb ||
       (!prob->init_generate && (!prob->gam_vb || !prob->mu_beta_vb)))
-    return aq_fail_ext(AQ_ERR_ARG, "aq_vb_run_multi: NULL data pointer");
+    return aq_fail(AQ_ERR_ARG, "aq_vb_run_multi: NULL data pointer");
   const int ndev = aq_device_count();
-  if (ndev < 1) return aq_fail_ext(AQ_ERR_DEVICE, "no HIP device visible: libatlasqtl_hip has no CPU fallback (MI355X / gfx950 required)");
+  if (ndev < 1) return aq_fail(AQ_ERR_DEVICE, "no HIP device visible: libatlasqtl_hip has no CPU fallback (MI355X / gfx950 required)");
   std::vector<int> dev(n_gpus);
   for (int r = 0; r < n_gpus; r++) {
     dev[r] = devices ? devices[r] : r;
-    if (dev[r] < 0 || dev[r] >= ndev) return aq_fail_ext(AQ_ERR_ARG, "aq_vb_run_multi: device ordinal out of range");
+    if (dev[r] < 0 || dev[r] >= ndev) return aq_fail(AQ_ERR_ARG, "aq_vb_run_multi: device ordinal out of range");
     if (transport == 0)
       for (int k = 0; k < r; k++)
-        if (dev[k] == dev[r]) return aq_fail_ext(AQ_ERR_ARG, "aq_vb_run_multi: RCCL needs distinct devices (transport 1 allows repeats)");
+        if (dev[k] == dev[r]) return aq_fail(AQ_ERR_ARG, "aq_vb_run_multi: RCCL needs distinct devices (transport 1 allows repeats)");
   }
   std::vector<AqRankJob> jobs(n_gpus);
   for (int r = 0; r < n_gpus; r++) {
@@ -241,10 +239,10 @@ extern "C" int aq_vb_run_multi(const aq_vb_problem *prob, int32_t n_gpus, const 
   AqShared sh(n_gpus, transport);
   if (transport == 0) {
     std::lock_guard<std::mutex> g(rccl_m);
-    if (!rccl.load()) return aq_fail_ext(AQ_ERR_DEVICE, "aq_vb_run_multi: " + rccl.err + " (transport 1 needs no RCCL)");
+    if (!rccl.load()) return aq_fail(AQ_ERR_DEVICE, "aq_vb_run_multi: " + rccl.err + " (transport 1 needs no RCCL)");
     sh.rccl = &rccl;
     const int rc = rccl.CommInitAll(sh.comm.data(), n_gpus, dev.data());
-    if (rc != 0) return aq_fail_ext(AQ_ERR_DEVICE, std::string("ncclCommInitAll: ") + rccl.GetErrorString(rc));
+    if (rc != 0) return aq_fail(AQ_ERR_DEVICE, std::string("ncclCommInitAll: ") + rccl.GetErrorString(rc));
   }
   std::vector<aq_vb_status> st(n_gpus);
   std::vector<int32_t> tr_it;
@@ -258,14 +256,14 @@ extern "C" int aq_vb_run_multi(const aq_vb_problem *prob, int32_t n_gpus, const 
   if (transport == 0)
     for (int r = 0; r < n_gpus; r++)
       if (sh.comm[r]) rccl.CommDestroy(sh.comm[r]);
-  if (sh.err_code != AQ_OK) return aq_fail_ext(sh.err_code, sh.err_msg);
+  if (sh.err_code != AQ_OK) return aq_fail(sh.err_code, sh.err_msg);
   out->it = st[0].it; out->converged = st[0].converged; out->lb_opt = st[0].lb_opt; out->diff_lb = st[0].diff_lb;
   out->sig02_inv_vb = st[0].sig02_inv_vb; out->sig2_inv_vb = st[0].sig2_inv_vb;
   out->seconds = secs;
   out->core_ms = 0.0;
   for (int r = 0; r < n_gpus; r++) {
     if (st[r].it != st[0].it || st[r].converged != st[0].converged)
-      return aq_fail_ext(AQ_ERR_DEVICE, "aq_vb_run_multi: the ranks left lock-step (different iteration counts)");
+      return aq_fail(AQ_ERR_DEVICE, "aq_vb_run_multi: the ranks left lock-step (different iteration counts)");
     if (st[r].core_ms > out->core_ms) out->core_ms = st[r].core_ms;
   }
   out->n_elbo = (int32_t)tr_it.size();

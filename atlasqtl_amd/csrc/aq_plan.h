@@ -1,6 +1,6 @@
 // aq_plan.h -- the launch planner: which sweep kernel serves a problem and with what geometry.  A pure function of the problem
 // sizes, the missingness counts, the device's CU count and memory, and the AQ_* hooks: integer and double arithmetic only, no
-// HIP header, no device code, no getenv.  aq_vb_create (atlasqtl_hip.hip) runs it before it allocates anything; aq_plan_query
+// HIP header, no device code, no getenv.  aq_vb_create (aq_vb_create.hip) runs it before it allocates anything; aq_plan_query
 // exposes it on the C ABI without a device.  This is the single place where kernel and geometry are chosen.
 #pragma once
 #include <algorithm>

@@ -10,16 +10,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string>
-#include "../../include/atlasqtl_hip.h"
-#include "aq_pair_src.h"   // aq_pair_src, aq_src_pos
-
-int aq_fail_ext(int code, const std::string &msg);   // atlasqtl_hip.hip
-
-#define AQP_HIP(call)                                                                                       \
-  do {                                                                                                      \
-    hipError_t e_ = (call);                                                                                 \
-    if (e_ != hipSuccess) { rc = aq_fail_ext(AQ_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); goto done; } \
-  } while (0)
+#include "aq_internal.h"   // aq_fail, AQ_HIP, AqDev; aq_pair_src, aq_src_pos
 
 template <typename I>
 __global__ void aq_k_iota(I *v, size_t n) {
@@ -40,54 +31,40 @@ __global__ void aq_k_bfdr_scatter(const double *__restrict__ cs, const I *__rest
 // Descending stable sort of the PPIs with their positions and the running sum of 1 - PPI along that order: the common part
 // of assign_bFDR and of the sharded cutoff search below.  Index type: 32 bits below 2^32 entries, 64 bits beyond (the p q
 // of C5 on one GPU is 4e9).  Allocates *keys (sorted PPIs), *csum (inclusive running sum of 1 - PPI), *idx (original
-// position of each sorted entry); the caller frees them.
+// position of each sorted entry).
 template <typename I>
-static int aq_sort_ppi(const double *d_ppi, size_t n, double **keys, double **csum, I **idx) {
-  int rc = AQ_OK;
-  double *tmpd = nullptr;
-  I *vin = nullptr;
-  void *tmp = nullptr;
+static int aq_sort_ppi(const double *d_ppi, size_t n, AqDev<double> *keys, AqDev<double> *csum, AqDev<I> *idx) {
+  AqDev<double> tmpd;
+  AqDev<I> vin;
+  AqDev<char> tmp;
   size_t tb_sort = 0, tb_scan = 0, tb = 0;
   const unsigned grid = (unsigned)((n + 255) / 256);
-  *keys = nullptr; *csum = nullptr; *idx = nullptr;
-  AQP_HIP(hipMalloc((void **)keys, n * sizeof(double)));
-  AQP_HIP(hipMalloc((void **)csum, n * sizeof(double)));
-  AQP_HIP(hipMalloc((void **)&tmpd, n * sizeof(double)));
-  AQP_HIP(hipMalloc((void **)&vin, n * sizeof(I)));
-  AQP_HIP(hipMalloc((void **)idx, n * sizeof(I)));
-  AQP_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb_sort, d_ppi, *keys, vin, *idx, (int64_t)n));
-  AQP_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb_scan, tmpd, *csum, (int64_t)n));
+  AQ_TRY(keys->alloc(n));
+  AQ_TRY(csum->alloc(n));
+  AQ_TRY(tmpd.alloc(n));
+  AQ_TRY(vin.alloc(n));
+  AQ_TRY(idx->alloc(n));
+  AQ_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb_sort, d_ppi, keys->get(), vin.get(), idx->get(), (int64_t)n));
+  AQ_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb_scan, tmpd.get(), csum->get(), (int64_t)n));
   tb = tb_sort > tb_scan ? tb_sort : tb_scan;
-  AQP_HIP(hipMalloc(&tmp, tb));
-  hipLaunchKernelGGL((aq_k_iota<I>), dim3(grid), dim3(256), 0, 0, vin, n);
-  AQP_HIP(hipcub::DeviceRadixSort::SortPairsDescending(tmp, tb, d_ppi, *keys, vin, *idx, (int64_t)n));   // ind <- order(vec_ppi, decreasing = TRUE)
-  hipLaunchKernelGGL(aq_k_one_minus, dim3(grid), dim3(256), 0, 0, *keys, tmpd, n);
-  AQP_HIP(hipcub::DeviceScan::InclusiveSum(tmp, tb, tmpd, *csum, (int64_t)n));                           // cumsum(1 - vec_ppi_ord)
-  AQP_HIP(hipGetLastError());
-  AQP_HIP(hipDeviceSynchronize());
-done:
-  if (tmpd) hipFree(tmpd);
-  if (vin) hipFree(vin);
-  if (tmp) hipFree(tmp);
-  if (rc != AQ_OK) {
-    if (*keys) hipFree(*keys);
-    if (*csum) hipFree(*csum);
-    if (*idx) hipFree(*idx);
-    *keys = *csum = nullptr; *idx = nullptr;
-  }
-  return rc;
+  AQ_TRY(tmp.alloc(tb));
+  hipLaunchKernelGGL((aq_k_iota<I>), dim3(grid), dim3(256), 0, 0, vin.get(), n);
+  AQ_HIP(hipcub::DeviceRadixSort::SortPairsDescending(tmp.get(), tb, d_ppi, keys->get(), vin.get(), idx->get(), (int64_t)n));   // ind <- order(vec_ppi, decreasing = TRUE)
+  hipLaunchKernelGGL(aq_k_one_minus, dim3(grid), dim3(256), 0, 0, keys->get(), tmpd.get(), n);
+  AQ_HIP(hipcub::DeviceScan::InclusiveSum(tmp.get(), tb, tmpd.get(), csum->get(), (int64_t)n));                           // cumsum(1 - vec_ppi_ord)
+  AQ_HIP(hipGetLastError());
+  AQ_HIP(hipDeviceSynchronize());
+  return AQ_OK;
 }
 
 template <typename I>
 static int aq_bfdr_typed(const double *d_ppi, double *d_fdr, size_t n) {
-  double *keys = nullptr, *csum = nullptr;
-  I *idx = nullptr;
-  int rc = aq_sort_ppi<I>(d_ppi, n, &keys, &csum, &idx);
-  if (rc != AQ_OK) return rc;
-  hipLaunchKernelGGL((aq_k_bfdr_scatter<I>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, csum, idx, d_fdr, n);
-  if (hipDeviceSynchronize() != hipSuccess) rc = aq_fail_ext(AQ_ERR_DEVICE, "assign_bFDR: scatter failed");
-  hipFree(keys); hipFree(csum); hipFree(idx);
-  return rc;
+  AqDev<double> keys, csum;
+  AqDev<I> idx;
+  AQ_TRY(aq_sort_ppi<I>(d_ppi, n, &keys, &csum, &idx));
+  hipLaunchKernelGGL((aq_k_bfdr_scatter<I>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, csum.get(), idx.get(), d_fdr, n);
+  if (hipDeviceSynchronize() != hipSuccess) return aq_fail(AQ_ERR_DEVICE, "assign_bFDR: scatter failed");
+  return AQ_OK;
 }
 
 // d_ppi, d_fdr: device vectors of len doubles (as.vector of the p x q matrix); d_fdr may alias nothing.
@@ -105,19 +82,12 @@ int aq_bfdr_device(const double *d_ppi, double *d_fdr, int64_t len) {
 // gives the running mean at the end of c's tie block; the running mean is non-decreasing along the order, so
 // {FDR < thres} is a prefix of it and a bisection over c (one 4-double all-reduce per step, driven by the caller) finds it.
 struct aq_shard_sorted {
-  double *keys = nullptr, *csum = nullptr;
-  uint32_t *idx32 = nullptr;
-  uint64_t *idx64 = nullptr;
+  AqDev<double> keys, csum;
+  AqDev<uint32_t> idx32;
+  AqDev<uint64_t> idx64;
   size_t n = 0;
 };
-void aq_shard_free(aq_shard_sorted *s) {
-  if (!s) return;
-  if (s->keys) hipFree(s->keys);
-  if (s->csum) hipFree(s->csum);
-  if (s->idx32) hipFree(s->idx32);
-  if (s->idx64) hipFree(s->idx64);
-  delete s;
-}
+void aq_shard_free(aq_shard_sorted *s) { delete s; }
 int aq_shard_sort(const double *d_ppi, int64_t len, aq_shard_sorted **out) {
   aq_shard_sorted *s = new aq_shard_sorted();
   s->n = (size_t)len;
@@ -142,12 +112,10 @@ __global__ void aq_k_shard_query(const double *__restrict__ keys, const double *
   out[4] = nge < n ? keys[nge] : -1.0;
 }
 int aq_shard_query(const aq_shard_sorted *s, double c, double out[5]) {
-  double *d = nullptr;
-  if (hipMalloc((void **)&d, 5 * sizeof(double)) != hipSuccess) return aq_fail_ext(AQ_ERR_DEVICE, "aq_shard_query: hipMalloc failed");
-  hipLaunchKernelGGL(aq_k_shard_query, dim3(1), dim3(1), 0, 0, s->keys, s->csum, s->n, c, d);
-  hipError_t e = hipMemcpy(out, d, 5 * sizeof(double), hipMemcpyDeviceToHost);
-  hipFree(d);
-  if (e != hipSuccess) return aq_fail_ext(AQ_ERR_DEVICE, std::string("aq_shard_query: ") + hipGetErrorString(e));
+  AqDev<double> d;
+  AQ_TRY(d.alloc(5));
+  hipLaunchKernelGGL(aq_k_shard_query, dim3(1), dim3(1), 0, 0, s->keys.get(), s->csum.get(), s->n, c, d.get());
+  AQ_HIP(hipMemcpy(out, d.get(), 5 * sizeof(double), hipMemcpyDeviceToHost));
   return AQ_OK;
 }
 // rs[j] += 1 for every entry of the first `upto` sorted positions (column-major position -> row = position % p), and for the
@@ -159,18 +127,15 @@ __global__ void aq_k_shard_rows(const I *__restrict__ idx, size_t upto, size_t t
   else if (i - upto < take) atomicAdd(&rs[(size_t)idx[t0 + (i - upto)] % (size_t)p], 1ull);
 }
 int aq_shard_rows(const aq_shard_sorted *s, int64_t upto, int64_t t0, int64_t take, int p, int64_t *rs_host) {
-  unsigned long long *d = nullptr;
-  if (hipMalloc((void **)&d, (size_t)p * sizeof(unsigned long long)) != hipSuccess) return aq_fail_ext(AQ_ERR_DEVICE, "aq_shard_rows: hipMalloc failed");
-  hipMemset(d, 0, (size_t)p * sizeof(unsigned long long));
+  AqDev<unsigned long long> d;
+  AQ_TRY(d.alloc_zeroed((size_t)p));
   const size_t tot = (size_t)upto + (size_t)take;
   if (tot > 0) {
     const unsigned grid = (unsigned)((tot + 255) / 256);
-    if (s->idx32) hipLaunchKernelGGL((aq_k_shard_rows<uint32_t>), dim3(grid), dim3(256), 0, 0, s->idx32, (size_t)upto, (size_t)t0, (size_t)take, p, d);
-    else hipLaunchKernelGGL((aq_k_shard_rows<uint64_t>), dim3(grid), dim3(256), 0, 0, s->idx64, (size_t)upto, (size_t)t0, (size_t)take, p, d);
+    if (s->idx32.get()) hipLaunchKernelGGL((aq_k_shard_rows<uint32_t>), dim3(grid), dim3(256), 0, 0, s->idx32.get(), (size_t)upto, (size_t)t0, (size_t)take, p, d.get());
+    else hipLaunchKernelGGL((aq_k_shard_rows<uint64_t>), dim3(grid), dim3(256), 0, 0, s->idx64.get(), (size_t)upto, (size_t)t0, (size_t)take, p, d.get());
   }
-  hipError_t e = hipMemcpy(rs_host, d, (size_t)p * sizeof(int64_t), hipMemcpyDeviceToHost);
-  hipFree(d);
-  if (e != hipSuccess) return aq_fail_ext(AQ_ERR_DEVICE, std::string("aq_shard_rows: ") + hipGetErrorString(e));
+  AQ_HIP(hipMemcpy(rs_host, d.get(), (size_t)p * sizeof(int64_t), hipMemcpyDeviceToHost));
   return AQ_OK;
 }
 
@@ -187,8 +152,7 @@ __global__ void aq_k_row_count(const double *__restrict__ m, int64_t *__restrict
 }
 int aq_row_count_device(const double *d_m, int64_t *d_rs, int p, int q, double thres, int lt) {
   hipLaunchKernelGGL(aq_k_row_count, dim3((p + 255) / 256), dim3(256), 0, 0, d_m, d_rs, p, q, thres, lt);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return aq_fail_ext(AQ_ERR_DEVICE, std::string("aq_k_row_count: ") + hipGetErrorString(e));
+  AQ_HIP(hipGetLastError());
   return AQ_OK;
 }
 
@@ -286,134 +250,108 @@ __global__ void aq_k_pairs_gather(aq_pair_src s, const double *__restrict__ key,
   fdr[r] = cs[i] / (double)(i + 1);
 }
 
-// count -> scan -> *n_sel; then the first min(limit, *n_sel) selected pairs into *okey / *oval (allocated here)
+// count -> scan -> *n_sel; then the first min(limit, *n_sel) selected pairs into *okey / *oval (allocated here; left empty when none)
 template <typename F>
-static int aq_select_compact(F f, size_t n, int64_t limit, int64_t *n_sel, double **okey, uint64_t **oval) {
-  int rc = AQ_OK;
+static int aq_select_compact(F f, size_t n, int64_t limit, int64_t *n_sel, AqDev<double> *okey, AqDev<uint64_t> *oval) {
   const size_t nw = (n + AQ_SEL_ITEMS - 1) / AQ_SEL_ITEMS;
   const unsigned grid = (unsigned)((nw + 3) / 4);
-  unsigned long long *cnt = nullptr, *off = nullptr, last[2] = {0, 0};
-  void *tmp = nullptr;
+  AqDev<unsigned long long> cnt, off;
+  unsigned long long last[2] = {0, 0};
+  AqDev<char> tmp;
   size_t tb = 0, m = 0;
-  *okey = nullptr; *oval = nullptr; *n_sel = 0;
-  AQP_HIP(hipMalloc((void **)&cnt, nw * sizeof(unsigned long long)));
-  AQP_HIP(hipMalloc((void **)&off, nw * sizeof(unsigned long long)));
-  hipLaunchKernelGGL((aq_k_sel_count<F>), dim3(grid), dim3(256), 0, 0, f, n, cnt);
-  AQP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, off, (int64_t)nw));
-  AQP_HIP(hipMalloc(&tmp, tb));
-  AQP_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, off, (int64_t)nw));
-  AQP_HIP(hipMemcpy(&last[0], cnt + (nw - 1), sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  AQP_HIP(hipMemcpy(&last[1], off + (nw - 1), sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  *n_sel = 0;
+  AQ_TRY(cnt.alloc(nw));
+  AQ_TRY(off.alloc(nw));
+  hipLaunchKernelGGL((aq_k_sel_count<F>), dim3(grid), dim3(256), 0, 0, f, n, cnt.get());
+  AQ_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt.get(), off.get(), (int64_t)nw));
+  AQ_TRY(tmp.alloc(tb));
+  AQ_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.get(), tb, cnt.get(), off.get(), (int64_t)nw));
+  AQ_HIP(hipMemcpy(&last[0], cnt.get() + (nw - 1), sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  AQ_HIP(hipMemcpy(&last[1], off.get() + (nw - 1), sizeof(unsigned long long), hipMemcpyDeviceToHost));
   *n_sel = (int64_t)(last[0] + last[1]);
   m = (size_t)(limit < *n_sel ? limit : *n_sel);
   if (m > 0) {
-    AQP_HIP(hipMalloc((void **)okey, m * sizeof(double)));
-    AQP_HIP(hipMalloc((void **)oval, m * sizeof(uint64_t)));
-    hipLaunchKernelGGL((aq_k_sel_write<F>), dim3(grid), dim3(256), 0, 0, f, n, off, m, *okey, *oval);
-    AQP_HIP(hipGetLastError());
-    AQP_HIP(hipDeviceSynchronize());
+    AQ_TRY(okey->alloc(m));
+    AQ_TRY(oval->alloc(m));
+    hipLaunchKernelGGL((aq_k_sel_write<F>), dim3(grid), dim3(256), 0, 0, f, n, off.get(), m, okey->get(), oval->get());
+    AQ_HIP(hipGetLastError());
+    AQ_HIP(hipDeviceSynchronize());
   }
-done:
-  if (cnt) hipFree(cnt);
-  if (off) hipFree(off);
-  if (tmp) hipFree(tmp);
-  if (rc != AQ_OK) {
-    if (*okey) hipFree(*okey);
-    if (*oval) hipFree(*oval);
-    *okey = nullptr; *oval = nullptr;
-  }
-  return rc;
+  return AQ_OK;
 }
 
 // rows [0, m) of the table to the host arrays that were asked for (key = the PPIs in table order)
 template <typename I>
 static int aq_pairs_emit(const aq_pair_src &src, const double *key, const uint64_t *val, const I *idx, const double *cs, size_t m,
                          int32_t *snp, int32_t *trait, double *ppi, double *beta, double *fdr) {
-  int rc = AQ_OK;
-  int32_t *d_i = nullptr;
-  double *d_d = nullptr;
-  AQP_HIP(hipMalloc((void **)&d_i, 2 * m * sizeof(int32_t)));
-  AQP_HIP(hipMalloc((void **)&d_d, 2 * m * sizeof(double)));
-  hipLaunchKernelGGL((aq_k_pairs_gather<I>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, src, key, val, idx, cs, m, d_i,
-                     d_i + m, d_d, d_d + m);
-  AQP_HIP(hipGetLastError());
-  if (snp) AQP_HIP(hipMemcpy(snp, d_i, m * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (trait) AQP_HIP(hipMemcpy(trait, d_i + m, m * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (ppi) AQP_HIP(hipMemcpy(ppi, key, m * sizeof(double), hipMemcpyDeviceToHost));
-  if (beta && src.mul) AQP_HIP(hipMemcpy(beta, d_d, m * sizeof(double), hipMemcpyDeviceToHost));
-  if (fdr) AQP_HIP(hipMemcpy(fdr, d_d + m, m * sizeof(double), hipMemcpyDeviceToHost));
-  AQP_HIP(hipDeviceSynchronize());
-done:
-  if (d_i) hipFree(d_i);
-  if (d_d) hipFree(d_d);
-  return rc;
+  AqDev<int32_t> d_i;
+  AqDev<double> d_d;
+  AQ_TRY(d_i.alloc(2 * m));
+  AQ_TRY(d_d.alloc(2 * m));
+  hipLaunchKernelGGL((aq_k_pairs_gather<I>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, src, key, val, idx, cs, m, d_i.get(),
+                     d_i.get() + m, d_d.get(), d_d.get() + m);
+  AQ_HIP(hipGetLastError());
+  if (snp) AQ_HIP(hipMemcpy(snp, d_i.get(), m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (trait) AQ_HIP(hipMemcpy(trait, d_i.get() + m, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (ppi) AQ_HIP(hipMemcpy(ppi, key, m * sizeof(double), hipMemcpyDeviceToHost));
+  if (beta && src.mul) AQ_HIP(hipMemcpy(beta, d_d.get(), m * sizeof(double), hipMemcpyDeviceToHost));
+  if (fdr) AQ_HIP(hipMemcpy(fdr, d_d.get() + m, m * sizeof(double), hipMemcpyDeviceToHost));
+  AQ_HIP(hipDeviceSynchronize());
+  return AQ_OK;
 }
 
 static int aq_pairs_ppi(const aq_pair_src &src, double thres, int64_t cap, int32_t *snp, int32_t *trait, double *ppi, double *beta,
                         double *fdr, int64_t *n_pairs) {
-  int rc = AQ_OK;
   const size_t n_el = src.tiled ? (size_t)((src.q + 15) / 16) * src.p_pad * 16 : (size_t)src.p * src.q;
-  double *ka = nullptr, *kb = nullptr;
-  uint64_t *va = nullptr, *vb = nullptr;
-  void *tmp = nullptr;
+  AqDev<double> ka, kb;
+  AqDev<uint64_t> va, vb;
+  AqDev<char> tmp;
   size_t tb = 0, tb2 = 0, m = 0, N = 0;
   int pos_bits = 1;
   aq_sel_ppi f{src, thres};
   // cap = 0 counts only: nothing is written
-  rc = aq_select_compact(f, n_el, cap > 0 ? INT64_MAX : 0, n_pairs, &ka, &va);
-  if (rc != AQ_OK) return rc;
+  AQ_TRY(aq_select_compact(f, n_el, cap > 0 ? INT64_MAX : 0, n_pairs, &ka, &va));
   N = (size_t)*n_pairs;
   m = (size_t)((int64_t)N < cap ? (int64_t)N : cap);
-  if (m == 0) goto done;
+  if (m == 0) return AQ_OK;
   while (pos_bits < 64 && ((uint64_t)src.p * (uint64_t)src.q) >> pos_bits) pos_bits++;
-  AQP_HIP(hipMalloc((void **)&kb, N * sizeof(double)));
-  AQP_HIP(hipMalloc((void **)&vb, N * sizeof(uint64_t)));
-  AQP_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, va, vb, ka, kb, (int64_t)N, 0, pos_bits));
-  AQP_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb2, kb, ka, vb, va, (int64_t)N));
+  AQ_TRY(kb.alloc(N));
+  AQ_TRY(vb.alloc(N));
+  AQ_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, va.get(), vb.get(), ka.get(), kb.get(), (int64_t)N, 0, pos_bits));
+  AQ_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb2, kb.get(), ka.get(), vb.get(), va.get(), (int64_t)N));
   if (tb2 > tb) tb = tb2;
-  AQP_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb2, kb, kb, (int64_t)m));
+  AQ_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb2, kb.get(), kb.get(), (int64_t)m));
   if (tb2 > tb) tb = tb2;
-  AQP_HIP(hipMalloc(&tmp, tb));
+  AQ_TRY(tmp.alloc(tb));
   if (src.tiled) {   // the tiled storage is not in position order: order(decreasing = TRUE) breaks ties by position
-    AQP_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, va, vb, ka, kb, (int64_t)N, 0, pos_bits));
-    AQP_HIP(hipcub::DeviceRadixSort::SortPairsDescending(tmp, tb, kb, ka, vb, va, (int64_t)N));
+    AQ_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(), tb, va.get(), vb.get(), ka.get(), kb.get(), (int64_t)N, 0, pos_bits));
+    AQ_HIP(hipcub::DeviceRadixSort::SortPairsDescending(tmp.get(), tb, kb.get(), ka.get(), vb.get(), va.get(), (int64_t)N));
   } else {
-    AQP_HIP(hipcub::DeviceRadixSort::SortPairsDescending(tmp, tb, ka, kb, va, vb, (int64_t)N));
-    { double *t = ka; ka = kb; kb = t; }
-    { uint64_t *t = va; va = vb; vb = t; }
+    AQ_HIP(hipcub::DeviceRadixSort::SortPairsDescending(tmp.get(), tb, ka.get(), kb.get(), va.get(), vb.get(), (int64_t)N));
+    std::swap(ka, kb);
+    std::swap(va, vb);
   }
   // (ka, va) = the table order; kb, vb are free: 1 - ppi and its running sum over the rows that are returned
-  hipLaunchKernelGGL(aq_k_one_minus, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, ka, kb, m);
-  AQP_HIP(hipcub::DeviceScan::InclusiveSum(tmp, tb, kb, (double *)vb, (int64_t)m));
-  AQP_HIP(hipGetLastError());
-  rc = aq_pairs_emit<uint64_t>(src, ka, va, nullptr, (const double *)vb, m, snp, trait, ppi, beta, fdr);
-done:
-  if (ka) hipFree(ka);
-  if (kb) hipFree(kb);
-  if (va) hipFree(va);
-  if (vb) hipFree(vb);
-  if (tmp) hipFree(tmp);
-  return rc;
+  hipLaunchKernelGGL(aq_k_one_minus, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, ka.get(), kb.get(), m);
+  AQ_HIP(hipcub::DeviceScan::InclusiveSum(tmp.get(), tb, kb.get(), (double *)vb.get(), (int64_t)m));
+  AQ_HIP(hipGetLastError());
+  return aq_pairs_emit<uint64_t>(src, ka.get(), va.get(), nullptr, (const double *)vb.get(), m, snp, trait, ppi, beta, fdr);
 }
 
 template <typename I>
 static int aq_pairs_fdr(const double *d_cm, const aq_pair_src &src, double thres, int64_t cap, int32_t *snp, int32_t *trait,
                         double *ppi, double *beta, double *fdr, int64_t *n_pairs) {
-  double *keys = nullptr, *csum = nullptr, *sk = nullptr;
-  uint64_t *sv = nullptr;
-  I *idx = nullptr;
-  int rc = aq_sort_ppi<I>(d_cm, (size_t)src.p * src.q, &keys, &csum, &idx);
-  if (rc != AQ_OK) return rc;
-  aq_sel_fdr f{keys, csum, thres};
-  rc = aq_select_compact(f, (size_t)src.p * src.q, cap, n_pairs, &sk, &sv);
-  if (rc == AQ_OK && sk) {
+  AqDev<double> keys, csum, sk;
+  AqDev<uint64_t> sv;
+  AqDev<I> idx;
+  AQ_TRY(aq_sort_ppi<I>(d_cm, (size_t)src.p * src.q, &keys, &csum, &idx));
+  aq_sel_fdr f{keys.get(), csum.get(), thres};
+  AQ_TRY(aq_select_compact(f, (size_t)src.p * src.q, cap, n_pairs, &sk, &sv));
+  if (sk.get()) {
     const size_t m = (size_t)(*n_pairs < cap ? *n_pairs : cap);
-    rc = aq_pairs_emit<I>(src, sk, sv, idx, csum, m, snp, trait, ppi, beta, fdr);
+    AQ_TRY(aq_pairs_emit<I>(src, sk.get(), sv.get(), idx.get(), csum.get(), m, snp, trait, ppi, beta, fdr));
   }
-  hipFree(keys); hipFree(csum); hipFree(idx);
-  if (sk) hipFree(sk);
-  if (sv) hipFree(sv);
-  return rc;
+  return AQ_OK;
 }
 
 // src_ppi / src_mul: the storage the table's ppi and beta are read from (tiled != 0: trait-tiled with p_pad rows per tile);
@@ -444,28 +382,24 @@ __global__ void aq_k_shard_pairs(aq_pair_src s, const double *__restrict__ keys,
 }
 int aq_shard_pairs(const aq_shard_sorted *sh, int64_t upto, int64_t t0, int64_t take, const double *gam_tile, const double *mu_tile,
                    int p, int q, int p_pad, int32_t *snp, int32_t *trait, double *ppi, double *beta) {
-  int rc = AQ_OK;
   const size_t m = (size_t)upto + (size_t)take;
-  int32_t *d_i = nullptr;
-  double *d_d = nullptr;
+  AqDev<int32_t> d_i;
+  AqDev<double> d_d;
   aq_pair_src src{gam_tile, mu_tile, p, q, p_pad, 1};
   if (m == 0) return AQ_OK;
-  AQP_HIP(hipMalloc((void **)&d_i, 2 * m * sizeof(int32_t)));
-  AQP_HIP(hipMalloc((void **)&d_d, 2 * m * sizeof(double)));
-  if (sh->idx32)
-    hipLaunchKernelGGL((aq_k_shard_pairs<uint32_t>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, src, sh->keys, sh->idx32,
-                       (size_t)upto, (size_t)t0, m, d_i, d_i + m, d_d, d_d + m);
+  AQ_TRY(d_i.alloc(2 * m));
+  AQ_TRY(d_d.alloc(2 * m));
+  if (sh->idx32.get())
+    hipLaunchKernelGGL((aq_k_shard_pairs<uint32_t>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, src, sh->keys.get(), sh->idx32.get(),
+                       (size_t)upto, (size_t)t0, m, d_i.get(), d_i.get() + m, d_d.get(), d_d.get() + m);
   else
-    hipLaunchKernelGGL((aq_k_shard_pairs<uint64_t>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, src, sh->keys, sh->idx64,
-                       (size_t)upto, (size_t)t0, m, d_i, d_i + m, d_d, d_d + m);
-  AQP_HIP(hipGetLastError());
-  if (snp) AQP_HIP(hipMemcpy(snp, d_i, m * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (trait) AQP_HIP(hipMemcpy(trait, d_i + m, m * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (ppi) AQP_HIP(hipMemcpy(ppi, d_d, m * sizeof(double), hipMemcpyDeviceToHost));
-  if (beta) AQP_HIP(hipMemcpy(beta, d_d + m, m * sizeof(double), hipMemcpyDeviceToHost));
-  AQP_HIP(hipDeviceSynchronize());
-done:
-  if (d_i) hipFree(d_i);
-  if (d_d) hipFree(d_d);
-  return rc;
+    hipLaunchKernelGGL((aq_k_shard_pairs<uint64_t>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, src, sh->keys.get(), sh->idx64.get(),
+                       (size_t)upto, (size_t)t0, m, d_i.get(), d_i.get() + m, d_d.get(), d_d.get() + m);
+  AQ_HIP(hipGetLastError());
+  if (snp) AQ_HIP(hipMemcpy(snp, d_i.get(), m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (trait) AQ_HIP(hipMemcpy(trait, d_i.get() + m, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (ppi) AQ_HIP(hipMemcpy(ppi, d_d.get(), m * sizeof(double), hipMemcpyDeviceToHost));
+  if (beta) AQ_HIP(hipMemcpy(beta, d_d.get() + m, m * sizeof(double), hipMemcpyDeviceToHost));
+  AQ_HIP(hipDeviceSynchronize());
+  return AQ_OK;
 }

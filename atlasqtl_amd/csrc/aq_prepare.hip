@@ -13,31 +13,24 @@
 // matrix with its column hashes, one gather pass for the compaction.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <memory>
 #include <stdint.h>
 #include <algorithm>
 #include <cmath>
 #include <string>
 #include <unordered_map>
 #include <vector>
-#include "../../include/atlasqtl_hip.h"
-
-int aq_fail_ext(int code, const std::string &msg);   // atlasqtl_hip.hip
+#include "aq_internal.h"   // aq_fail, AQ_HIP, aq_need_device, AqDev
 
 struct aq_prep {
   int n = 0, p = 0, q = 0, p_kept = 0, device = 0;
-  double *Xs = nullptr;   // n x p_kept, standardised, compact
-  double *Yc = nullptr;   // n x q, centred (NaN = missing)
+  AqDev<double> Xs;   // n x p_kept, standardised, compact
+  AqDev<double> Yc;   // n x q, centred (NaN = missing)
   std::vector<uint8_t> bool_cst, bool_coll;   // p each (bool_coll in the ORIGINAL column numbering)
   std::vector<int32_t> dup_of;                // original index of the kept column a removed duplicate equals, else -1
   std::vector<double> mean, sd;               // p each
   std::vector<int32_t> gcounts;               // 4 x p (hom A1, het, hom A2, missing): aq_prepare_data_bed only
 };
-
-#define AQR_HIP(call)                                                                                        \
-  do {                                                                                                       \
-    hipError_t e_ = (call);                                                                                  \
-    if (e_ != hipSuccess) { rc = aq_fail_ext(AQ_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); goto done; } \
-  } while (0)
 
 template <typename T>
 __device__ __forceinline__ double aq_xval(const T *X, size_t i) { return (double)X[i]; }
@@ -172,28 +165,28 @@ __global__ __launch_bounds__(256) void aq_k_centre_y(const double *__restrict__ 
 // everything from a device-resident n x p matrix on: column statistics, hashes, duplicate confirmation, compact standardise
 template <typename T>
 static int aq_prepare_x_device(aq_prep *h, const T *dX) {
-  int rc = AQ_OK;
   const int n = h->n, p = h->p;
-  double *dmean = nullptr, *dsd = nullptr;
-  uint8_t *dcst = nullptr;
-  unsigned long long *dhash = nullptr;
-  int *ddst = nullptr, *dpairs = nullptr, *dout = nullptr;
+  AqDev<double> dmean_, dsd_;
+  AqDev<uint8_t> dcst;
+  AqDev<unsigned long long> dhash;
+  AqDev<int> ddst, dpairs_, dout_;
   std::vector<unsigned long long> hash((size_t)2 * p);
   std::vector<int> dst(p, -1);
   {
-    AQR_HIP(hipMalloc((void **)&dmean, (size_t)p * sizeof(double)));
-    AQR_HIP(hipMalloc((void **)&dsd, (size_t)p * sizeof(double)));
-    AQR_HIP(hipMalloc((void **)&dcst, (size_t)p));
-    AQR_HIP(hipMalloc((void **)&dhash, (size_t)2 * p * sizeof(unsigned long long)));
-    hipLaunchKernelGGL((aq_k_col_stats<T>), dim3(p), dim3(256), 0, 0, dX, n, dmean, dsd, dcst);
+    AQ_TRY(dmean_.alloc((size_t)p));
+    AQ_TRY(dsd_.alloc((size_t)p));
+    AQ_TRY(dcst.alloc((size_t)p));
+    AQ_TRY(dhash.alloc((size_t)2 * p));
+    double *const dmean = dmean_.get(), *const dsd = dsd_.get();
+    hipLaunchKernelGGL((aq_k_col_stats<T>), dim3(p), dim3(256), 0, 0, dX, n, dmean, dsd, dcst.get());
     // first pass over the standardised values: hashes only (nothing is written yet: the compact column index needs them)
-    hipLaunchKernelGGL((aq_k_standardise<T>), dim3(p), dim3(256), 0, 0, dX, n, dmean, dsd, (const int *)nullptr, (double *)nullptr, dhash);
-    AQR_HIP(hipGetLastError());
+    hipLaunchKernelGGL((aq_k_standardise<T>), dim3(p), dim3(256), 0, 0, dX, n, dmean, dsd, (const int *)nullptr, (double *)nullptr, dhash.get());
+    AQ_HIP(hipGetLastError());
     h->bool_cst.assign(p, 0); h->bool_coll.assign(p, 0); h->dup_of.assign(p, -1); h->mean.resize(p); h->sd.resize(p);
-    AQR_HIP(hipMemcpy(h->bool_cst.data(), dcst, (size_t)p, hipMemcpyDeviceToHost));
-    AQR_HIP(hipMemcpy(h->mean.data(), dmean, (size_t)p * sizeof(double), hipMemcpyDeviceToHost));
-    AQR_HIP(hipMemcpy(h->sd.data(), dsd, (size_t)p * sizeof(double), hipMemcpyDeviceToHost));
-    AQR_HIP(hipMemcpy(hash.data(), dhash, hash.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    AQ_HIP(hipMemcpy(h->bool_cst.data(), dcst.get(), (size_t)p, hipMemcpyDeviceToHost));
+    AQ_HIP(hipMemcpy(h->mean.data(), dmean, (size_t)p * sizeof(double), hipMemcpyDeviceToHost));
+    AQ_HIP(hipMemcpy(h->sd.data(), dsd, (size_t)p * sizeof(double), hipMemcpyDeviceToHost));
+    AQ_HIP(hipMemcpy(hash.data(), dhash.get(), hash.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (const char *e = getenv("AQ_PREP_HASH_MASK")) {   // test hook: truncate the hashes so that different columns collide
       const unsigned long long mask = strtoull(e, nullptr, 0);
       for (auto &v : hash) v &= mask;
@@ -215,12 +208,13 @@ static int aq_prepare_x_device(aq_prep *h, const T *dX) {
     }
     if (!cand.empty()) {
       std::vector<int> out(cand.size(), 0);
-      AQR_HIP(hipMalloc((void **)&dpairs, pairs.size() * sizeof(int)));
-      AQR_HIP(hipMalloc((void **)&dout, out.size() * sizeof(int)));
-      AQR_HIP(hipMemcpy(dpairs, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice));
-      AQR_HIP(hipMemset(dout, 0, out.size() * sizeof(int)));
+      AQ_TRY(dpairs_.alloc(pairs.size()));
+      AQ_TRY(dout_.alloc(out.size()));
+      int *const dpairs = dpairs_.get(), *const dout = dout_.get();
+      AQ_HIP(hipMemcpy(dpairs, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice));
+      AQ_HIP(hipMemset(dout, 0, out.size() * sizeof(int)));
       hipLaunchKernelGGL((aq_k_cols_equal<T>), dim3((unsigned)cand.size()), dim3(256), 0, 0, dX, n, dmean, dsd, dpairs, dout);
-      AQR_HIP(hipMemcpy(out.data(), dout, out.size() * sizeof(int), hipMemcpyDeviceToHost));
+      AQ_HIP(hipMemcpy(out.data(), dout, out.size() * sizeof(int), hipMemcpyDeviceToHost));
       // A candidate the bitwise comparison found DIFFERENT from the first column of its hash class (a 128-bit collision) is a
       // column of its own: it joins the class, and every later candidate of the class that differs from the first member is
       // compared with the further members as well, in column order (one pair per launch: this never happens in practice).
@@ -228,10 +222,10 @@ static int aq_prepare_x_device(aq_prep *h, const T *dX) {
         const int pr2[2] = {ca, cb};
         int res = 0;
         if (hipMemcpy(dpairs, pr2, sizeof(pr2), hipMemcpyHostToDevice) != hipSuccess || hipMemset(dout, 0, sizeof(int)) != hipSuccess)
-          return aq_fail_ext(AQ_ERR_DEVICE, "aq_prepare_data: duplicate check failed");
+          return aq_fail(AQ_ERR_DEVICE, "aq_prepare_data: duplicate check failed");
         hipLaunchKernelGGL((aq_k_cols_equal<T>), dim3(1), dim3(256), 0, 0, dX, n, dmean, dsd, dpairs, dout);
         if (hipMemcpy(&res, dout, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-          return aq_fail_ext(AQ_ERR_DEVICE, "aq_prepare_data: duplicate check failed");
+          return aq_fail(AQ_ERR_DEVICE, "aq_prepare_data: duplicate check failed");
         *eq = (res == 0);
         return AQ_OK;
       };
@@ -242,8 +236,7 @@ static int aq_prepare_x_device(aq_prep *h, const T *dX) {
         bool dup = false;
         for (size_t m = 1; m < members.size() && !dup; m++) {
           bool eq = false;
-          rc = equal_on_device(members[m], j, &eq);
-          if (rc != AQ_OK) goto done;
+          AQ_TRY(equal_on_device(members[m], j, &eq));
           if (eq) { h->bool_coll[j] = 1; h->dup_of[j] = members[m]; dup = true; }
         }
         if (!dup) members.push_back(j);
@@ -253,71 +246,47 @@ static int aq_prepare_x_device(aq_prep *h, const T *dX) {
     for (int j = 0; j < p; j++)
       if (!h->bool_cst[j] && !h->bool_coll[j]) dst[j] = kept++;
     h->p_kept = kept;
-    if (kept < 1) { rc = aq_fail_ext(AQ_ERR_ARG, "There must be at least 1 non-constant candidate predictor stored in X."); goto done; }
-    AQR_HIP(hipMalloc((void **)&ddst, (size_t)p * sizeof(int)));
-    AQR_HIP(hipMemcpy(ddst, dst.data(), (size_t)p * sizeof(int), hipMemcpyHostToDevice));
-    AQR_HIP(hipMalloc((void **)&h->Xs, (size_t)n * kept * sizeof(double)));
-    hipLaunchKernelGGL((aq_k_standardise<T>), dim3(p), dim3(256), 0, 0, dX, n, dmean, dsd, ddst, h->Xs, (unsigned long long *)nullptr);
-    AQR_HIP(hipGetLastError());
-    AQR_HIP(hipDeviceSynchronize());
+    if (kept < 1) return aq_fail(AQ_ERR_ARG, "There must be at least 1 non-constant candidate predictor stored in X.");
+    AQ_TRY(ddst.alloc((size_t)p));
+    AQ_HIP(hipMemcpy(ddst.get(), dst.data(), (size_t)p * sizeof(int), hipMemcpyHostToDevice));
+    AQ_TRY(h->Xs.alloc((size_t)n * kept));
+    hipLaunchKernelGGL((aq_k_standardise<T>), dim3(p), dim3(256), 0, 0, dX, n, dmean, dsd, ddst.get(), h->Xs.get(), (unsigned long long *)nullptr);
+    AQ_HIP(hipGetLastError());
+    AQ_HIP(hipDeviceSynchronize());
   }
-done:
-  if (dmean) hipFree(dmean);
-  if (dsd) hipFree(dsd);
-  if (dcst) hipFree(dcst);
-  if (dhash) hipFree(dhash);
-  if (ddst) hipFree(ddst);
-  if (dpairs) hipFree(dpairs);
-  if (dout) hipFree(dout);
-  return rc;
+  return AQ_OK;
 }
 
 // brings the host matrix to the device and runs the pipeline on it
 template <typename T>
 static int aq_prepare_x(aq_prep *h, const T *X_host) {
-  int rc = AQ_OK;
   const size_t np = (size_t)h->n * h->p;
-  T *dX = nullptr;
-  AQR_HIP(hipMalloc((void **)&dX, np * sizeof(T)));
-  AQR_HIP(hipMemcpy(dX, X_host, np * sizeof(T), hipMemcpyHostToDevice));
-  rc = aq_prepare_x_device<T>(h, dX);
-done:
-  if (dX) hipFree(dX);
-  return rc;
+  AqDev<T> dX;
+  AQ_TRY(dX.alloc(np));
+  AQ_HIP(hipMemcpy(dX.get(), X_host, np * sizeof(T), hipMemcpyHostToDevice));
+  return aq_prepare_x_device<T>(h, dX.get());
 }
 
 extern "C" void aq_prep_destroy(aq_prep_handle h) {
   if (!h) return;
   hipSetDevice(h->device);
-  if (h->Xs) hipFree(h->Xs);
-  if (h->Yc) hipFree(h->Yc);
   delete h;
-}
-
-static int aq_check_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return aq_fail_ext(AQ_ERR_DEVICE, "no HIP device visible: libatlasqtl_hip has no CPU fallback (MI355X / gfx950 required)");
-  if (device < 0 || device >= ndev) return aq_fail_ext(AQ_ERR_ARG, "device ordinal out of range");
-  if (hipSetDevice(device) != hipSuccess) return aq_fail_ext(AQ_ERR_DEVICE, "hipSetDevice failed");
-  return AQ_OK;
 }
 
 // Y <- scale(Y, center = TRUE, scale = FALSE) into h->Yc and the two missingness guards (R/prepare_atlasqtl.R:39-45, :83)
 static int aq_prepare_y(aq_prep *h, const double *Y_host) {
-  int rc = AQ_OK;
   const int n = h->n, q = h->q;
   const size_t nq = (size_t)n * q;
-  double *dY = nullptr;
-  int *dnobs = nullptr;
+  AqDev<double> dY;
+  AqDev<int> dnobs;
   std::vector<int> nobs(q);
-  AQR_HIP(hipMalloc((void **)&dY, nq * sizeof(double)));
-  AQR_HIP(hipMalloc((void **)&h->Yc, nq * sizeof(double)));
-  AQR_HIP(hipMalloc((void **)&dnobs, (size_t)q * sizeof(int)));
-  AQR_HIP(hipMemcpy(dY, Y_host, nq * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(aq_k_centre_y, dim3(q), dim3(256), 0, 0, dY, n, h->Yc, dnobs);
-  AQR_HIP(hipGetLastError());
-  AQR_HIP(hipMemcpy(nobs.data(), dnobs, nobs.size() * sizeof(int), hipMemcpyDeviceToHost));
+  AQ_TRY(dY.alloc(nq));
+  AQ_TRY(h->Yc.alloc(nq));
+  AQ_TRY(dnobs.alloc((size_t)q));
+  AQ_HIP(hipMemcpy(dY.get(), Y_host, nq * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(aq_k_centre_y, dim3(q), dim3(256), 0, 0, dY.get(), n, h->Yc.get(), dnobs.get());
+  AQ_HIP(hipGetLastError());
+  AQ_HIP(hipMemcpy(nobs.data(), dnobs.get(), nobs.size() * sizeof(int), hipMemcpyDeviceToHost));
   {
     long long tot = 0;
     std::string low;
@@ -325,34 +294,28 @@ static int aq_prepare_y(aq_prep *h, const double *Y_host) {
       tot += nobs[k];
       if ((double)nobs[k] / n < 0.025) low += (low.empty() ? "" : " ") + std::to_string(k + 1);
     }
-    if ((double)tot / ((double)n * q) < 0.05) { rc = aq_fail_ext(AQ_ERR_ARG, "Too few non-NA values in matrix Y. Exit."); goto done; }
-    if (!low.empty()) {
-      rc = aq_fail_ext(AQ_ERR_ARG, "Column(s) " + low + " of matrix Y have more than 97.5% missing values, and should be removed. Exit.");
-      goto done;
-    }
+    if ((double)tot / ((double)n * q) < 0.05) return aq_fail(AQ_ERR_ARG, "Too few non-NA values in matrix Y. Exit.");
+    if (!low.empty())
+      return aq_fail(AQ_ERR_ARG, "Column(s) " + low + " of matrix Y have more than 97.5% missing values, and should be removed. Exit.");
   }
-done:
-  if (dY) hipFree(dY);
-  if (dnobs) hipFree(dnobs);
-  return rc;
+  return AQ_OK;
 }
 
 extern "C" int aq_prepare_data(const aq_prep_input *in, aq_prep_handle *out) {
-  if (!in || !out) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data: NULL argument");
+  if (!in || !out) return aq_fail(AQ_ERR_ARG, "aq_prepare_data: NULL argument");
   *out = nullptr;
-  if (in->n < 2 || in->p < 1 || in->q < 1) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data: n >= 2, p >= 1, q >= 1 required");
-  if ((!in->X && !in->X_i8) || !in->Y) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data: NULL data pointer");
-  if (int rc = aq_check_device(in->device)) return rc;
+  if (in->n < 2 || in->p < 1 || in->q < 1) return aq_fail(AQ_ERR_ARG, "aq_prepare_data: n >= 2, p >= 1, q >= 1 required");
+  if ((!in->X && !in->X_i8) || !in->Y) return aq_fail(AQ_ERR_ARG, "aq_prepare_data: NULL data pointer");
+  AQ_TRY(aq_need_device(in->device));
   const size_t np = (size_t)in->n * in->p;
   if (in->X)
     for (size_t i = 0; i < np; i++)   // check_structure_(X, "matrix", "numeric"): no NA, finite (R/utils.R:34-100)
-      if (!std::isfinite(in->X[i])) return aq_fail_ext(AQ_ERR_ARG, "X must be a non-empty a numeric matrix, finite without missing value.");
-  aq_prep *h = new aq_prep();
+      if (!std::isfinite(in->X[i])) return aq_fail(AQ_ERR_ARG, "X must be a non-empty a numeric matrix, finite without missing value.");
+  std::unique_ptr<aq_prep> h(new aq_prep());
   h->n = in->n; h->p = in->p; h->q = in->q; h->device = in->device;
-  int rc = in->X ? aq_prepare_x<double>(h, in->X) : aq_prepare_x<int8_t>(h, in->X_i8);
-  if (rc == AQ_OK) rc = aq_prepare_y(h, in->Y);
-  if (rc != AQ_OK) { aq_prep_destroy(h); return rc; }
-  *out = h;
+  AQ_TRY(in->X ? aq_prepare_x<double>(h.get(), in->X) : aq_prepare_x<int8_t>(h.get(), in->X_i8));
+  AQ_TRY(aq_prepare_y(h.get(), in->Y));
+  *out = h.release();
   return AQ_OK;
 }
 
@@ -465,71 +428,64 @@ __global__ __launch_bounds__(256) void aq_k_bed_impute(const int8_t *__restrict_
 }
 
 // the decode pass: packed blocks -> *dG_out (n x p int8, AQ_BED_NA = missing) and h->gcounts
-static int aq_bed_decode(aq_prep *h, const aq_prep_bed_input *in, int8_t **dG_out) {
-  int rc = AQ_OK;
+static int aq_bed_decode(aq_prep *h, const aq_prep_bed_input *in, AqDev<int8_t> *dG_out) {
   const int n = h->n, p = h->p;
   const size_t stride = ((size_t)in->n_file + 3) / 4, nbytes = (size_t)p * stride;
-  uint32_t *dbed = nullptr;
-  int32_t *didx = nullptr, *dcnt = nullptr;
+  AqDev<uint32_t> dbed;
+  AqDev<int32_t> didx, dcnt;
   const unsigned grid = (unsigned)(((long long)p + 3) / 4);
   // two dwords of padding: the aligned pair a lane reads may end one dword past the last block (those bits are shifted out)
-  AQR_HIP(hipMalloc((void **)&dbed, (nbytes / 4 + 3) * 4));
-  AQR_HIP(hipMemcpy(dbed, in->bed, nbytes, hipMemcpyHostToDevice));
-  AQR_HIP(hipMalloc((void **)dG_out, (size_t)n * p));
-  AQR_HIP(hipMalloc((void **)&dcnt, (size_t)4 * p * sizeof(int32_t)));
+  AQ_TRY(dbed.alloc(nbytes / 4 + 3));
+  AQ_HIP(hipMemcpy(dbed.get(), in->bed, nbytes, hipMemcpyHostToDevice));
+  AQ_TRY(dG_out->alloc((size_t)n * p));
+  AQ_TRY(dcnt.alloc((size_t)4 * p));
   if (in->sample_idx) {
-    AQR_HIP(hipMalloc((void **)&didx, (size_t)n * sizeof(int32_t)));
-    AQR_HIP(hipMemcpy(didx, in->sample_idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(aq_k_bed_gather, dim3(grid), dim3(256), 0, 0, (const uint8_t *)dbed, (long long)stride, n, p, didx,
-                       in->count_a2, *dG_out, dcnt);
+    AQ_TRY(didx.alloc((size_t)n));
+    AQ_HIP(hipMemcpy(didx.get(), in->sample_idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(aq_k_bed_gather, dim3(grid), dim3(256), 0, 0, (const uint8_t *)dbed.get(), (long long)stride, n, p, didx.get(),
+                       in->count_a2, dG_out->get(), dcnt.get());
   } else {
-    hipLaunchKernelGGL(aq_k_bed_decode, dim3(grid), dim3(256), 0, 0, dbed, (long long)stride, n, p, in->count_a2, *dG_out, dcnt);
+    hipLaunchKernelGGL(aq_k_bed_decode, dim3(grid), dim3(256), 0, 0, dbed.get(), (long long)stride, n, p, in->count_a2, dG_out->get(), dcnt.get());
   }
-  AQR_HIP(hipGetLastError());
+  AQ_HIP(hipGetLastError());
   h->gcounts.resize((size_t)4 * p);
-  AQR_HIP(hipMemcpy(h->gcounts.data(), dcnt, h->gcounts.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-done:
-  if (dbed) hipFree(dbed);
-  if (didx) hipFree(didx);
-  if (dcnt) hipFree(dcnt);
-  return rc;
+  AQ_HIP(hipMemcpy(h->gcounts.data(), dcnt.get(), h->gcounts.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return AQ_OK;
 }
 
 extern "C" int aq_prepare_data_bed(const aq_prep_bed_input *in, aq_prep_handle *out) {
-  if (!in || !out) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: NULL argument");
+  if (!in || !out) return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: NULL argument");
   *out = nullptr;
-  if (in->n < 2 || in->p < 1 || in->q < 1) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: n >= 2, p >= 1, q >= 1 required");
-  if (!in->bed || !in->Y) return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: NULL data pointer");
+  if (in->n < 2 || in->p < 1 || in->q < 1) return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: n >= 2, p >= 1, q >= 1 required");
+  if (!in->bed || !in->Y) return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: NULL data pointer");
   if (in->n > in->n_file)
-    return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: n = " + std::to_string(in->n) + " rows asked of a file with n_file = " +
+    return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: n = " + std::to_string(in->n) + " rows asked of a file with n_file = " +
                                        std::to_string(in->n_file) + " samples");
   if (!in->sample_idx && in->n != in->n_file)
-    return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: sample_idx is NULL, so n = " + std::to_string(in->n) +
+    return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: sample_idx is NULL, so n = " + std::to_string(in->n) +
                                        " must equal n_file = " + std::to_string(in->n_file));
   if (in->sample_idx)
     for (int i = 0; i < in->n; i++)
       if (in->sample_idx[i] < 0 || in->sample_idx[i] >= in->n_file)
-        return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: sample_idx[" + std::to_string(i) + "] = " +
+        return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: sample_idx[" + std::to_string(i) + "] = " +
                                            std::to_string(in->sample_idx[i]) + " is out of range [0, " + std::to_string(in->n_file) + ")");
   if ((in->count_a2 != 0 && in->count_a2 != 1) || (in->missing != 0 && in->missing != 1))
-    return aq_fail_ext(AQ_ERR_ARG, "aq_prepare_data_bed: count_a2 and missing must be 0 or 1");
-  if (int rc = aq_check_device(in->device)) return rc;
-  aq_prep *h = new aq_prep();
+    return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: count_a2 and missing must be 0 or 1");
+  AQ_TRY(aq_need_device(in->device));
+  std::unique_ptr<aq_prep> h(new aq_prep());
   h->n = in->n; h->p = in->p; h->q = in->q; h->device = in->device;
-  int rc = AQ_OK;
-  int8_t *dG = nullptr;
-  double *dX = nullptr, *dfill = nullptr;
+  AqDev<int8_t> dG;
+  AqDev<double> dX, dfill;
   long long n_mis = 0, p_mis = 0, first_mis = -1;
-  rc = aq_bed_decode(h, in, &dG);
-  if (rc != AQ_OK) goto done;
+  AQ_TRY(aq_bed_decode(h.get(), in, &dG));
   for (int j = 0; j < in->p; j++) {
     const int m = h->gcounts[4 * (size_t)j + 3];
     if (m > 0) { n_mis += m; p_mis++; if (first_mis < 0) first_mis = j; }
   }
   if (n_mis == 0) {
-    rc = aq_prepare_x_device<int8_t>(h, dG);
+    AQ_TRY(aq_prepare_x_device<int8_t>(h.get(), dG.get()));
   } else if (!in->missing) {
-    rc = aq_fail_ext(AQ_ERR_ARG, "X must be a non-empty a numeric matrix, finite without missing value. " + std::to_string(n_mis) +
+    return aq_fail(AQ_ERR_ARG, "X must be a non-empty a numeric matrix, finite without missing value. " + std::to_string(n_mis) +
                                      " genotype(s) in " + std::to_string(p_mis) + " variant(s) are missing among the " +
                                      std::to_string(in->n) + " samples used; the first such variant has index " +
                                      std::to_string(first_mis) + " (0-based, among the variants given). missing = \"mean\" replaces "
@@ -541,40 +497,33 @@ extern "C" int aq_prepare_data_bed(const aq_prep_bed_input *in, aq_prep_handle *
       const int n_obs = c[0] + c[1] + c[2];
       fill[j] = n_obs > 0 ? (double)(c[1] + 2 * (long long)(in->count_a2 ? c[2] : c[0])) / (double)n_obs : 0.0;
     }
-    AQR_HIP(hipMalloc((void **)&dfill, (size_t)in->p * sizeof(double)));
-    AQR_HIP(hipMemcpy(dfill, fill.data(), (size_t)in->p * sizeof(double), hipMemcpyHostToDevice));
-    AQR_HIP(hipMalloc((void **)&dX, (size_t)in->n * in->p * sizeof(double)));
-    hipLaunchKernelGGL(aq_k_bed_impute, dim3(in->p), dim3(256), 0, 0, dG, in->n, dfill, dX);
-    AQR_HIP(hipGetLastError());
-    AQR_HIP(hipDeviceSynchronize());
-    hipFree(dG); dG = nullptr;
-    rc = aq_prepare_x_device<double>(h, dX);
+    AQ_TRY(dfill.alloc((size_t)in->p));
+    AQ_HIP(hipMemcpy(dfill.get(), fill.data(), (size_t)in->p * sizeof(double), hipMemcpyHostToDevice));
+    AQ_TRY(dX.alloc((size_t)in->n * in->p));
+    hipLaunchKernelGGL(aq_k_bed_impute, dim3(in->p), dim3(256), 0, 0, dG.get(), in->n, dfill.get(), dX.get());
+    AQ_HIP(hipGetLastError());
+    AQ_HIP(hipDeviceSynchronize());
+    dG.reset();
+    AQ_TRY(aq_prepare_x_device<double>(h.get(), dX.get()));
   }
-  if (rc == AQ_OK) {
-    if (dG) { hipFree(dG); dG = nullptr; }
-    if (dX) { hipFree(dX); dX = nullptr; }
-    rc = aq_prepare_y(h, in->Y);
-  }
-done:
-  if (dG) hipFree(dG);
-  if (dX) hipFree(dX);
-  if (dfill) hipFree(dfill);
-  if (rc != AQ_OK) { aq_prep_destroy(h); return rc; }
-  *out = h;
+  dG.reset();
+  dX.reset();
+  AQ_TRY(aq_prepare_y(h.get(), in->Y));
+  *out = h.release();
   return AQ_OK;
 }
 
 extern "C" int aq_prep_genotype_counts(aq_prep_handle h, int32_t *counts) {
-  if (!h || !counts) return aq_fail_ext(AQ_ERR_ARG, "aq_prep_genotype_counts: NULL argument");
+  if (!h || !counts) return aq_fail(AQ_ERR_ARG, "aq_prep_genotype_counts: NULL argument");
   if (h->gcounts.empty())
-    return aq_fail_ext(AQ_ERR_ARG, "aq_prep_genotype_counts: the handle was not made by aq_prepare_data_bed");
+    return aq_fail(AQ_ERR_ARG, "aq_prep_genotype_counts: the handle was not made by aq_prepare_data_bed");
   std::copy(h->gcounts.begin(), h->gcounts.end(), counts);
   return AQ_OK;
 }
 
 extern "C" int aq_prep_info(aq_prep_handle h, int32_t *p_kept, uint8_t *bool_cst, uint8_t *bool_coll, int32_t *dup_of,
                             double *x_mean, double *x_sd) {
-  if (!h) return aq_fail_ext(AQ_ERR_ARG, "NULL handle");
+  if (!h) return aq_fail(AQ_ERR_ARG, "NULL handle");
   if (p_kept) *p_kept = h->p_kept;
   if (bool_cst) std::copy(h->bool_cst.begin(), h->bool_cst.end(), bool_cst);
   if (bool_coll) std::copy(h->bool_coll.begin(), h->bool_coll.end(), bool_coll);
@@ -584,15 +533,15 @@ extern "C" int aq_prep_info(aq_prep_handle h, int32_t *p_kept, uint8_t *bool_cst
   return AQ_OK;
 }
 
-extern "C" const double *aq_prep_x_device(aq_prep_handle h) { return h ? h->Xs : nullptr; }
-extern "C" const double *aq_prep_y_device(aq_prep_handle h) { return h ? h->Yc : nullptr; }
+extern "C" const double *aq_prep_x_device(aq_prep_handle h) { return h ? h->Xs.get() : nullptr; }
+extern "C" const double *aq_prep_y_device(aq_prep_handle h) { return h ? h->Yc.get() : nullptr; }
 
 extern "C" int aq_prep_get(aq_prep_handle h, double *X_out, double *Y_out) {
-  if (!h) return aq_fail_ext(AQ_ERR_ARG, "NULL handle");
-  if (hipSetDevice(h->device) != hipSuccess) return aq_fail_ext(AQ_ERR_DEVICE, "hipSetDevice failed");
-  if (X_out && hipMemcpy(X_out, h->Xs, (size_t)h->n * h->p_kept * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-    return aq_fail_ext(AQ_ERR_DEVICE, "aq_prep_get: copy of X failed");
-  if (Y_out && hipMemcpy(Y_out, h->Yc, (size_t)h->n * h->q * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-    return aq_fail_ext(AQ_ERR_DEVICE, "aq_prep_get: copy of Y failed");
+  if (!h) return aq_fail(AQ_ERR_ARG, "NULL handle");
+  if (hipSetDevice(h->device) != hipSuccess) return aq_fail(AQ_ERR_DEVICE, "hipSetDevice failed");
+  if (X_out && hipMemcpy(X_out, h->Xs.get(), (size_t)h->n * h->p_kept * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    return aq_fail(AQ_ERR_DEVICE, "aq_prep_get: copy of X failed");
+  if (Y_out && hipMemcpy(Y_out, h->Yc.get(), (size_t)h->n * h->q * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    return aq_fail(AQ_ERR_DEVICE, "aq_prep_get: copy of Y failed");
   return AQ_OK;
 }

@@ -13,16 +13,7 @@
 #include <string.h>
 #include <string>
 #include <vector>
-#include "../../include/atlasqtl_hip.h"
-#include "aq_pair_src.h"
-
-int aq_fail_ext(int code, const std::string &msg);   // atlasqtl_hip.hip
-
-#define AQS_HIP(call)                                                                                       \
-  do {                                                                                                      \
-    hipError_t e_ = (call);                                                                                 \
-    if (e_ != hipSuccess) { rc = aq_fail_ext(AQ_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); goto done; } \
-  } while (0)
+#include "aq_internal.h"   // aq_fail, AQ_HIP, AqDev; aq_pair_src
 
 #define AQS_BLOCK 256
 #define AQS_UNROLL 4          // independent loads in flight per thread (8 measured slower)
@@ -184,15 +175,14 @@ static double aq_pairwise_sum(const aq_mom_part *p, size_t n) {
 
 // count, n_nan, min, max, sum of the values of src (n_el storage elements), synchronous.  count == 0: min = +Inf, max = -Inf.
 int aq_moments_device(const aq_pair_src &src, size_t n_el, aq_moments *out) {
-  int rc = AQ_OK;
   const unsigned grid = aq_rsel_grid(n_el);
-  aq_mom_part *d = nullptr;
+  AqDev<aq_mom_part> d;
   std::vector<aq_mom_part> h(grid);
   uint64_t kmin = ~0ull, kmax = 0ull;
-  AQS_HIP(hipMalloc((void **)&d, grid * sizeof(aq_mom_part)));
-  hipLaunchKernelGGL(aq_k_moments, dim3(grid), dim3(AQS_BLOCK), 0, 0, src, n_el, d);
-  AQS_HIP(hipGetLastError());
-  AQS_HIP(hipMemcpy(h.data(), d, grid * sizeof(aq_mom_part), hipMemcpyDeviceToHost));
+  AQ_TRY(d.alloc(grid));
+  hipLaunchKernelGGL(aq_k_moments, dim3(grid), dim3(AQS_BLOCK), 0, 0, src, n_el, d.get());
+  AQ_HIP(hipGetLastError());
+  AQ_HIP(hipMemcpy(h.data(), d.get(), grid * sizeof(aq_mom_part), hipMemcpyDeviceToHost));
   out->count = out->n_nan = 0;
   for (unsigned i = 0; i < grid; i++) {
     out->count += (int64_t)h[i].count;
@@ -203,38 +193,30 @@ int aq_moments_device(const aq_pair_src &src, size_t n_el, aq_moments *out) {
   out->sum = aq_pairwise_sum(h.data(), grid);        // the workgroups' sums in a fixed pairwise order
   out->min = out->count ? aq_value_of_key(kmin) : HUGE_VAL;
   out->max = out->count ? aq_value_of_key(kmax) : -HUGE_VAL;
-done:
-  if (d) hipFree(d);
-  return rc;
+  return AQ_OK;
 }
 
 // one pass into d_hist (n_prefix x AQS_NBIN, device), copied to hist (host); synchronous
 static int aq_rsel_hist_run(const aq_pair_src &src, size_t n_el, const aq_rsel_pass &a, unsigned long long *d_hist, int64_t *hist) {
-  int rc = AQ_OK;
   const size_t bytes = (size_t)a.n_prefix * AQS_NBIN * sizeof(unsigned long long);
-  AQS_HIP(hipMemsetAsync(d_hist, 0, bytes, 0));
+  AQ_HIP(hipMemsetAsync(d_hist, 0, bytes, 0));
   hipLaunchKernelGGL(aq_k_rsel_hist, dim3(aq_rsel_grid(n_el)), dim3(AQS_BLOCK), bytes, 0, src, n_el, a, d_hist);
-  AQS_HIP(hipGetLastError());
-  AQS_HIP(hipMemcpy(hist, d_hist, bytes, hipMemcpyDeviceToHost));
-done:
-  return rc;
+  AQ_HIP(hipGetLastError());
+  AQ_HIP(hipMemcpy(hist, d_hist, bytes, hipMemcpyDeviceToHost));
+  return AQ_OK;
 }
 
 // prefix: n_prefix ascending values of key >> (shift + AQ_RSEL_BITS); the caller has checked the arguments
 int aq_rsel_hist_device(const aq_pair_src &src, size_t n_el, int n_prefix, const uint64_t *prefix, int shift, int64_t *hist) {
-  int rc = AQ_OK;
-  unsigned long long *d_hist = nullptr;
+  AqDev<unsigned long long> d_hist;
   aq_rsel_pass a;
   memset(&a, 0, sizeof(a));
   a.n_prefix = n_prefix;
   a.shift = shift;
   if (shift + AQ_RSEL_BITS < 64)
     for (int i = 0; i < n_prefix; i++) a.prefix[i] = prefix[i];
-  AQS_HIP(hipMalloc((void **)&d_hist, (size_t)n_prefix * AQS_NBIN * sizeof(unsigned long long)));
-  rc = aq_rsel_hist_run(src, n_el, a, d_hist, hist);
-done:
-  if (d_hist) hipFree(d_hist);
-  return rc;
+  AQ_TRY(d_hist.alloc((size_t)n_prefix * AQS_NBIN));
+  return aq_rsel_hist_run(src, n_el, a, d_hist.get(), hist);
 }
 
 // out[i] = the ranks[i]-th smallest value (0-based, ranks ascending); *mom the moments.  The digit loop: per wanted rank
@@ -242,24 +224,22 @@ done:
 // neighbours.
 int aq_order_stats_device(const aq_pair_src &src, size_t n_el, int n_ranks, const int64_t *ranks, double *out, aq_moments *mom,
                           const char *who) {
-  int rc = AQ_OK;
-  unsigned long long *d_hist = nullptr;
+  AqDev<unsigned long long> d_hist;
   std::vector<int64_t> hist((size_t)AQ_RSEL_MAX_PREFIX * AQS_NBIN);
   uint64_t pre[AQ_RSEL_MAX_PREFIX];
   int64_t rem[AQ_RSEL_MAX_PREFIX];
   int slot[AQ_RSEL_MAX_PREFIX];
   aq_moments m;
-  rc = aq_moments_device(src, n_el, &m);
-  if (rc != AQ_OK) return rc;
+  AQ_TRY(aq_moments_device(src, n_el, &m));
   if (mom) *mom = m;
   for (int i = 0; i < n_ranks; i++) {
     if (ranks[i] >= m.count)
-      return aq_fail_ext(AQ_ERR_ARG, std::string(who) + ": rank " + std::to_string(ranks[i]) + " is not below the number of values (" +
+      return aq_fail(AQ_ERR_ARG, std::string(who) + ": rank " + std::to_string(ranks[i]) + " is not below the number of values (" +
                                          std::to_string(m.count) + ")");
     pre[i] = 0;
     rem[i] = ranks[i];
   }
-  AQS_HIP(hipMalloc((void **)&d_hist, hist.size() * sizeof(unsigned long long)));
+  AQ_TRY(d_hist.alloc(hist.size()));
   for (int shift = 64 - AQ_RSEL_BITS; shift >= 0; shift -= AQ_RSEL_BITS) {
     aq_rsel_pass a;
     memset(&a, 0, sizeof(a));
@@ -268,23 +248,17 @@ int aq_order_stats_device(const aq_pair_src &src, size_t n_el, int n_ranks, cons
       if (i == 0 || (shift + AQ_RSEL_BITS < 64 && pre[i] != pre[i - 1])) a.prefix[a.n_prefix++] = pre[i];
       slot[i] = a.n_prefix - 1;
     }
-    rc = aq_rsel_hist_run(src, n_el, a, d_hist, hist.data());
-    if (rc != AQ_OK) goto done;
+    AQ_TRY(aq_rsel_hist_run(src, n_el, a, d_hist.get(), hist.data()));
     for (int i = 0; i < n_ranks; i++) {
       const int64_t *row = hist.data() + (size_t)slot[i] * AQS_NBIN;
       int64_t below = 0;
       int d = 0;
       while (d < AQS_NBIN && below + row[d] <= rem[i]) below += row[d++];
-      if (d == AQS_NBIN) {
-        rc = aq_fail_ext(AQ_ERR_DEVICE, std::string(who) + ": histogram holds fewer values than the moments pass counted");
-        goto done;
-      }
+      if (d == AQS_NBIN) return aq_fail(AQ_ERR_DEVICE, std::string(who) + ": histogram holds fewer values than the moments pass counted");
       rem[i] -= below;
       pre[i] = (pre[i] << AQ_RSEL_BITS) | (uint64_t)d;
     }
   }
   for (int i = 0; i < n_ranks; i++) out[i] = aq_value_of_key(pre[i]);
-done:
-  if (d_hist) hipFree(d_hist);
-  return rc;
+  return AQ_OK;
 }

@@ -1,188 +1,10 @@
-// aq_vec_kernels.h -- layout conversion, p- and q-vector updates, reductions and
-// the ELBO pieces that surround the core sweep kernel.  Step numbers (S1..S22)
-// are those of SURVEY.md section 3.2; each kernel cites the reference lines it follows.
+// aq_sweep_kernels.h -- p- and q-vector updates, reductions and the ELBO pieces that surround the core sweep kernel.
+// Step numbers (S1..S22) are those of SURVEY.md section 3.2; each kernel cites the reference lines it follows.
+// Non-template kernels: included by aq_vb_sweep.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "aq_special.h"
-
-#define AQ_RED_EXTRA 8   // scalars appended to the row-sum all-reduce payload
-
-// Device-resident scalars of the VB state (one struct, updated by 1-thread kernels).
-struct AqScalars {
-  double sig02_inv;     // horseshoe global precision sig02_inv_vb
-  double S_gam;         // sum(gam_vb) over all traits (all-reduced)
-  double T2;            // sum_k tau_k * colSums(m2_beta)_k (all-reduced)
-  double sum_zeta_old;  // sum(zeta_vb) before this sweep's zeta update (all-reduced)
-  double nu_vb, rho_vb, sig2_inv, log_sig2_inv;   // S1-S3, S8
-  double rho_xi_inv, xi_inv, nu_s0, rho_s0;       // S13, S15, S18
-  double sum_theta;     // sum(theta_vb) after S17
-  double sum_sig2_theta;
-  double sum_theta_sq;  // global-only core: sum (theta - m0)^2
-  double elbo_C;        // e_theta_hs_ / e_theta_ (replicated p-sum)
-  double elbo;          // assembled ELBO
-  unsigned long long lentz_mask[2];
-  int lentz_iters;
-  int pad_;
-};
-
-// ---------------------------------------------------------------- layouts ----
-__device__ __forceinline__ int aqv_drow(int dmode, int reg, int g) { return dmode ? (4 * g + reg) : (4 * reg + g); }
-
-// X (n x p, R column-major) -> XA / XU MFMA operand layouts (see aq_core_sweep.h)
-__global__ void aq_k_build_x_layouts(const double *__restrict__ X, double2 *__restrict__ XA,
-                                     double2 *__restrict__ XU, int n, int p, int nb, int NTT, int dmode) {
-  size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)nb * NTT * 128;
-  if (e >= total) return;
-  int lane = (int)(e & 63);
-  int h = (int)((e >> 6) & 1);
-  size_t bt = e >> 7;
-  int T = (int)(bt % NTT);
-  int b = (int)(bt / NTT);
-  int g = lane >> 4, c15 = lane & 15;
-  {
-    int snp = 16 * b + c15;
-    int s0 = 16 * T + aqv_drow(dmode, 2 * h, g), s1 = 16 * T + aqv_drow(dmode, 2 * h + 1, g);
-    double2 v;
-    v.x = (snp < p && s0 < n) ? X[(size_t)s0 + (size_t)n * snp] : 0.0;
-    v.y = (snp < p && s1 < n) ? X[(size_t)s1 + (size_t)n * snp] : 0.0;
-    XA[e] = v;
-  }
-  {
-    int s = 16 * T + c15;
-    int j0 = 16 * b + 4 * (2 * h) + g, j1 = 16 * b + 4 * (2 * h + 1) + g;
-    double2 v;
-    v.x = (s < n && j0 < p) ? X[(size_t)s + (size_t)n * j0] : 0.0;
-    v.y = (s < n && j1 < p) ? X[(size_t)s + (size_t)n * j1] : 0.0;
-    XU[e] = v;
-  }
-}
-
-// x' y over n samples with compensated (Kahan) summation: the error stays at a few ulp for any n.  A plain running sum loses about
-// sqrt(n) ulp -- 5e-14 relative in the worst of 9000 entries at n = 4000 -- and with missing values the diagonal of these blocks is
-// X_norm_sq(j, k), which goes into mu_beta_vb and tau_vb entry by entry (tests/test_gpu_link_range.py, wide-c12-na).  Once per handle.
-__device__ __forceinline__ double aq_dot_kahan(const double *__restrict__ x, const double *__restrict__ y, int n) {
-  double s = 0.0, c = 0.0;
-  for (int r = 0; r < n; r++) {
-    const double t = x[r] * y[r] - c;
-    const double u = s + t;
-    c = (u - s) - t;
-    s = u;
-  }
-  return s;
-}
-
-// diagonal Gram blocks G[b] = X_b' X_b and first off-diagonal blocks Gx[b] = X_b' X_{b-1} (16 x 16 each):
-// the only parts of cp_X (R/atlasqtl_global_local_core.R:41) the blocked recursion needs
-__global__ void aq_k_gram_blocks(const double *__restrict__ X, double *__restrict__ G, double *__restrict__ Gx, int n,
-                                 int p) {
-  int b = blockIdx.x;
-  int i = threadIdx.x >> 4, j = threadIdx.x & 15;
-  int ji = 16 * b + i, jj = 16 * b + j;
-  {   // cross block with the previous SNP block: Gx[b][i][j] = x_{16b+i}' x_{16(b-1)+j}
-    int jp = 16 * (b - 1) + j;
-    double sx = 0.0;
-    if (b > 0 && ji < p && jp < p) sx = aq_dot_kahan(X + (size_t)n * ji, X + (size_t)n * jp, n);
-    Gx[(size_t)b * 256 + threadIdx.x] = sx;
-  }
-  double s = 0.0;
-  if (ji < p && jj < p) {     // (the smaller index first: G stays exactly symmetric)
-    const int lo = i <= j ? ji : jj, hi = i <= j ? jj : ji;
-    s = aq_dot_kahan(X + (size_t)n * lo, X + (size_t)n * hi, n);
-  }
-  G[(size_t)b * 256 + threadIdx.x] = s;
-}
-
-// (rows x q) R column-major  ->  [ntile][rows_pad][16] trait-tiled; zero padded.
-// grid (ceil(rows_pad/64), ntile), 256 threads.  nan_to_zero: Y with NA -> 0 (R/atlasqtl_global_local_core.R:22)
-__global__ void aq_k_tile_from_colmajor(const double *__restrict__ src, double *__restrict__ dst, int rows, int q,
-                                        int rows_pad, int nan_to_zero) {
-  __shared__ double buf[16][65];
-  int tile = blockIdx.y;
-  int r0 = blockIdx.x * 64;
-  for (int e = threadIdx.x; e < 16 * 64; e += 256) {
-    int k = e >> 6, rr = e & 63;
-    int kk = tile * 16 + k, r = r0 + rr;
-    double v = 0.0;
-    if (kk < q && r < rows) {
-      v = src[(size_t)r + (size_t)rows * kk];
-      if (nan_to_zero && v != v) v = 0.0;
-    }
-    buf[k][rr] = v;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 16 * 64; e += 256) {
-    int rr = e >> 4, k = e & 15;
-    int r = r0 + rr;
-    if (r < rows_pad) dst[((size_t)tile * rows_pad + r) * 16 + k] = buf[k][rr];
-  }
-}
-
-// trait-tiled -> column-major (rows x q); mul != NULL gives src*mul (beta_vb = gam_vb * mu_beta_vb, R/update_vb.R:17)
-__global__ void aq_k_colmajor_from_tile(const double *__restrict__ src, const double *__restrict__ mul,
-                                        double *__restrict__ dst, int rows, int q, int rows_pad) {
-  __shared__ double buf[16][65];
-  int tile = blockIdx.y;
-  int r0 = blockIdx.x * 64;
-  for (int e = threadIdx.x; e < 16 * 64; e += 256) {
-    int rr = e >> 4, k = e & 15;
-    int r = r0 + rr;
-    double v = 0.0;
-    if (r < rows_pad) {
-      size_t off = ((size_t)tile * rows_pad + r) * 16 + k;
-      v = src[off];
-      if (mul) v *= mul[off];
-    }
-    buf[k][rr] = v;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 16 * 64; e += 256) {
-    int k = e >> 6, rr = e & 63;
-    int kk = tile * 16 + k, r = r0 + rr;
-    if (kk < q && r < rows) dst[(size_t)r + (size_t)rows * kk] = buf[k][rr];
-  }
-}
-
-// ----------------------------------------------- initial values on the device ----
-// auto_set_init_ (R/set_hyper_init.R:385-387): gam_vb = pnorm(rnorm(p q, mean = n0, sd = s02 + t02)), mu_beta_vb = rnorm(p q).
-// R's Mersenne-Twister stream cannot be reproduced anyway, so the draws come from a counter-based generator
-// that any shard can evaluate on its own: Philox4x32-10 (Salmon et al., SC'11) keyed by the seed, counter = (SNP j, global
-// trait k, 0, 0); one call yields both normals of the entry (Box-Muller).  the CPU checker under tests/ restates the same stream.
-__host__ __device__ inline void aq_philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  for (int r = 0; r < 10; r++) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
-__host__ __device__ inline void aq_init_pair(uint64_t seed, uint32_t j, uint32_t k_global, double gam_mean, double gam_sd,
-                                             double *gam, double *mu) {
-  uint32_t c[4] = {j, k_global, 0u, 0u};
-  aq_philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-  // two uniforms in (0, 1) with 53 bits each
-  const double u1 = ((double)(c[0] >> 5) * 67108864.0 + (double)(c[1] >> 6) + 0.5) * (1.0 / 9007199254740992.0);
-  const double u2 = ((double)(c[2] >> 5) * 67108864.0 + (double)(c[3] >> 6) + 0.5) * (1.0 / 9007199254740992.0);
-  const double r = sqrt(-2.0 * log(u1));
-  const double z1 = r * cos(6.283185307179586476925286766559 * u2), z2 = r * sin(6.283185307179586476925286766559 * u2);
-  *gam = 0.5 * erfc(-(gam_mean + gam_sd * z1) * 0.70710678118654752440084436210485);    // pnorm
-  *mu = z2;
-}
-// gam, mu in the trait-tiled layout [ntile][p_pad][16]; padding entries are 0
-__global__ void aq_k_init_generate(double *__restrict__ gam, double *__restrict__ mu, int p, int q, int p_pad, int ntile,
-                                   unsigned long long seed, int trait_offset, double gam_mean, double gam_sd) {
-  size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)ntile * p_pad * 16;
-  if (e >= total) return;
-  int hk = (int)(e & 15);
-  size_t rest = e >> 4;
-  int j = (int)(rest % p_pad), tile = (int)(rest / p_pad);
-  int k = tile * 16 + hk;
-  double g = 0.0, m = 0.0;
-  if (j < p && k < q) aq_init_pair(seed, (uint32_t)j, (uint32_t)(trait_offset + k), gam_mean, gam_sd, &g, &m);
-  gam[e] = g;
-  mu[e] = m;
-}
+#include "aq_vec_args.h"
 
 // ------------------------------------------------------------- pre-pass ----
 // Everything transcendental that the core sweep needs per (j,k) entry, from the current
@@ -195,15 +17,6 @@ __global__ void aq_k_init_generate(double *__restrict__ gam, double *__restrict_
 // pass adds the entropy-like p x q part of e_beta_gamma_ (R/elbo.R:10-34) for the ELBO that
 // closes the previous sweep (it needs exactly these refreshed log Phi values).
 // grid (nchunk, ntile), 256 threads: thread (hj, hk) walks rows hj, hj+16, ... of its chunk.
-struct AqPrepass {
-  const double *theta, *zeta, *gam;
-  double *Aarr, *Barr, *rowA, *colApart, *Hpart;
-  int p, q, p_pad, q_pad, rows_per_chunk;
-  double sqrt_c;
-  int c_is_one, do_H;
-  int write_AB;   // 0: only the ELBO part (do_H); A, b and the sums of a are produced inside the sweep kernel
-};
-
 __global__ __launch_bounds__(256) void aq_k_prepass(AqPrepass v) {
   __shared__ double sh[256];
   const double eps = 1.81898940354585648e-12;   // .Machine$double.eps^0.75, R/elbo.R:15
@@ -300,18 +113,6 @@ __global__ __launch_bounds__(256) void aq_k_prepass(AqPrepass v) {
 }
 
 // -------------------------------------------------------- q-vector: S1-S8 ----
-struct AqQvec {
-  const double *eta_h, *kappa_h, *n0, *nobs;  // hyper (q_pad), observed-sample counts
-  double *zeta, *tau, *sig2b, *log_tau, *eta_vb, *kappa_vb, *coef, *inv2s, *cst;
-  double *sums;  // [5][q_pad]: sum gam, sum m2, sum beta^2, sum gam*b, ||R||^2
-  const double *colApart;  // [nchunk][q_pad] column sums of the Z intercept a
-  int nchunk;
-  int q, q_pad, n;
-  double nu_h, rho_h;
-  int na;   // 1: Y has missing values: kappa uses the X_norm_sq form (R/update_vb.R:150-155), sums[2] = sum_j X_norm_sq (m2 - beta^2),
-            //    sums[5] = sum_j gam log sig2_beta_jk (sig2_beta_vb is p x q, R/update_vb.R:45)
-};
-
 // S1-S8: R/atlasqtl_global_local_core.R:134-150 with R/update_vb.R:116-159,33-50.
 // kappa in n-space: Y_norm_sq - 2 sum beta (Y'X) + sum (X'X beta) beta == ||y_k - X beta_k||^2 = sums[4].
 __global__ void aq_k_qpre(AqQvec v, AqScalars *sc, double c) {
@@ -427,13 +228,6 @@ __global__ void aq_k_take_reduced_scalars(AqScalars *sc, const double *red_tail)
 }
 
 // ------------------------------------------------- p-vector: S12-S18 --------
-struct AqPvec {
-  double *theta, *sig2_theta, *L, *lam2_inv, *Q;
-  const double *rsZ;     // all-reduced row sums of Z
-  double *part;          // [3][nblk] partial sums: theta, lam*shr*(...), sig2_theta
-  int p, p_pad;
-  double shr, m0, A2_inv, df;
-};
 
 // S12 + the shared stopping rule of Q_approx_vec (R/utils.R:380-423, note N2): bit i of the
 // AND-mask is set iff every x > 1 element has |Delta - 1| < eps2 at iteration counter j = i + 2.
@@ -750,4 +544,27 @@ __global__ void aq_k_elbo_final(AqScalars *sc, const double *ered, AqElboConst k
     G = aq_e_sig2_inv(0.5, sc->nu_s0, log_sig02_inv, 0.5, sc->rho_s0, sc->sig02_inv);
   }
   sc->elbo = A + B + C + D + E + F + G + H;
+}
+
+// NA-form sums (6 rows per slot): rows 0-3 and 5 added over the chained segments, ||R||^2 (row 4) from the last one
+__global__ void aq_k_combine_segment_sums6(double *sums, int q_pad, int nslot) {
+  int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= q_pad) return;
+  size_t Q = q_pad;
+  for (int v = 0; v < 6; v++) {
+    if (v == 4) continue;
+    double acc = sums[v * Q + k];
+    for (int s = 1; s < nslot; s++) acc += sums[(size_t)s * 6 * Q + v * Q + k];
+    sums[v * Q + k] = acc;
+  }
+  sums[4 * Q + k] = sums[(size_t)(nslot - 1) * 6 * Q + 4 * Q + k];
+}
+
+// sums[4][k] = sum over the C sample parts of their ||R_k||^2 (fixed order)
+__global__ void aq_k_sum_parts(const double *__restrict__ rnpart, double *__restrict__ dst, int C, int q_pad) {
+  int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= q_pad) return;
+  double s = 0.0;
+  for (int c = 0; c < C; c++) s += rnpart[(size_t)c * q_pad + k];
+  dst[k] = s;
 }

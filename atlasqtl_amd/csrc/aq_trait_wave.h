@@ -15,7 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "aq_special.h"
-#include "aq_vec_kernels.h"
+#include "aq_vec_args.h"
 
 struct AqTwArgs {
   const double *X;       // n x p column-major (standardised)

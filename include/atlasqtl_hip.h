@@ -404,6 +404,10 @@ int aq_special_eval_device(int32_t which, const double *x, const double *x2, dou
  * waiting for its predecessor, a sample part waiting for its partners); every later aq_vb_run / aq_vb_get_status /
  * aq_vb_get_state / aq_vb_get_result on the handle must then fail with AQ_ERR_DEVICE. */
 int aq_vb_debug_raise_errflag(aq_vb_handle h);
+/* Test hook: the bytes of device memory that the library's own allocations hold in this process at the moment (handles,
+ * prepared data, buffers of entries in flight).  0 in a fresh process; back at its earlier value once everything that was
+ * created since has been destroyed. */
+int64_t aq_debug_live_device_bytes(void);
 /* exp(x) E1(x) for a vector with the reference's shared Lentz stopping rule (R/utils.R:380-423);
  * host evaluation; writes the shared iteration count to *iters. */
 int aq_q_approx_vec(const double *x, double *out, int64_t len, int32_t *iters);

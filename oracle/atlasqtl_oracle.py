@@ -813,7 +813,7 @@ def philox4x32_10(ctr, key):
 
 def philox_init(seed, p, q, gam_mean, gam_sd, trait_offset=0):
     """gam_vb, mu_beta_vb of auto_set_init_ (R/set_hyper_init.R:385-387: pnorm(rnorm(p q, n0, sd = s02 + t02)), rnorm(p q))
-    from the counter-based stream the device uses (aq_init_pair, atlasqtl_amd/csrc/aq_vec_kernels.h): counter
+    from the counter-based stream the device uses (aq_init_pair, atlasqtl_amd/csrc/aq_setup_kernels.h): counter
     (SNP j, global trait k, 0, 0), key = seed; two 53-bit uniforms -> Box-Muller."""
     j = np.broadcast_to(np.arange(p, dtype=np.uint64)[:, None], (p, q))
     k = np.broadcast_to((np.arange(q, dtype=np.uint64) + np.uint64(trait_offset))[None, :], (p, q))

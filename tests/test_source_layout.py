@@ -1,0 +1,70 @@
+"""The source layout of atlasqtl_amd/csrc: one owner of device memory, one definition per exported symbol, and no
+hand-copied prototypes between translation units (they live in headers, where a mismatch is a compile error)."""
+import os
+import re
+
+from atlasqtl_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "atlasqtl_amd", "csrc")
+
+
+def _sources(ext=None):
+    out = {}
+    for fn in sorted(os.listdir(CSRC)):
+        path = os.path.join(CSRC, fn)
+        if os.path.isfile(path) and (ext is None or fn.endswith(ext)):
+            with open(path) as f:
+                out[fn] = f.read()
+    return out
+
+
+def _without_comments(src):
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return re.sub(r"//[^\n]*", "", src)
+
+
+# a function declarator that starts a line at file scope: optional extern "C", a return type, the name, the parameters,
+# then `{` (definition) or `;` (prototype).  Calls and local declarations are indented; `static` ones are the unit's own.
+_DECL = re.compile(r'^(?:extern\s+"C"\s+)?(?!static\b|return\b|typedef\b|using\b)[A-Za-z_][\w:<>\*&, ]*?[\s\*&](aq_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*([;{])',
+                   re.M)
+
+
+def _declarations(src):
+    """(name, is_definition, is_extern_c) of every non-static file-scope function declarator."""
+    return [(m.group(1), m.group(3) == "{", m.group(0).startswith("extern")) for m in _DECL.finditer(_without_comments(src))]
+
+
+def test_device_memory_has_one_owner():
+    assert "aq_internal.h" in _sources()
+    for fn, src in _sources().items():
+        if fn != "aq_internal.h":
+            assert "hipMalloc(" not in src and "hipFree(" not in src, fn
+    owner = _sources()["aq_internal.h"]
+    assert "hipMalloc(" in owner and "hipFree(" in owner
+
+
+def test_every_exported_symbol_is_defined_by_exactly_one_unit():
+    defined = {}
+    for fn, src in _sources(".hip").items():
+        for name, is_def, ext_c in _declarations(src):
+            if is_def and ext_c:
+                defined.setdefault(name, []).append(fn)
+    assert len(_lib.SYMBOLS) >= 15
+    for name in _lib.SYMBOLS:
+        assert len(defined.get(name, [])) == 1, (name, defined.get(name))
+
+
+def test_no_unit_declares_what_another_unit_defines():
+    units = {fn: _declarations(src) for fn, src in _sources(".hip").items()}
+    assert len(units) >= 8
+    definer = {}
+    for fn, decls in units.items():
+        for name, is_def, _ in decls:
+            if is_def:
+                definer.setdefault(name, set()).add(fn)
+    assert "aq_fail" in definer and "aq_bfdr_device" in definer      # the scan sees plain C++ definitions too
+    for fn, decls in units.items():
+        for name, is_def, _ in decls:
+            if not is_def:
+                assert not (definer.get(name, set()) - {fn}), (fn, name, "is defined in", definer[name])
