@@ -153,7 +153,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise AtlasqtlHipError(f"{LIB_PATH} not found: build it first (python -c 'import __graft_entry__ as g; "
                                    "g.build()' or make -C atlasqtl_amd/csrc). There is no CPU fallback.")
-        # PyTorch (used for device tensors and torch.distributed) ships its own copy of the HIP runtime.  If it is loaded AFTER this
+        # PyTorch (used for device tensors and the collectives of ranks.py) ships its own copy of the HIP runtime.  If it is loaded AFTER this
         # library has initialised the system copy, torch.cuda no longer finds a device ("No HIP GPUs are available"); loaded first,
         # both live together.  So: torch first, when it is installed.
         try:

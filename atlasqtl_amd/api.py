@@ -11,7 +11,8 @@ import warnings
 
 import numpy as np
 
-from .core import (atlasqtl_global_local_core_, hotspot_sizes, six_numbers_host_, sparse_output_options, value_summary)
+from .core import atlasqtl_global_local_core_
+from .postproc import hotspot_sizes, six_numbers_host_, sparse_output_options, value_summary
 from .hyper_init import prepare_list_hyper_, prepare_list_init_
 from .prepare import check_annealing_, check_positive_, check_vector_, check_verbose_, prepare_data_
 

@@ -1,16 +1,19 @@
-"""Host-side mirror of the reference's operator interface for the VB hot path.
+"""Host-side mirror of the reference's driver interface for the VB hot path.
 
 Same names, argument meaning and error behaviour as the reference's R functions,
 with the arithmetic done by libatlasqtl_hip.so on the GPU:
 
-  coreDualLoop(...) / coreDualMisLoop(...)     R/RcppExports.R:4-10  (in place, as the reference)
   atlasqtl_global_local_core_(...)             R/atlasqtl_global_local_core.R:8-433
+  atlasqtl_global_core_(...)                   R/atlasqtl_global_core.R:8-366
 
-One process drives one GPU.  With a torch.distributed process group the trait
+One process drives one GPU.  With a process group (ranks.RankGroup) the trait
 axis q is sharded over the ranks: each rank passes its own columns of Y and of
 the q-indexed hyper-parameters / initial values; the only exchange per sweep is
 one SUM all-reduce (RCCL over xGMI) of aq_vb_reduce_len(p) doubles, plus one of
 8 doubles on the sweeps where the ELBO is evaluated.
+
+The in-place operators live in operators.py and the handle-free post-processing in postproc.py; their names stay
+importable from here.
 """
 from __future__ import annotations
 
@@ -20,78 +23,11 @@ import numpy as np
 
 from . import _lib
 from ._lib import AqVbProblem, AqVbStatus, as_dp, as_ip, check, lib
-
-
-def _f64F(a, name, shape=None):
-    a = np.asarray(a)
-    if a.dtype != np.float64 or not a.flags.f_contiguous:
-        raise TypeError(f"{name} must be a float64 Fortran-ordered (R layout) array; it is updated in place")
-    if shape is not None and tuple(a.shape) != tuple(shape):
-        raise ValueError(f"{name} must have shape {shape}, got {a.shape}")
-    return a
-
-
-def _vec(a, name, n):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    if a.shape != (n,):
-        raise ValueError(f"{name} must have length {n}")
-    return a
-
-
-def coreDualLoop(cp_X, cp_Y_X, gam_vb, log_Phi_theta_plus_zeta, log_1_min_Phi_theta_plus_zeta, log_sig2_inv_vb,
-                 log_tau_vb, m1_beta, cp_betaX_X, mu_beta_vb, sig2_beta_vb, tau_vb, shuffled_ind, sample_q, c=1.0):
-    """R/RcppExports.R:4-6 -> src/coreLoop.cpp:38-86.  gam_vb, m1_beta, cp_betaX_X, mu_beta_vb are
-    modified in place (they must be float64 Fortran-ordered p x q arrays); returns None."""
-    gam_vb = _f64F(gam_vb, "gam_vb")
-    p, q = gam_vb.shape
-    cp_X = _f64F(np.asfortranarray(cp_X, dtype=np.float64), "cp_X", (p, p))
-    cp_Y_X = _f64F(np.asfortranarray(cp_Y_X, dtype=np.float64), "cp_Y_X", (q, p))
-    lP = _f64F(np.asfortranarray(log_Phi_theta_plus_zeta, dtype=np.float64), "log_Phi_theta_plus_zeta", (p, q))
-    l1 = _f64F(np.asfortranarray(log_1_min_Phi_theta_plus_zeta, dtype=np.float64), "log_1_min_Phi_theta_plus_zeta",
-               (p, q))
-    m1_beta = _f64F(m1_beta, "m1_beta", (p, q))
-    cp_betaX_X = _f64F(cp_betaX_X, "cp_betaX_X", (p, q))
-    mu_beta_vb = _f64F(mu_beta_vb, "mu_beta_vb", (p, q))
-    lt = _vec(log_tau_vb, "log_tau_vb", q)
-    s2 = _vec(sig2_beta_vb, "sig2_beta_vb", q)
-    tv = _vec(tau_vb, "tau_vb", q)
-    si = np.ascontiguousarray(shuffled_ind, dtype=np.int32)
-    sq = np.ascontiguousarray(sample_q, dtype=np.int32)
-    rc = lib().aq_core_dual_loop(as_dp(cp_X), as_dp(cp_Y_X), as_dp(gam_vb), as_dp(lP), as_dp(l1),
-                                 float(log_sig2_inv_vb), as_dp(lt), as_dp(m1_beta), as_dp(cp_betaX_X),
-                                 as_dp(mu_beta_vb), as_dp(s2), as_dp(tv), as_ip(si), len(si), as_ip(sq), len(sq),
-                                 float(c), p, q)
-    check(rc, "coreDualLoop")
-
-
-def coreDualMisLoop(cp_X, cp_X_rm, cp_Y_X, gam_vb, log_Phi_theta_plus_zeta, log_1_min_Phi_theta_plus_zeta,
-                    log_sig2_inv_vb, log_tau_vb, m1_beta, cp_betaX_X, mu_beta_vb, sig2_beta_vb, tau_vb, shuffled_ind,
-                    sample_q, c=1.0):
-    """R/RcppExports.R:8-10 -> src/coreLoop.cpp:91-138.  cp_X_rm: list of q (p x p) matrices;
-    sig2_beta_vb: p x q.  In place like coreDualLoop."""
-    gam_vb = _f64F(gam_vb, "gam_vb")
-    p, q = gam_vb.shape
-    if len(cp_X_rm) != q:
-        raise ValueError("cp_X_rm must be a list of q matrices")
-    cp_X = np.asfortranarray(cp_X, dtype=np.float64)
-    rms = [_f64F(np.asfortranarray(m, dtype=np.float64), "cp_X_rm[[k]]", (p, p)) for m in cp_X_rm]
-    arr = (_lib.dp * q)(*[as_dp(m) for m in rms])
-    cp_Y_X = np.asfortranarray(cp_Y_X, dtype=np.float64)
-    lP = np.asfortranarray(log_Phi_theta_plus_zeta, dtype=np.float64)
-    l1 = np.asfortranarray(log_1_min_Phi_theta_plus_zeta, dtype=np.float64)
-    m1_beta = _f64F(m1_beta, "m1_beta", (p, q))
-    cp_betaX_X = _f64F(cp_betaX_X, "cp_betaX_X", (p, q))
-    mu_beta_vb = _f64F(mu_beta_vb, "mu_beta_vb", (p, q))
-    s2 = _f64F(np.asfortranarray(sig2_beta_vb, dtype=np.float64), "sig2_beta_vb", (p, q))
-    lt = _vec(log_tau_vb, "log_tau_vb", q)
-    tv = _vec(tau_vb, "tau_vb", q)
-    si = np.ascontiguousarray(shuffled_ind, dtype=np.int32)
-    sq = np.ascontiguousarray(sample_q, dtype=np.int32)
-    rc = lib().aq_core_dual_mis_loop(as_dp(cp_X), arr, as_dp(cp_Y_X), as_dp(gam_vb), as_dp(lP), as_dp(l1),
-                                     float(log_sig2_inv_vb), as_dp(lt), as_dp(m1_beta), as_dp(cp_betaX_X),
-                                     as_dp(mu_beta_vb), as_dp(s2), as_dp(tv), as_ip(si), len(si), as_ip(sq), len(sq),
-                                     float(c), p, q)
-    check(rc, "coreDualMisLoop")
+from .operators import coreDualLoop, coreDualMisLoop  # noqa: F401
+from .postproc import (SPARSE_OUTPUT_DEFAULTS, _fetch_pairs, _key_to_double, assign_bFDR, associations,  # noqa: F401
+                       fdr_cutoff, hotspot_sizes, merge_pair_tables, order_stats_, quantile_ranks_, radix_select_,
+                       six_numbers_, six_numbers_host_, sparse_output_options, value_summary)
+from .ranks import RankGroup
 
 
 def _build_problem(Y, X, prep, n, p, q, q_total, list_hyper, list_init, anneal, tol, maxit, thinned_elbo_eval, debug, device,
@@ -194,16 +130,15 @@ class VbRun:
         self.q_total = int(q if q_total is None else q_total)
         self.pg = process_group
         self.trait_offset = int(trait_offset)
+        self.ranks = None                   # ranks.RankGroup: the collectives over the trait shards
         self.world = 1
         self._red = self._ered = None
         ext_main = ext_elbo = None
         if process_group is not None:
-            import torch
-            import torch.distributed as dist
-            self.world = dist.get_world_size(process_group)
-            dev = torch.device("cuda", device)
-            self._red = torch.zeros(int(L.aq_vb_reduce_len(p)), dtype=torch.float64, device=dev)
-            self._ered = torch.zeros(8, dtype=torch.float64, device=dev)
+            self.ranks = RankGroup(process_group, device)
+            self.world = self.ranks.world
+            self._red = self.ranks.device_zeros(L.aq_vb_reduce_len(p))
+            self._ered = self.ranks.device_zeros(8)
             ext_main, ext_elbo = self._red.data_ptr(), self._ered.data_ptr()
         pr, keep = _build_problem(Y, X, prep, n, p, q, self.q_total, list_hyper, list_init, anneal, tol, maxit, thinned_elbo_eval,
                                   debug, device, self.world, trait_offset, scheme, df, ext_main, ext_elbo)
@@ -223,19 +158,6 @@ class VbRun:
         except Exception:
             pass
 
-    def _allreduce(self, which):
-        if self.pg is None:
-            return
-        import torch.distributed as dist
-        t = self._red if which == 0 else self._ered
-        if dist.get_backend(self.pg) == "gloo":
-            # CPU-staged exchange (tests on a one-GPU box); RCCL reduces the device buffer in place
-            h = t.cpu()
-            dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.pg)
-            t.copy_(h)
-        else:
-            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.pg)
-
     def advance_until_done(self):
         """aq_vb_advance loop; all-reduces the payloads across the process group."""
         L = lib()
@@ -245,7 +167,7 @@ class VbRun:
                 check(-rc, "aq_vb_advance")
             if rc == _lib.AQ_VB_DONE:
                 return
-            self._allreduce(0 if rc == _lib.AQ_VB_NEED_ALLREDUCE_MAIN else 1)
+            self.ranks.allreduce_device(self._red if rc == _lib.AQ_VB_NEED_ALLREDUCE_MAIN else self._ered)
 
     def run(self):
         if self.pg is None:
@@ -274,97 +196,35 @@ class VbRun:
             check(lib().aq_vb_hotspot_sizes(self.h, float(thres), int(bool(fdr_adjust)), rs.ctypes.data_as(C.POINTER(C.c_int64)),
                                             C.byref(tot)), "aq_vb_hotspot_sizes")
             if self.pg is not None:
-                rs = self._sum_over_ranks(rs)
+                rs = self.ranks.sum(rs)
             return rs, int(rs.sum()) if self.pg is not None else int(tot.value)
         return self._hotspot_sizes_fdr_sharded(float(thres))
 
-    def _sum_over_ranks(self, a):
-        import torch
-        import torch.distributed as dist
-        t = torch.from_numpy(np.ascontiguousarray(a))
-        if dist.get_backend(self.pg) != "gloo":
-            t = t.cuda()
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.pg)
-        return t.cpu().numpy()
-
     def _hotspot_sizes_fdr_sharded(self, thres):
-        """rowSums(assign_bFDR(gam_vb) < thres) over the traits of all ranks: the cutoff of `_fdr_cutoff_sharded`, counted
-        per predictor by aq_vb_bfdr_rows and summed over the ranks."""
+        """rowSums(assign_bFDR(gam_vb) < thres) over the traits of all ranks: the cutoff of `_fdr_cutoff`, counted per
+        predictor by aq_vb_bfdr_rows and summed over the ranks."""
         L = lib()
         check(L.aq_vb_bfdr_begin(self.h), "aq_vb_bfdr_begin")
         try:
             rs = np.zeros(self.p, dtype=np.int64)
-            cut = self._fdr_cutoff_sharded(thres)
+            cut = self._fdr_cutoff(thres)
             if cut is None:                                       # FDR of the very first entry >= thres: nothing qualifies
                 return rs, 0
             upto, tie_first, take = cut
             check(L.aq_vb_bfdr_rows(self.h, upto, tie_first, take, rs.ctypes.data_as(C.POINTER(C.c_int64))), "aq_vb_bfdr_rows")
-            rs = self._sum_over_ranks(rs)
+            rs = self.ranks.sum(rs)
             return rs, int(rs.sum())
         finally:
             L.aq_vb_bfdr_end(self.h)
 
-    def _fdr_cutoff_sharded(self, thres):
+    def _fdr_cutoff(self, thres):
         """Between aq_vb_bfdr_begin and aq_vb_bfdr_end: this rank's part (upto, tie_first, take) of the global
-        {FDR < thres} set, or None when it is empty.
-        {FDR < thres} is a prefix of the global decreasing PPI order (the running mean of 1 - PPI never decreases along
-        it).  M(c) = mean of 1 - PPI over all entries >= c is the estimated FDR at the end of c's tie block; it grows as c
-        falls, so a bisection over the bit patterns of c in [0, max PPI] finds the smallest c* with M(c*) < thres: every
-        entry >= c* is in.  Of the next tie block down, the first entries (original order: lower ranks, then position) are
-        in for as long as the running mean stays below thres.  Every step all-reduces four numbers."""
-        import struct
-        import torch
-        import torch.distributed as dist
-        L = lib()
-        rank, world = dist.get_rank(self.pg), dist.get_world_size(self.pg)
-        bits = lambda x: struct.unpack("<q", struct.pack("<d", x))[0]
-        val = lambda b: struct.unpack("<d", struct.pack("<q", b))[0]
-
-        def query(c):              # local five numbers, global sums of the first four
+        {FDR < thres} set, or None when it is empty (postproc.fdr_cutoff over this handle's sorted shard)."""
+        def query(c):
             out = np.zeros(5)
-            check(L.aq_vb_bfdr_query(self.h, float(c), as_dp(out)), "aq_vb_bfdr_query")
-            return out, self._sum_over_ranks(out[:4].copy())
-
-        def below(c):              # M(c) < thres, with at least one entry >= c
-            _, g = query(c)
-            return g[0] > 0 and g[1] / g[0] < thres
-
-        vmax = self._max_over_ranks(query(2.0)[0][4])         # the largest PPI of all
-        if not below(vmax):
-            return None
-        if below(0.0):
-            c_star = 0.0
-        else:
-            lo, hi = bits(0.0), bits(vmax)                    # below(lo) false, below(hi) true
-            while hi - lo > 1:
-                mid = (lo + hi) // 2
-                lo, hi = (lo, mid) if below(val(mid)) else (mid, hi)
-            c_star = val(hi)
-        loc, g = query(c_star)
-        upto = int(loc[0])                                    # this rank's entries >= c*
-        n_star, s_star = float(g[0]), float(g[1])
-        tie_val = self._max_over_ranks(loc[4])                # next PPI value down, over all ranks (-1: none)
-        take, tie_first = 0, upto
-        if tie_val >= 0.0:
-            loc_t, g_t = query(tie_val)
-            t_loc, t_glob = int(loc_t[0]) - int(loc_t[2]), int(g_t[0] - g_t[2])
-            d = 1.0 - tie_val
-            step_ok = lambda i: (s_star + i * d) / (n_star + i) < thres      # running mean after i entries of the block
-            i = 0
-            if d > thres:                                     # (else the whole block would have qualified)
-                i = int(max(0, min(t_glob, np.floor((thres * n_star - s_star) / (d - thres)))))
-                while i > 0 and not step_ok(i):
-                    i -= 1
-                while i < t_glob and step_ok(i + 1):
-                    i += 1
-            counts = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
-            tl = torch.tensor([t_loc], dtype=torch.int64)
-            if dist.get_backend(self.pg) != "gloo":
-                counts, tl = [c.cuda() for c in counts], tl.cuda()
-            dist.all_gather(counts, tl, group=self.pg)
-            before = sum(int(c.item()) for c in counts[:rank])                # ties of lower ranks come first
-            take = int(min(max(i - before, 0), t_loc))
-        return upto, tie_first, take
+            check(lib().aq_vb_bfdr_query(self.h, c, as_dp(out)), "aq_vb_bfdr_query")
+            return out
+        return fdr_cutoff(query, self.ranks, thres)
 
     def associations(self, thres=0.5, fdr_adjust=False, max_pairs=None):
         """The associated (SNP, trait) pairs as a table, from the gam_vb / mu_beta_vb resident on the device (no p x q copy
@@ -380,13 +240,13 @@ class VbRun:
             tab = self._select_pairs(thres, fdr_adjust, max_pairs)
             if self.pg is None:
                 return tab
-            n_pairs = int(self._sum_over_ranks(np.array([tab["n_pairs"]], dtype=np.int64))[0])
+            n_pairs = int(self.ranks.sum(np.array([tab["n_pairs"]], dtype=np.int64))[0])
         else:
             L = lib()
             check(L.aq_vb_bfdr_begin(self.h), "aq_vb_bfdr_begin")
             try:
-                upto, tie_first, take = self._fdr_cutoff_sharded(thres) or (0, 0, 0)
-                n_pairs = int(self._sum_over_ranks(np.array([upto + take], dtype=np.int64))[0])
+                upto, tie_first, take = self._fdr_cutoff(thres) or (0, 0, 0)
+                n_pairs = int(self.ranks.sum(np.array([upto + take], dtype=np.int64))[0])
                 if max_pairs is not None:                     # a rank's share of the first max_pairs rows is among its own first
                     upto = min(upto, int(max_pairs))
                     take = min(take, int(max_pairs) - upto)
@@ -408,32 +268,10 @@ class VbRun:
         return tab
 
     def _gather_tables(self, tab):
-        """Every rank's rows (snp, global trait, ppi, beta) on every rank: one all-gather of the counts, one of the rows
-        padded to the longest table (int32 indices travel as doubles, exactly)."""
-        import torch
-        import torch.distributed as dist
-        world = dist.get_world_size(self.pg)
-        dev = (lambda t: t) if dist.get_backend(self.pg) == "gloo" else (lambda t: t.cuda())
-        m = len(tab["snp"])
-        counts = [dev(torch.zeros(1, dtype=torch.int64)) for _ in range(world)]
-        dist.all_gather(counts, dev(torch.tensor([m], dtype=torch.int64)), group=self.pg)
-        counts = [int(c.item()) for c in counts]
-        buf = torch.zeros((max(max(counts), 1), 4), dtype=torch.float64)
-        buf[:m] = torch.from_numpy(np.column_stack([tab["snp"], tab["trait"], tab["ppi"], tab["beta"]]).astype(np.float64))
-        outs = [dev(torch.zeros_like(buf)) for _ in range(world)]
-        dist.all_gather(outs, dev(buf), group=self.pg)
-        outs = [o.cpu().numpy()[:c] for o, c in zip(outs, counts)]
+        """Every rank's rows (snp, global trait, ppi, beta) on every rank (int32 indices travel as doubles, exactly)."""
+        rows = np.column_stack([tab["snp"], tab["trait"], tab["ppi"], tab["beta"]]).astype(np.float64)
         return [dict(snp=o[:, 0].astype(np.int32), trait=o[:, 1].astype(np.int32), ppi=o[:, 2].copy(), beta=o[:, 3].copy())
-                for o in outs]
-
-    def _max_over_ranks(self, v):
-        import torch
-        import torch.distributed as dist
-        t = torch.tensor([float(v)], dtype=torch.float64)
-        if dist.get_backend(self.pg) != "gloo":
-            t = t.cuda()
-        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.pg)
-        return float(t.item())
+                for o in self.ranks.gather_rows(rows)]
 
     def value_summary(self, which):
         """Min., 1st Qu., Median, Mean, 3rd Qu., Max. of all p q entries of "gam_vb" or "beta_vb" (= gam_vb * mu_beta_vb), as
@@ -449,23 +287,19 @@ class VbRun:
         mom = _lib.AqMoments()
         if self.pg is None:
             check(L.aq_vb_moments(self.h, w, C.byref(mom)), "aq_vb_moments")
-            ranks = quantile_ranks_(mom.count)
-            r = np.asarray(ranks, dtype=np.int64)
-            out = np.zeros(r.size)
-            check(L.aq_vb_order_stats(self.h, w, r.size, r.ctypes.data_as(C.POINTER(C.c_int64)), as_dp(out), C.byref(mom)),
-                  "aq_vb_order_stats")
-            return six_numbers_(mom.count, dict(zip(ranks, out.tolist())), mom.sum, mom.n_nan)
+            mom, stat = order_stats_(mom.count, lambda *out: L.aq_vb_order_stats(self.h, w, *out), "aq_vb_order_stats")
+            return six_numbers_(mom.count, stat, mom.sum, mom.n_nan)
         check(L.aq_vb_moments(self.h, w, C.byref(mom)), "aq_vb_moments")
-        count, n_nan = (int(v) for v in self._sum_over_ranks(np.array([mom.count, mom.n_nan], dtype=np.int64)))
-        total = self._sum_in_rank_order(mom.sum)
-        lo, hi = -self._max_over_ranks(-mom.min), self._max_over_ranks(mom.max)
+        count, n_nan = (int(v) for v in self.ranks.sum(np.array([mom.count, mom.n_nan], dtype=np.int64)))
+        total = self.ranks.sum_in_rank_order(mom.sum)
+        lo, hi = -self.ranks.max(-mom.min), self.ranks.max(mom.max)
 
         def hist_fn(prefixes, shift):
             pre = np.asarray(prefixes, dtype=np.uint64)
             hist = np.zeros((pre.size, 1 << _lib.AQ_RSEL_BITS), dtype=np.int64)
             check(L.aq_vb_radix_hist(self.h, w, pre.size, pre.ctypes.data_as(C.POINTER(C.c_uint64)), int(shift),
                                      hist.ctypes.data_as(C.POINTER(C.c_int64))), "aq_vb_radix_hist")
-            return self._sum_over_ranks(hist)
+            return self.ranks.sum(hist)
 
         ranks = quantile_ranks_(count)
         stat = dict(zip(ranks, radix_select_(hist_fn, ranks, _lib.AQ_RSEL_BITS)))
@@ -473,20 +307,6 @@ class VbRun:
         if out["min"] != lo or out["max"] != hi:
             raise _lib.AtlasqtlHipError("value_summary: the select's extremes differ from the moments pass's")
         return out
-
-    def _sum_in_rank_order(self, v):
-        """Sum of one double per rank, added in rank order on every rank: the same bits everywhere (an all-reduce may add
-        in another order on another rank)."""
-        import torch
-        import torch.distributed as dist
-        world = dist.get_world_size(self.pg)
-        dev = (lambda t: t) if dist.get_backend(self.pg) == "gloo" else (lambda t: t.cuda())
-        parts = [dev(torch.zeros(1, dtype=torch.float64)) for _ in range(world)]
-        dist.all_gather(parts, dev(torch.tensor([float(v)], dtype=torch.float64)), group=self.pg)
-        total = 0.0
-        for t in parts:
-            total += float(t.item())
-        return total
 
     def get_state(self):
         """The complete loop state between two sweeps as one uint8 array (aq_vb_get_state): unlike the reference's
@@ -529,36 +349,26 @@ class VbRun:
 
     def result(self, full_output=False, dense=True):
         """dense=False skips the p x q matrices (beta_vb, gam_vb, mu_beta_vb): aq_vb_get_result gets NULL for them."""
-        p, q = self.p, self.q
-        if not dense:
-            return self._result_vectors(full_output)
-        beta = np.zeros((p, q), order="F"); gam = np.zeros((p, q), order="F")
-        theta = np.zeros(p); zeta = np.zeros(q)
-        mu = np.zeros((p, q), order="F") if full_output else None
-        lam = np.zeros(p) if full_output else None
-        s2t = np.zeros(p) if full_output else None
-        tau = np.zeros(q) if full_output else None
-        s2b = np.zeros(q) if full_output else None
+        out = _result_buffers(self.p, self.q, full_output, dense)
         nul = C.cast(None, _lib.dp)
-        check(lib().aq_vb_get_result(self.h, as_dp(beta), as_dp(gam), as_dp(mu) if full_output else nul, as_dp(theta),
-                                     as_dp(zeta), as_dp(lam) if full_output else nul,
-                                     as_dp(s2t) if full_output else nul, as_dp(tau) if full_output else nul,
-                                     as_dp(s2b) if full_output else nul), "aq_vb_get_result")
-        out = dict(beta_vb=beta, gam_vb=gam, theta_vb=theta, zeta_vb=zeta)
-        if full_output:
-            out.update(mu_beta_vb=mu, lam2_inv_vb=lam, sig2_theta_vb=s2t, tau_vb=tau, sig2_beta_vb=s2b)
+        check(lib().aq_vb_get_result(self.h, *[as_dp(out[k]) if k in out else nul for k in RESULT_KEYS]), "aq_vb_get_result")
         return out
 
-    def _result_vectors(self, full_output):
-        out = dict(theta_vb=np.zeros(self.p), zeta_vb=np.zeros(self.q))
-        if full_output:
-            out.update(lam2_inv_vb=np.zeros(self.p), sig2_theta_vb=np.zeros(self.p), tau_vb=np.zeros(self.q),
-                       sig2_beta_vb=np.zeros(self.q))
-        nul = C.cast(None, _lib.dp)
-        ptr = lambda k: as_dp(out[k]) if k in out else nul
-        check(lib().aq_vb_get_result(self.h, nul, nul, nul, ptr("theta_vb"), ptr("zeta_vb"), ptr("lam2_inv_vb"),
-                                     ptr("sig2_theta_vb"), ptr("tau_vb"), ptr("sig2_beta_vb")), "aq_vb_get_result")
-        return out
+
+RESULT_KEYS = ("beta_vb", "gam_vb", "mu_beta_vb", "theta_vb", "zeta_vb", "lam2_inv_vb", "sig2_theta_vb", "tau_vb",
+               "sig2_beta_vb")             # in the argument order of aq_vb_get_result
+
+
+def _result_buffers(p, q, full_output, dense=True):
+    """Zeroed output arrays by result key; a key that is absent is not asked for (NULL to the library): the p x q
+    matrices without dense, the variational parameters beyond the reference's return list without full_output."""
+    out = dict(beta_vb=np.zeros((p, q), order="F"), gam_vb=np.zeros((p, q), order="F")) if dense else {}
+    out.update(theta_vb=np.zeros(p), zeta_vb=np.zeros(q))
+    if full_output:
+        if dense:
+            out["mu_beta_vb"] = np.zeros((p, q), order="F")
+        out.update(lam2_inv_vb=np.zeros(p), sig2_theta_vb=np.zeros(p), tau_vb=np.zeros(q), sig2_beta_vb=np.zeros(q))
+    return out
 
 
 def vb_partition(q, n_parts):
@@ -600,10 +410,7 @@ def run_multi(Y, X, list_hyper, list_init, anneal, tol, maxit, n_gpus, devices=N
     pr, keep = _build_problem(Y, X, None, n, p, q, q, list_hyper, list_init, anneal, tol, maxit, thinned_elbo_eval, debug,
                               0, 1, 0, scheme, df)
     out = _lib.AqVbMultiOut()
-    res = dict(beta_vb=np.zeros((p, q), order="F"), gam_vb=np.zeros((p, q), order="F"), theta_vb=np.zeros(p), zeta_vb=np.zeros(q))
-    if full_output:
-        res.update(mu_beta_vb=np.zeros((p, q), order="F"), lam2_inv_vb=np.zeros(p), sig2_theta_vb=np.zeros(p), tau_vb=np.zeros(q),
-                   sig2_beta_vb=np.zeros(q))
+    res = _result_buffers(p, q, full_output)
     for k, v in res.items():
         setattr(out, k, as_dp(v))
     cap = 4096
@@ -631,194 +438,6 @@ def atlasqtl_global_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, verbose, li
                                        thinned_elbo_eval=thinned_elbo_eval, debug=debug, batch=batch, scheme="global", **kw)
 
 
-def assign_bFDR(mat_ppi, device=0):
-    """assign_bFDR of the reference (R/summarise_output.R:207-223) on the GPU: sort of all p q PPIs (hipCUB radix sort,
-    ties in original order), running mean of 1 - PPI, scattered back."""
-    m = np.asarray(mat_ppi, dtype=np.float64)
-    vec = np.ascontiguousarray(m.reshape(-1, order="F"))
-    out = np.empty_like(vec)
-    check(lib().aq_assign_bfdr(as_dp(vec), as_dp(out), vec.size, int(device)), "aq_assign_bfdr")
-    return out.reshape(m.shape, order="F")
-
-
-def hotspot_sizes(gam_vb, thres=0.5, fdr_adjust=False, device=0):
-    """rs_thres and nb_pairwise of summary.atlasqtl / plot.atlasqtl (R/summarise_output.R:98-105,177-182)."""
-    m = np.asfortranarray(gam_vb, dtype=np.float64)
-    p, q = m.shape
-    rs = np.zeros(p, dtype=np.int64)
-    tot = C.c_int64(0)
-    check(lib().aq_hotspot_sizes(as_dp(m), p, q, float(thres), int(bool(fdr_adjust)),
-                                 rs.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(tot), int(device)), "aq_hotspot_sizes")
-    return rs, int(tot.value)
-
-
-def _key_to_double(key):
-    """Inverse of the order-preserving key map of aq_summary.hip (negative: all bits flipped; otherwise: sign bit set)."""
-    import struct
-    bits = key ^ (1 << 63) if key >> 63 else ~key & ((1 << 64) - 1)
-    return struct.unpack("<d", struct.pack("<Q", bits))[0]
-
-
-def radix_select_(hist_fn, ranks, bits=_lib.AQ_RSEL_BITS):
-    """The digit loop of the radix select, for values held elsewhere (on the device, or spread over trait shards): the
-    ranks[i]-th smallest values (0-based, ranks ascending), as a list of floats.
-    hist_fn(prefixes, shift) -> n_prefix x 2^bits counts: for every prefix (sorted, distinct; a prefix is key >> (shift +
-    bits)), the histogram of the digit (key >> shift) & (2^bits - 1) among the values with that prefix; at the top digit
-    (shift + bits == 64) prefixes is [0] and all values count.  Per wanted rank the state is (prefix, rank left inside the
-    prefix); per digit the bin where the cumulative count first exceeds the rank left is appended to the prefix and the
-    count below it subtracted.  After the last digit the prefix is the key.  Counts are Python integers: no 2^32 limit."""
-    if 64 % bits:
-        raise ValueError("bits must divide 64")
-    ranks = [int(r) for r in ranks]
-    if any(r < 0 for r in ranks) or any(b < a for a, b in zip(ranks, ranks[1:])):
-        raise ValueError("ranks must be non-negative and ascending")
-    pre, rem = [0] * len(ranks), list(ranks)
-    for shift in range(64 - bits, -1, -bits):
-        prefixes = sorted(set(pre))
-        hist = np.asarray(hist_fn(prefixes, shift))
-        if hist.shape != (len(prefixes), 1 << bits):
-            raise ValueError(f"hist_fn must return {len(prefixes)} x {1 << bits} counts")
-        row = {pf: [int(c) for c in hist[i]] for i, pf in enumerate(prefixes)}
-        for i in range(len(ranks)):
-            below = 0
-            for d, c in enumerate(row[pre[i]]):
-                if below + c > rem[i]:
-                    break
-                below += c
-            else:
-                raise ValueError(f"rank {ranks[i]} is not below the number of values")
-            rem[i] -= below
-            pre[i] = (pre[i] << bits) | d
-    return [_key_to_double(k) for k in pre]
-
-
-_QUARTILES = (("q1", 0.25), ("median", 0.5), ("q3", 0.75))
-
-
-def quantile_ranks_(count):
-    """The order statistics (0-based ranks, sorted, distinct) that min, max and the type-7 quartiles of `count` values
-    need: {0, N - 1} and floor / ceil of (N - 1) {1/4, 1/2, 3/4}."""
-    N = int(count)
-    if N < 1:
-        raise ValueError("no value to summarise (all entries are NaN)")
-    want = {0, N - 1}
-    for _, prob in _QUARTILES:
-        index = (N - 1) * prob
-        want.update((int(np.floor(index)), int(np.ceil(index))))
-    return sorted(want)
-
-
-def six_numbers_(count, stat, total, n_nan=0):
-    """R's summary.default from order statistics: stat[rank] = the rank-th smallest of the `count` values, total their
-    sum.  Quartiles as stats::quantile.default, type 7 (third-party arithmetic restated): index = (N - 1) prob, lo = floor,
-    hi = ceil; x[lo], unless index > lo and x[hi] != x[lo]: then (1 - h) x[lo] + h x[hi] with h = index - lo."""
-    N = int(count)
-    out = {"min": float(stat[0])}
-    for name, prob in _QUARTILES:
-        index = (N - 1) * prob
-        lo, hi = int(np.floor(index)), int(np.ceil(index))
-        qs = float(stat[lo])
-        if index > lo and float(stat[hi]) != qs:
-            h = index - lo
-            qs = (1 - h) * qs + h * float(stat[hi])
-        out[name] = qs
-    out["mean"] = float(total) / N
-    out["max"] = float(stat[N - 1])
-    out.update(count=N, n_nan=int(n_nan))
-    return {k: out[k] for k in ("min", "q1", "median", "mean", "q3", "max", "count", "n_nan")}
-
-
-def six_numbers_host_(x):
-    """six_numbers_ of a short host vector (theta_vb, the hotspot sizes: p entries), NaN left out as R leaves out NA."""
-    import math
-    v = np.asarray(x, dtype=np.float64).reshape(-1)
-    nan = np.isnan(v)
-    s = np.sort(v[~nan])
-    return six_numbers_(s.size, {r: s[r] for r in quantile_ranks_(s.size)}, math.fsum(s), int(nan.sum()))
-
-
-def value_summary(x, device=0):
-    """Min., 1st Qu., Median, Mean, 3rd Qu., Max. (R's summary.default; plus count and n_nan) of the entries of a host
-    array of any shape -- summary(as.vector(x)) -- by the radix select on the GPU (aq_order_stats)."""
-    v = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
-    if v.size < 1:
-        raise ValueError("x has no entry")
-    # NaN is left out on the device; its count is not known beforehand, so the ranks are asked for once it is
-    n_nan = int(np.isnan(v).sum())
-    ranks = quantile_ranks_(v.size - n_nan)
-    r = np.asarray(ranks, dtype=np.int64)
-    out = np.zeros(r.size)
-    mom = _lib.AqMoments()
-    check(lib().aq_order_stats(as_dp(v), v.size, r.size, r.ctypes.data_as(C.POINTER(C.c_int64)), as_dp(out), C.byref(mom),
-                               int(device)), "aq_order_stats")
-    if mom.n_nan != n_nan:
-        raise _lib.AtlasqtlHipError(f"aq_order_stats counted {mom.n_nan} NaN, the host {n_nan}")
-    return six_numbers_(mom.count, dict(zip(ranks, out.tolist())), mom.sum, mom.n_nan)
-
-
-def merge_pair_tables(tables, p, max_pairs=None, n_pairs=None):
-    """One table from several (the trait shards' own): rows ordered by (-ppi, position j + p k of the whole matrix, i.e.
-    `trait` global) as order(as.vector(gam_vb), decreasing = TRUE) orders them, and fdr = cumsum(1 - ppi) / (1:N) along
-    it -- assign_bFDR (R/summarise_output.R:207-223) at those entries, because the union of the tables is a prefix of
-    that order.  n_pairs: the full count when the tables were already cut to max_pairs rows each."""
-    snp = np.concatenate([np.asarray(t["snp"], dtype=np.int32) for t in tables])
-    trait = np.concatenate([np.asarray(t["trait"], dtype=np.int32) for t in tables])
-    ppi = np.concatenate([np.asarray(t["ppi"], dtype=np.float64) for t in tables])
-    beta = np.concatenate([np.asarray(t["beta"], dtype=np.float64) for t in tables])
-    order = np.lexsort((snp.astype(np.int64) + int(p) * trait.astype(np.int64), -ppi))
-    snp, trait, ppi, beta = snp[order], trait[order], ppi[order], beta[order]
-    fdr = np.cumsum(1 - ppi) / np.arange(1, ppi.size + 1)
-    m = ppi.size if max_pairs is None else min(ppi.size, int(max_pairs))
-    return dict(snp=snp[:m], trait=trait[:m], ppi=ppi[:m], beta=beta[:m], fdr=fdr[:m],
-                n_pairs=int(ppi.size if n_pairs is None else n_pairs))
-
-
-def associations(gam_vb, beta_vb=None, thres=0.5, fdr_adjust=False, max_pairs=None, device=0):
-    """The table of VbRun.associations from host matrices (gam_vb, and beta_vb for the effect sizes; without it the table
-    has no `beta`): summary.atlasqtl's gam_vb > thres / assign_bFDR(gam_vb) < thres (R/summarise_output.R:99-106)."""
-    m = np.asfortranarray(gam_vb, dtype=np.float64)
-    p, q = m.shape
-    b = None
-    if beta_vb is not None:
-        b = np.asfortranarray(beta_vb, dtype=np.float64)
-        if b.shape != m.shape:
-            raise ValueError("beta_vb must have the shape of gam_vb")
-    if max_pairs is not None and int(max_pairs) < 0:
-        raise ValueError("max_pairs must be None or >= 0")
-    args = (as_dp(m), C.cast(None, _lib.dp) if b is None else as_dp(b), p, q, float(thres), int(bool(fdr_adjust)))
-    return _fetch_pairs(lambda cap, *out: lib().aq_select_pairs(*args, cap, *out, int(device)), "aq_select_pairs",
-                        b is not None, max_pairs)
-
-
-def _fetch_pairs(call, what, with_beta, max_pairs):
-    """Drive aq_select_pairs / aq_vb_select_pairs: call(cap, snp, trait, ppi, beta, fdr, n_pairs).  The count is not known
-    beforehand, so without max_pairs the first call offers room for 65 536 rows and only a longer table costs a second call."""
-    cap = (1 << 16) if max_pairs is None else int(max_pairs)
-    n = C.c_int64(0)
-    while True:
-        tab = dict(snp=np.zeros(cap, dtype=np.int32), trait=np.zeros(cap, dtype=np.int32), ppi=np.zeros(cap), fdr=np.zeros(cap))
-        if with_beta:
-            tab["beta"] = np.zeros(cap)
-        check(call(cap, as_ip(tab["snp"]), as_ip(tab["trait"]), as_dp(tab["ppi"]),
-                   as_dp(tab["beta"]) if with_beta else C.cast(None, _lib.dp), as_dp(tab["fdr"]), C.byref(n)), what)
-        if n.value <= cap or max_pairs is not None:
-            break
-        cap = int(n.value)
-    tab = {k: v[:min(cap, n.value)].copy() for k, v in tab.items()}
-    tab["n_pairs"] = int(n.value)
-    return tab
-
-
-SPARSE_OUTPUT_DEFAULTS = {"thres": 0.5, "fdr_adjust": False, "max_pairs": None, "summary": False}
-
-
-def sparse_output_options(sparse_output):
-    """The `sparse_output` argument of atlasqtl() / atlasqtl_global_local_core_ with its defaults filled in."""
-    if not isinstance(sparse_output, dict) or set(sparse_output) - set(SPARSE_OUTPUT_DEFAULTS):
-        raise ValueError("sparse_output must be None or a dict with keys among 'thres', 'fdr_adjust', 'max_pairs', "
-                         "'summary'")
-    return {**SPARSE_OUTPUT_DEFAULTS, **sparse_output}
-
 
 def _run_with_checkpoints(run, checkpoint_path, rate, maxit):
     """checkpoint_ / checkpoint_clean_up_ (R/utils.R:571-627, R/atlasqtl_global_local_core.R:379,388): every `rate`
@@ -831,8 +450,7 @@ def _run_with_checkpoints(run, checkpoint_path, rate, maxit):
     import os
     if not os.path.isdir(checkpoint_path):
         raise ValueError("The directory specified in checkpoint_path does not exist. ")       # R/prepare_atlasqtl.R:21-22
-    rank = 0 if run.pg is None else __import__("torch").distributed.get_rank(run.pg)
-    tag = "" if run.pg is None else f"_rank{rank}"
+    tag = "" if run.ranks is None else f"_rank{run.ranks.rank}"
     while True:
         st = run.status()
         if st["converged"] or st["it"] >= maxit:

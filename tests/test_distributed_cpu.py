@@ -2,43 +2,20 @@
 the ranks exchange exactly the payload the HIP path all-reduces (p + 3 doubles per sweep, 6 on ELBO
 sweeps) -- reproduces the unsharded run: same iteration count, same ELBO trace, same state."""
 import os
-import socket
-import sys
 
 import numpy as np
-import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+from tests.util import gloo_rank, make_problem, shard_lists, spawn_ranks
 
 
 def _worker(rank, world, port, outdir):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist = gloo_rank(rank, world, port)
     from oracle import sharded_oracle as S
-    from tests.util import make_problem
     prob = make_problem(100, 75, 20, p_act=10, prob_assoc=1.0)
     q = 20
     k0, k1 = (0, 16) if rank == 0 else (16, 20)       # shards are whole 16-trait tiles, as in bench.py
-    lh, li = dict(prob["list_hyper"]), dict(prob["list_init"])
-    for k in ("eta", "kappa", "n0"):
-        lh[k] = np.asarray(lh[k])[k0:k1]
-    for k in ("sig2_beta_vb", "tau_vb", "zeta_vb"):
-        li[k] = np.asarray(li[k])[k0:k1]
-    for k in ("gam_vb", "mu_beta_vb"):
-        li[k] = np.asarray(li[k])[:, k0:k1]
+    lh, li = shard_lists(prob["list_hyper"], prob["list_init"], k0, k1)
     calls = []
 
     def allreduce(v):
@@ -56,9 +33,7 @@ def _worker(rank, world, port, outdir):
 
 def test_q_sharded_protocol_two_ranks(tmp_path):
     from oracle import atlasqtl_oracle as O
-    from tests.util import make_problem
-    port = _free_port()
-    mp.spawn(_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    spawn_ranks(_worker, 2, str(tmp_path))
     prob = make_problem(100, 75, 20, p_act=10, prob_assoc=1.0)
     tr = []
     ref = O.atlasqtl_global_local_core_(prob["Y"], prob["X"], 20, (1, 2, 10), 1, 0.1, 1000, prob["list_hyper"],

@@ -242,21 +242,12 @@ def test_device_generated_init_does_not_depend_on_sharding():
 
 def _sharded_device_init_worker(rank, world, port, outdir):
     import os
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from tests.util import gloo_rank, make_problem, shard_lists
+    dist = gloo_rank(rank, world, port)
     import atlasqtl_amd as A
-    from tests.util import make_problem
     prob = make_problem(200, 130, 49, p_act=10, prob_assoc=0.3)
     k0, k1 = (0, 32) if rank == 0 else (32, 49)
-    lh, li = dict(prob["list_hyper"]), _device_init_list(prob)
-    for k in ("eta", "kappa", "n0"):
-        lh[k] = np.asarray(lh[k])[k0:k1]
-    for k in ("sig2_beta_vb", "tau_vb", "zeta_vb"):
-        li[k] = np.asarray(li[k])[k0:k1]
+    lh, li = shard_lists(prob["list_hyper"], _device_init_list(prob), k0, k1)
     args = (prob["Y"][:, k0:k1], prob["X"], 49, (1, 2, 10), 1, 0.1, 1000, 0, lh, li)
     if rank == 0:   # without the offset the shards would silently all start from the draws of traits 0..q_local-1
         with pytest.raises(ValueError, match="trait_offset is required"):
@@ -270,12 +261,9 @@ def test_sharded_core_function_with_device_init_reproduces_single_gpu(tmp_path):
     """atlasqtl_global_local_core_(process_group=..., trait_offset=...) with device-drawn initial values: two trait shards
     (two processes on the one GPU, gloo-staged payloads) reproduce the single-process run -- the Philox counters are
     (SNP, GLOBAL trait)."""
-    import socket
-    import torch.multiprocessing as mp
     import atlasqtl_amd as A
-    from tests.util import make_problem
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    mp.spawn(_sharded_device_init_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    from tests.util import make_problem, spawn_ranks
+    spawn_ranks(_sharded_device_init_worker, 2, str(tmp_path))
     prob = make_problem(200, 130, 49, p_act=10, prob_assoc=0.3)
     one = A.atlasqtl_global_local_core_(prob["Y"], prob["X"], 49, (1, 2, 10), 1, 0.1, 1000, 0, prob["list_hyper"],
                                         _device_init_list(prob), full_output=True, debug=True)

@@ -144,24 +144,15 @@ def test_count_only_call_of_the_c_entry_agrees():
 
 def _assoc_shard_worker(rank, world, port, outdir, ties):
     import os
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from tests.util import gloo_rank, shard_lists
+    dist = gloo_rank(rank, world, port)
     from atlasqtl_amd.core import VbRun
     from tests.test_gpu_postproc import _fdr_problem
     prob, gam, cuts = _fdr_problem(ties)
     q = gam.shape[1]
     k0, k1 = cuts[rank], cuts[rank + 1]
-    lh, li = dict(prob["list_hyper"]), dict(prob["list_init"])
-    for k in ("eta", "kappa", "n0"):
-        lh[k] = np.asarray(lh[k])[k0:k1]
-    for k in ("sig2_beta_vb", "tau_vb", "zeta_vb"):
-        li[k] = np.asarray(li[k])[k0:k1]
+    lh, li = shard_lists(prob["list_hyper"], prob["list_init"], k0, k1)
     li["gam_vb"] = np.asfortranarray(gam[:, k0:k1])
-    li["mu_beta_vb"] = np.asfortranarray(np.asarray(li["mu_beta_vb"])[:, k0:k1])
     run = VbRun(prob["Y"][:, k0:k1], prob["X"], lh, li, None, 0.1, 5, True, False, q_total=q, process_group=dist.group.WORLD,
                 trait_offset=k0)
     run.run_sweeps(0)                       # the PPIs resident on the device are the crafted initial values
@@ -180,11 +171,9 @@ def _assoc_shard_worker(rank, world, port, outdir, ties):
 def test_three_trait_shards_return_the_table_of_the_whole_matrix(ties, tmp_path):
     """Every rank returns the same whole-problem table: global trait indices, beta = the crafted gam_vb times the initial
     mu_beta_vb bit for bit (no sweep has run)."""
-    import socket
-    import torch.multiprocessing as mp
     from tests.test_gpu_postproc import _fdr_problem
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    mp.spawn(_assoc_shard_worker, args=(3, port, str(tmp_path), ties), nprocs=3, join=True)
+    from tests.util import spawn_ranks
+    spawn_ranks(_assoc_shard_worker, 3, str(tmp_path), ties)
     prob, gam, _ = _fdr_problem(ties)
     beta = gam * np.asarray(prob["list_init"]["mu_beta_vb"])
     _assert_fdr_margin(gam, TIE_FDR_THRES)

@@ -87,12 +87,8 @@ def test_c5_shaped_slice_two_kernels_agree(monkeypatch):
 
 def _shard_worker(rank, world, port, outdir, n, p, q, sweeps):
     import os
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from tests.util import gloo_rank
+    dist = gloo_rank(rank, world, port)
     import bench
     from atlasqtl_amd.core import VbRun
     tiles = (q + 15) // 16
@@ -110,11 +106,9 @@ def _shard_worker(rank, world, port, outdir, n, p, q, sweeps):
 def test_c2_two_trait_shards_reproduce_the_single_shard_elbo(tmp_path):
     """The q-sharded protocol at C2 size (two processes share the one GPU, payloads reduced through gloo on the host): same
     ELBO trace as the unsharded run -- the all-reduced sums are added in a different order, nothing else differs."""
-    import socket
-    import torch.multiprocessing as mp
+    from tests.util import spawn_ranks
     n, p, q, sweeps = 1000, 5000, 1000, 16
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    mp.spawn(_shard_worker, args=(2, port, str(tmp_path), n, p, q, sweeps), nprocs=2, join=True)
+    spawn_ranks(_shard_worker, 2, str(tmp_path), n, p, q, sweeps)
     X, Y, lh, li = _bench_problem(n, p, q)
     st, (its, lbs), _, _ = _run(X, Y, lh, li, q, sweeps)
     r0, r1 = np.load(tmp_path / "rank0.npz"), np.load(tmp_path / "rank1.npz")

@@ -2,34 +2,21 @@
 traits, the all-reduce payloads travel through gloo (CPU-staged; RCCL needs one GPU per rank) --
 against the single-process HIP run and the golden fixture."""
 import os
-import socket
-import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _worker(rank, world, port, outdir):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from tests.util import gloo_rank, make_problem, shard_lists
+    dist = gloo_rank(rank, world, port)
     import atlasqtl_amd as A
-    from tests.util import make_problem
     prob = make_problem(200, 130, 49, p_act=10, prob_assoc=0.3)
     q = 49
     k0, k1 = (0, 32) if rank == 0 else (32, 49)
-    lh, li = dict(prob["list_hyper"]), dict(prob["list_init"])
-    for k in ("eta", "kappa", "n0"):
-        lh[k] = np.asarray(lh[k])[k0:k1]
-    for k in ("sig2_beta_vb", "tau_vb", "zeta_vb"):
-        li[k] = np.asarray(li[k])[k0:k1]
-    for k in ("gam_vb", "mu_beta_vb"):
-        li[k] = np.asarray(li[k])[:, k0:k1]
+    lh, li = shard_lists(prob["list_hyper"], prob["list_init"], k0, k1)
     out = A.atlasqtl_global_local_core_(prob["Y"][:, k0:k1], prob["X"], q, (1, 2, 10), 1, 0.1, 1000, 0, lh, li,
                                         full_output=True, debug=True, process_group=dist.group.WORLD)
     np.savez(os.path.join(outdir, f"rank{rank}.npz"), it=out["it"], lb=out["elbo_trace"][1], gam=out["gam_vb"],
@@ -43,13 +30,11 @@ def test_two_ranks_one_gpu_match_single_process(env, tmp_path, monkeypatch):
     another -- chained SNP segments, sample split with either exchange wave: the hand-offs assume that a workgroup's
     predecessor / partners are resident or dispatched next; a violation would surface as
     AQ_ERR_DEVICE from the bounded waits, never as a hang."""
-    import torch.multiprocessing as mp
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     import atlasqtl_amd as A
-    from tests.util import make_problem
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    mp.spawn(_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    from tests.util import make_problem, spawn_ranks
+    spawn_ranks(_worker, 2, str(tmp_path))
     prob = make_problem(200, 130, 49, p_act=10, prob_assoc=0.3)
     one = A.atlasqtl_global_local_core_(prob["Y"], prob["X"], 49, (1, 2, 10), 1, 0.1, 1000, 0, prob["list_hyper"],
                                         prob["list_init"], full_output=True, debug=True)

@@ -220,24 +220,15 @@ def test_five_million_values_over_65_tiles():
 # ---- 8. three trait shards ---------------------------------------------------------------------------------------------
 def _summary_shard_worker(rank, world, port, outdir, ties):
     import os
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from tests.util import gloo_rank, shard_lists
+    dist = gloo_rank(rank, world, port)
     from atlasqtl_amd.core import VbRun
     from tests.test_gpu_postproc import _fdr_problem
     prob, gam, cuts = _fdr_problem(ties)
     q = gam.shape[1]
     k0, k1 = cuts[rank], cuts[rank + 1]
-    lh, li = dict(prob["list_hyper"]), dict(prob["list_init"])
-    for k in ("eta", "kappa", "n0"):
-        lh[k] = np.asarray(lh[k])[k0:k1]
-    for k in ("sig2_beta_vb", "tau_vb", "zeta_vb"):
-        li[k] = np.asarray(li[k])[k0:k1]
+    lh, li = shard_lists(prob["list_hyper"], prob["list_init"], k0, k1)
     li["gam_vb"] = np.asfortranarray(gam[:, k0:k1])
-    li["mu_beta_vb"] = np.asfortranarray(np.asarray(li["mu_beta_vb"])[:, k0:k1])
     run = VbRun(prob["Y"][:, k0:k1], prob["X"], lh, li, None, 0.1, 5, True, False, q_total=q, process_group=dist.group.WORLD,
                 trait_offset=k0)
     run.run_sweeps(0)                       # the values resident on the device are the crafted initial values
@@ -255,11 +246,9 @@ def _summary_shard_worker(rank, world, port, outdir, ties):
 def test_three_trait_shards_return_the_numbers_of_the_whole_matrix(ties, tmp_path):
     """Three processes on the one GPU over gloo, trait cuts [0, 16, 32, 50]: the shards' digit histograms add, so every
     rank's six numbers are those of the whole p x q matrix, and the ranks agree bit for bit."""
-    import socket
-    import torch.multiprocessing as mp
     from tests.test_gpu_postproc import _fdr_problem
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    mp.spawn(_summary_shard_worker, args=(3, port, str(tmp_path), ties), nprocs=3, join=True)
+    from tests.util import spawn_ranks
+    spawn_ranks(_summary_shard_worker, 3, str(tmp_path), ties)
     prob, gam, _ = _fdr_problem(ties)
     beta = gam * np.asarray(prob["list_init"]["mu_beta_vb"])
     res = [np.load(tmp_path / f"rank{r}.npz") for r in range(3)]

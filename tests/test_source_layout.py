@@ -1,5 +1,6 @@
-"""The source layout of atlasqtl_amd/csrc: one owner of device memory, one definition per exported symbol, and no
-hand-copied prototypes between translation units (they live in headers, where a mismatch is a compile error)."""
+"""The source layout of atlasqtl_amd/csrc -- one owner of device memory, one definition per exported symbol, and no
+hand-copied prototypes between translation units (they live in headers, where a mismatch is a compile error) -- and of
+the Python package around it: one owner of the rank collectives."""
 import os
 import re
 
@@ -68,3 +69,20 @@ def test_no_unit_declares_what_another_unit_defines():
         for name, is_def, _ in decls:
             if not is_def:
                 assert not (definer.get(name, set()) - {fn}), (fn, name, "is defined in", definer[name])
+
+
+def test_the_rank_collectives_have_one_owner():
+    """Among atlasqtl_amd/*.py only ranks.py names torch.distributed, and only ranks.py and _lib.py (the load order of the
+    two HIP runtimes) import torch: everything else reaches the ranks through ranks.RankGroup."""
+    pkg = os.path.join(ROOT, "atlasqtl_amd")
+    naming, importing = set(), set()
+    for fn in sorted(os.listdir(pkg)):
+        if fn.endswith(".py"):
+            with open(os.path.join(pkg, fn)) as f:
+                src = f.read()
+            if "torch.distributed" in src:
+                naming.add(fn)
+            if re.search(r"\bimport\s+torch\b|\bfrom\s+torch\b|__import__\(\s*[\"']torch", src):
+                importing.add(fn)
+    assert naming == {"ranks.py"}
+    assert importing == {"ranks.py", "_lib.py"}

@@ -6,6 +6,47 @@ from atlasqtl_amd import synth
 from oracle import prepare_oracle
 
 
+def shard_lists(list_hyper, list_init, k0, k1):
+    """Copies of the two argument lists for the trait shard [k0, k1): the q-indexed vectors and the columns of the two
+    p x q initial matrices (left alone when they are None: drawn on the device)."""
+    lh, li = dict(list_hyper), dict(list_init)
+    for k in ("eta", "kappa", "n0"):
+        lh[k] = np.asarray(lh[k])[k0:k1]
+    for k in ("sig2_beta_vb", "tau_vb", "zeta_vb"):
+        li[k] = np.asarray(li[k])[k0:k1]
+    for k in ("gam_vb", "mu_beta_vb"):
+        if li.get(k) is not None:
+            li[k] = np.asarray(li[k])[:, k0:k1]
+    return lh, li
+
+
+def gloo_rank(rank, world, port):
+    """The prologue of a spawned worker: the repository on sys.path and this process in a gloo group of `world` ranks.
+    Returns torch.distributed (the worker ends with its destroy_process_group())."""
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    import torch.distributed as dist
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    return dist
+
+
+def spawn_ranks(worker, world, *args):
+    """Run worker(rank, world, port, *args) in `world` processes (worker: a module-level function, spawn pickles it by
+    name) on a free local port, and wait for them."""
+    import socket
+    import torch.multiprocessing as mp
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    mp.spawn(worker, args=(world, port) + args, nprocs=world, join=True)
+
+
 def make_problem(n, p, q, p_act=10, seed=123, init_seed=456, maf=0.2, p0=(5, 25), prob_assoc=0.2, na_frac=0.0,
                  q_act=None):
     """Synthetic data in the shape of the reference's example generator, pre-processed by the
