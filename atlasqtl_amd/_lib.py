@@ -49,6 +49,10 @@ class AqPrepBedInput(C.Structure):
                 ("sample_idx", ip), ("Y", dp), ("count_a2", C.c_int32), ("missing", C.c_int32), ("device", C.c_int32)]
 
 
+class AqPrepCov(C.Structure):
+    _fields_ = [("d", C.c_int32), ("Z", dp)]
+
+
 class AqVbMultiOut(C.Structure):
     _fields_ = [
         ("beta_vb", dp), ("gam_vb", dp), ("mu_beta_vb", dp), ("theta_vb", dp), ("zeta_vb", dp), ("lam2_inv_vb", dp),
@@ -137,6 +141,10 @@ SYMBOLS = {
     "aq_debug_live_device_bytes": (C.c_int64, []),
     "aq_prepare_data_bed": (C.c_int, [C.POINTER(AqPrepBedInput), C.POINTER(C.c_void_p)]),
     "aq_prep_genotype_counts": (C.c_int, [C.c_void_p, ip]),
+    "aq_prepare_data_cov": (C.c_int, [C.POINTER(AqPrepInput), C.POINTER(AqPrepCov), C.POINTER(C.c_void_p)]),
+    "aq_prepare_data_bed_cov": (C.c_int, [C.POINTER(AqPrepBedInput), C.POINTER(AqPrepCov), C.POINTER(C.c_void_p)]),
+    "aq_prep_cov_info": (C.c_int, [C.c_void_p, ip, C.POINTER(C.c_uint8), dp]),
+    "aq_cov_basis": (C.c_int, [dp, C.c_int32, C.c_int32, dp, ip]),
 }
 
 _lib = None

@@ -64,7 +64,7 @@ def add_collinear_back_pairs_(assoc, rs_thres, theta_vb, initial_colnames_X, rmv
 def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, verbose=1, list_hyper=None,
              list_init=None, save_hyper=False, save_init=False, full_output=False, thinned_elbo_eval=True,
              checkpoint_path=None, trace_path=None, add_collinear_back=False, device=0, device_init=False,
-             sparse_output=None):
+             sparse_output=None, covariates=None):
     """R/atlasqtl.R:179-322.
 
     X: a float64 matrix, int8 dosages, or a plink.PlinkBed (a PLINK 1 .bed / .bim / .fam fileset, unpacked on the GPU): the
@@ -76,7 +76,14 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
     table of pairs with gam_vb > thres (or assign_bFDR(gam_vb) < thres) with snp / trait indices and names, ppi, beta and
     fdr; `rs_thres` and `nb_pairwise` -- so that the matrices never leave the GPU.  With "summary": True also
     `value_summary`, the quartiles and means of all p q PPIs and effect sizes that summary() prints (computed on the GPU,
-    core.VbRun.value_summary).  None: the dense result."""
+    core.VbRun.value_summary).  None: the dense result.
+
+    covariates: an n x d matrix (age, sex, genotype PCs, batch factors ...; 1 <= d <= 96, finite, rows as in Y) that is
+    regressed, with an intercept, out of every predictor and every response on the GPU before the fit (prepare_on_device);
+    the fit is the fit to those residuals.  The result then carries `n_covariates`, `rmvd_cov_x` (names of the predictors
+    that the covariates explain entirely, or None; they are among `rmvd_cst_x`) and `cov_r2_x` (per predictor given, the
+    share of its variance that the covariates explain).  For a response with missing values the predictors are adjusted
+    over all samples, not over its observed ones, and the model is not told about the d + 1 degrees of freedom removed."""
     sparse = None if sparse_output is None else sparse_output_options(sparse_output)
     if sparse is not None and add_collinear_back and sparse["fdr_adjust"]:
         raise ValueError("add_collinear_back=True cannot be combined with sparse_output in FDR mode: the re-inserted copies "
@@ -88,7 +95,7 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
                          "cannot reproduce.  Use the dense output.")
     check_verbose_(verbose)
     check_annealing_(anneal)
-    dat = prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path)
+    dat = prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path, covariates=covariates)
     bool_rmvd_x = dat["bool_rmvd_x"]
     Xs, Yc = dat["X"], dat["Y"]
     n, p = Xs.shape
@@ -119,6 +126,8 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
     res["names_x"], res["names_y"] = dat["names_x"], dat["names_y"]
     if dat["genotype_counts"] is not None:                # X = PlinkBed: 4 x p (hom A1, het, hom A2, missing), before removals
         res["genotype_counts"] = dat["genotype_counts"]
+    if covariates is not None:
+        res["n_covariates"], res["rmvd_cov_x"], res["cov_r2_x"] = dat["n_covariates"], dat["rmvd_cov_x"], dat["cov_r2_x"]
     names_snp = dat["names_x"]
     if sparse is not None:
         if sparse["summary"]:

@@ -11,6 +11,8 @@
 // quarter of the int8 bytes) and one decode pass unpacks them into the int8 buffer that the same pipeline then reads.
 // All of it is HBM-bound streaming: one read of X for the column statistics, one read + one write for the standardised
 // matrix with its column hashes, one gather pass for the compaction.
+// aq_prepare_data_cov / aq_prepare_data_bed_cov regress covariates out of X and Y first (aq_cov_kernels.h): the residuals of
+// X are formed as fp64 on the device, enter the fp64 pipeline unchanged and are freed once the compact matrix is written.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <memory>
@@ -18,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 #include "aq_internal.h"   // aq_fail, AQ_HIP, aq_need_device, AqDev
@@ -30,6 +33,9 @@ struct aq_prep {
   std::vector<int32_t> dup_of;                // original index of the kept column a removed duplicate equals, else -1
   std::vector<double> mean, sd;               // p each
   std::vector<int32_t> gcounts;               // 4 x p (hom A1, het, hom A2, missing): aq_prepare_data_bed only
+  int n_cov = 0;                              // covariates regressed out of X and Y (0: none)
+  std::vector<uint8_t> cov_absorbed;          // p: the covariates explain the column (written as 0.0, reported constant)
+  std::vector<double> cov_r2;                 // p: share of the column's variance that the covariates explain
 };
 
 template <typename T>
@@ -48,6 +54,8 @@ __device__ __forceinline__ double aq_block_sum(double v, double *sh) {
   __syncthreads();
   return r;
 }
+
+#include "aq_cov_kernels.h"   // aq_k_cov_residualise, aq_k_cov_residualise_y
 
 // one workgroup per column: mean (sum / n, then one refinement pass as R's long-double colMeans would give), the n - 1
 // standard deviation of the centred values, and whether the column is constant
@@ -267,6 +275,101 @@ static int aq_prepare_x(aq_prep *h, const T *X_host) {
   return aq_prepare_x_device<T>(h, dX.get());
 }
 
+// ---- covariates: the basis on the host, the two residual passes on the device ----
+static int aq_cov_check_dims(int n, int d) {
+  if (d < 1 || d > AQ_COV_MAX_D)
+    return aq_fail(AQ_ERR_ARG, "covariates: between 1 and " + std::to_string(AQ_COV_MAX_D) + " columns are supported, " +
+                                   std::to_string(d) + " given");
+  if (n < 2 || d + 1 >= n)
+    return aq_fail(AQ_ERR_ARG, "covariates: " + std::to_string(d) + " columns and the intercept need more than " +
+                                   std::to_string(d + 1) + " samples, n = " + std::to_string(n));
+  return AQ_OK;
+}
+
+// Q (n x D column-major, D = d + 1): an orthonormal basis of [1, Z], columns in order, by modified Gram-Schmidt applied twice
+// with long double dot products.  Covariate l is collinear when what is left of it after the intercept and the covariates
+// before it has a squared norm <= AQ_COV_TOL times its own.
+extern "C" int aq_cov_basis(const double *Z, int32_t n, int32_t d, double *Q, int32_t *bad_col) {
+  if (bad_col) *bad_col = -1;
+  if (!Z || !Q) return aq_fail(AQ_ERR_ARG, "aq_cov_basis: NULL argument");
+  AQ_TRY(aq_cov_check_dims(n, d));
+  const size_t nd = (size_t)n * d;
+  for (size_t i = 0; i < nd; i++)
+    if (!std::isfinite(Z[i])) return aq_fail(AQ_ERR_ARG, "covariates must be a numeric matrix, finite without missing value.");
+  const double q0 = 1.0 / std::sqrt((double)n);
+  for (int i = 0; i < n; i++) Q[i] = q0;
+  for (int l = 1; l <= d; l++) {
+    double *v = Q + (size_t)l * n;
+    const double *z = Z + (size_t)(l - 1) * n;
+    long double own = 0.0L;
+    for (int i = 0; i < n; i++) { v[i] = z[i]; own += (long double)z[i] * z[i]; }
+    for (int pass = 0; pass < 2; pass++)
+      for (int k = 0; k < l; k++) {
+        const double *qk = Q + (size_t)k * n;
+        long double dot = 0.0L;
+        for (int i = 0; i < n; i++) dot += (long double)qk[i] * v[i];
+        const double c = (double)dot;
+        for (int i = 0; i < n; i++) v[i] -= qk[i] * c;
+      }
+    long double rem = 0.0L;
+    for (int i = 0; i < n; i++) rem += (long double)v[i] * v[i];
+    if (!(rem > (long double)AQ_COV_TOL * own)) {
+      if (bad_col) *bad_col = l - 1;
+      return aq_fail(AQ_ERR_ARG, "column " + std::to_string(l) + " of the covariates is collinear with the intercept and the "
+                                     "columns before it (a constant column is collinear with the intercept)");
+    }
+    const double nrm = (double)sqrtl(rem);
+    for (int i = 0; i < n; i++) v[i] /= nrm;
+  }
+  return AQ_OK;
+}
+
+// the checks of a covariate argument and its basis, all on the host: Q is n x (d + 1) afterwards
+static int aq_cov_host_basis(const aq_prep_cov *cov, int n, const char *who, std::vector<double> *Q) {
+  if (!cov->Z) return aq_fail(AQ_ERR_ARG, std::string(who) + ": NULL covariate pointer");
+  AQ_TRY(aq_cov_check_dims(n, cov->d));
+  Q->resize((size_t)n * (cov->d + 1));
+  return aq_cov_basis(cov->Z, n, cov->d, Q->data(), nullptr);
+}
+
+// x_j <- x_j - Q (Q' x_j) for every column of the device matrix dX into dXr (dX itself for T = double)
+template <typename T>
+static int aq_cov_residualise_x(aq_prep *h, const T *dX, double *dXr, const double *dQt, int D) {
+  const int n = h->n, p = h->p;
+  AqDev<uint8_t> dabs;
+  AqDev<double> dr2;
+  AQ_TRY(dabs.alloc((size_t)p));
+  AQ_TRY(dr2.alloc((size_t)p));
+  hipLaunchKernelGGL((aq_k_cov_residualise<T>), dim3(p), dim3(256), 0, 0, dX, n, D, dQt, dXr, dabs.get(), dr2.get());
+  AQ_HIP(hipGetLastError());
+  h->n_cov = D - 1;
+  h->cov_absorbed.resize(p);
+  h->cov_r2.resize(p);
+  AQ_HIP(hipMemcpy(h->cov_absorbed.data(), dabs.get(), (size_t)p, hipMemcpyDeviceToHost));
+  AQ_HIP(hipMemcpy(h->cov_r2.data(), dr2.get(), (size_t)p * sizeof(double), hipMemcpyDeviceToHost));
+  return AQ_OK;
+}
+
+// host matrix -> device, residuals on the covariates as fp64, then the fp64 pipeline on them
+template <typename T>
+static int aq_prepare_x_cov(aq_prep *h, const T *X_host, const double *dQt, int D) {
+  const size_t np = (size_t)h->n * h->p;
+  AqDev<T> dX;
+  AqDev<double> dXr;
+  AQ_TRY(dX.alloc(np));
+  AQ_HIP(hipMemcpy(dX.get(), X_host, np * sizeof(T), hipMemcpyHostToDevice));
+  double *xr;
+  if constexpr (std::is_same<T, double>::value) {
+    xr = dX.get();
+  } else {
+    AQ_TRY(dXr.alloc(np));
+    xr = dXr.get();
+  }
+  AQ_TRY(aq_cov_residualise_x<T>(h, dX.get(), xr, dQt, D));
+  if constexpr (!std::is_same<T, double>::value) dX.reset();
+  return aq_prepare_x_device<double>(h, xr);
+}
+
 extern "C" void aq_prep_destroy(aq_prep_handle h) {
   if (!h) return;
   hipSetDevice(h->device);
@@ -274,18 +377,29 @@ extern "C" void aq_prep_destroy(aq_prep_handle h) {
 }
 
 // Y <- scale(Y, center = TRUE, scale = FALSE) into h->Yc and the two missingness guards (R/prepare_atlasqtl.R:39-45, :83)
-static int aq_prepare_y(aq_prep *h, const double *Y_host) {
+// With covariates (dQt: their basis [D][n] on the device) the residuals on [1, Z] over each column's observed rows take the
+// place of the centring, and a column on whose observed rows the covariates are collinear is an error after the two guards.
+static int aq_prepare_y(aq_prep *h, const double *Y_host, const double *dQt = nullptr, int D = 0) {
   const int n = h->n, q = h->q;
   const size_t nq = (size_t)n * q;
   AqDev<double> dY;
-  AqDev<int> dnobs;
-  std::vector<int> nobs(q);
+  AqDev<int> dnobs, dflag;
+  std::vector<int> nobs(q), flag;
   AQ_TRY(dY.alloc(nq));
   AQ_TRY(h->Yc.alloc(nq));
   AQ_TRY(dnobs.alloc((size_t)q));
   AQ_HIP(hipMemcpy(dY.get(), Y_host, nq * sizeof(double), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(aq_k_centre_y, dim3(q), dim3(256), 0, 0, dY.get(), n, h->Yc.get(), dnobs.get());
-  AQ_HIP(hipGetLastError());
+  if (dQt) {
+    AQ_TRY(dflag.alloc_zeroed((size_t)q));
+    hipLaunchKernelGGL(aq_k_cov_residualise_y, dim3(q), dim3(256), aq_cov_y_lds_bytes(D), 0, dY.get(), n, D, dQt, h->Yc.get(), dnobs.get(),
+                       dflag.get());
+    AQ_HIP(hipGetLastError());
+    flag.resize(q);
+    AQ_HIP(hipMemcpy(flag.data(), dflag.get(), flag.size() * sizeof(int), hipMemcpyDeviceToHost));
+  } else {
+    hipLaunchKernelGGL(aq_k_centre_y, dim3(q), dim3(256), 0, 0, dY.get(), n, h->Yc.get(), dnobs.get());
+    AQ_HIP(hipGetLastError());
+  }
   AQ_HIP(hipMemcpy(nobs.data(), dnobs.get(), nobs.size() * sizeof(int), hipMemcpyDeviceToHost));
   {
     long long tot = 0;
@@ -298,14 +412,22 @@ static int aq_prepare_y(aq_prep *h, const double *Y_host) {
     if (!low.empty())
       return aq_fail(AQ_ERR_ARG, "Column(s) " + low + " of matrix Y have more than 97.5% missing values, and should be removed. Exit.");
   }
+  for (size_t k = 0; k < flag.size(); k++)
+    if (flag[k])
+      return aq_fail(AQ_ERR_ARG, "covariates are collinear on the samples observed for column " + std::to_string(k + 1) + " of Y (" +
+                                     std::to_string(nobs[k]) + " observed, " + std::to_string(D - 1) + " covariates and the intercept)");
   return AQ_OK;
 }
 
-extern "C" int aq_prepare_data(const aq_prep_input *in, aq_prep_handle *out) {
-  if (!in || !out) return aq_fail(AQ_ERR_ARG, "aq_prepare_data: NULL argument");
+// cov == NULL or cov->d == 0: no covariates, the path of aq_prepare_data
+static int aq_prepare_data_impl(const aq_prep_input *in, const aq_prep_cov *cov, aq_prep_handle *out, const std::string &who) {
+  if (!in || !out) return aq_fail(AQ_ERR_ARG, who + ": NULL argument");
   *out = nullptr;
-  if (in->n < 2 || in->p < 1 || in->q < 1) return aq_fail(AQ_ERR_ARG, "aq_prepare_data: n >= 2, p >= 1, q >= 1 required");
-  if ((!in->X && !in->X_i8) || !in->Y) return aq_fail(AQ_ERR_ARG, "aq_prepare_data: NULL data pointer");
+  if (in->n < 2 || in->p < 1 || in->q < 1) return aq_fail(AQ_ERR_ARG, who + ": n >= 2, p >= 1, q >= 1 required");
+  if ((!in->X && !in->X_i8) || !in->Y) return aq_fail(AQ_ERR_ARG, who + ": NULL data pointer");
+  const bool with_cov = cov && cov->d != 0;
+  std::vector<double> Q;
+  if (with_cov) AQ_TRY(aq_cov_host_basis(cov, in->n, who.c_str(), &Q));
   AQ_TRY(aq_need_device(in->device));
   const size_t np = (size_t)in->n * in->p;
   if (in->X)
@@ -313,10 +435,27 @@ extern "C" int aq_prepare_data(const aq_prep_input *in, aq_prep_handle *out) {
       if (!std::isfinite(in->X[i])) return aq_fail(AQ_ERR_ARG, "X must be a non-empty a numeric matrix, finite without missing value.");
   std::unique_ptr<aq_prep> h(new aq_prep());
   h->n = in->n; h->p = in->p; h->q = in->q; h->device = in->device;
-  AQ_TRY(in->X ? aq_prepare_x<double>(h.get(), in->X) : aq_prepare_x<int8_t>(h.get(), in->X_i8));
-  AQ_TRY(aq_prepare_y(h.get(), in->Y));
+  if (with_cov) {
+    const int D = cov->d + 1;
+    AqDev<double> dQt;   // n x D column-major = [D][n]
+    AQ_TRY(dQt.alloc(Q.size()));
+    AQ_HIP(hipMemcpy(dQt.get(), Q.data(), Q.size() * sizeof(double), hipMemcpyHostToDevice));
+    AQ_TRY(in->X ? aq_prepare_x_cov<double>(h.get(), in->X, dQt.get(), D) : aq_prepare_x_cov<int8_t>(h.get(), in->X_i8, dQt.get(), D));
+    AQ_TRY(aq_prepare_y(h.get(), in->Y, dQt.get(), D));
+  } else {
+    AQ_TRY(in->X ? aq_prepare_x<double>(h.get(), in->X) : aq_prepare_x<int8_t>(h.get(), in->X_i8));
+    AQ_TRY(aq_prepare_y(h.get(), in->Y));
+  }
   *out = h.release();
   return AQ_OK;
+}
+
+extern "C" int aq_prepare_data(const aq_prep_input *in, aq_prep_handle *out) {
+  return aq_prepare_data_impl(in, nullptr, out, "aq_prepare_data");
+}
+
+extern "C" int aq_prepare_data_cov(const aq_prep_input *in, const aq_prep_cov *cov, aq_prep_handle *out) {
+  return aq_prepare_data_impl(in, cov, out, cov && cov->d != 0 ? "aq_prepare_data_cov" : "aq_prepare_data");
 }
 
 // ---- PLINK 1 .bed input: 2 bits per genotype, unpacked on the device (include/atlasqtl_hip.h, aq_prepare_data_bed) ----
@@ -453,7 +592,7 @@ static int aq_bed_decode(aq_prep *h, const aq_prep_bed_input *in, AqDev<int8_t> 
   return AQ_OK;
 }
 
-extern "C" int aq_prepare_data_bed(const aq_prep_bed_input *in, aq_prep_handle *out) {
+static int aq_prepare_data_bed_impl(const aq_prep_bed_input *in, const aq_prep_cov *cov, aq_prep_handle *out) {
   if (!in || !out) return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: NULL argument");
   *out = nullptr;
   if (in->n < 2 || in->p < 1 || in->q < 1) return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: n >= 2, p >= 1, q >= 1 required");
@@ -471,18 +610,31 @@ extern "C" int aq_prepare_data_bed(const aq_prep_bed_input *in, aq_prep_handle *
                                            std::to_string(in->sample_idx[i]) + " is out of range [0, " + std::to_string(in->n_file) + ")");
   if ((in->count_a2 != 0 && in->count_a2 != 1) || (in->missing != 0 && in->missing != 1))
     return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: count_a2 and missing must be 0 or 1");
+  const bool with_cov = cov && cov->d != 0;
+  const int D = with_cov ? cov->d + 1 : 0;
+  std::vector<double> Q;
+  if (with_cov) AQ_TRY(aq_cov_host_basis(cov, in->n, "aq_prepare_data_bed_cov", &Q));
   AQ_TRY(aq_need_device(in->device));
   std::unique_ptr<aq_prep> h(new aq_prep());
   h->n = in->n; h->p = in->p; h->q = in->q; h->device = in->device;
   AqDev<int8_t> dG;
-  AqDev<double> dX, dfill;
+  AqDev<double> dX, dfill, dQt;
   long long n_mis = 0, p_mis = 0, first_mis = -1;
+  if (with_cov) {
+    AQ_TRY(dQt.alloc(Q.size()));
+    AQ_HIP(hipMemcpy(dQt.get(), Q.data(), Q.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
   AQ_TRY(aq_bed_decode(h.get(), in, &dG));
   for (int j = 0; j < in->p; j++) {
     const int m = h->gcounts[4 * (size_t)j + 3];
     if (m > 0) { n_mis += m; p_mis++; if (first_mis < 0) first_mis = j; }
   }
-  if (n_mis == 0) {
+  if (n_mis == 0 && with_cov) {   // the decoded dosages enter the residual pass as int8; its fp64 output enters the pipeline
+    AQ_TRY(dX.alloc((size_t)in->n * in->p));
+    AQ_TRY(aq_cov_residualise_x<int8_t>(h.get(), dG.get(), dX.get(), dQt.get(), D));
+    dG.reset();
+    AQ_TRY(aq_prepare_x_device<double>(h.get(), dX.get()));
+  } else if (n_mis == 0) {
     AQ_TRY(aq_prepare_x_device<int8_t>(h.get(), dG.get()));
   } else if (!in->missing) {
     return aq_fail(AQ_ERR_ARG, "X must be a non-empty a numeric matrix, finite without missing value. " + std::to_string(n_mis) +
@@ -504,12 +656,27 @@ extern "C" int aq_prepare_data_bed(const aq_prep_bed_input *in, aq_prep_handle *
     AQ_HIP(hipGetLastError());
     AQ_HIP(hipDeviceSynchronize());
     dG.reset();
+    if (with_cov) AQ_TRY(aq_cov_residualise_x<double>(h.get(), dX.get(), dX.get(), dQt.get(), D));   // in place
     AQ_TRY(aq_prepare_x_device<double>(h.get(), dX.get()));
   }
   dG.reset();
   dX.reset();
-  AQ_TRY(aq_prepare_y(h.get(), in->Y));
+  AQ_TRY(with_cov ? aq_prepare_y(h.get(), in->Y, dQt.get(), D) : aq_prepare_y(h.get(), in->Y));
   *out = h.release();
+  return AQ_OK;
+}
+
+extern "C" int aq_prepare_data_bed(const aq_prep_bed_input *in, aq_prep_handle *out) { return aq_prepare_data_bed_impl(in, nullptr, out); }
+
+extern "C" int aq_prepare_data_bed_cov(const aq_prep_bed_input *in, const aq_prep_cov *cov, aq_prep_handle *out) {
+  return aq_prepare_data_bed_impl(in, cov, out);
+}
+
+extern "C" int aq_prep_cov_info(aq_prep_handle h, int32_t *d, uint8_t *absorbed, double *r2) {
+  if (!h) return aq_fail(AQ_ERR_ARG, "NULL handle");
+  if (d) *d = h->n_cov;
+  if (absorbed) std::copy(h->cov_absorbed.begin(), h->cov_absorbed.end(), absorbed);
+  if (r2) std::copy(h->cov_r2.begin(), h->cov_r2.end(), r2);
   return AQ_OK;
 }
 

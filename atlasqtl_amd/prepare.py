@@ -5,7 +5,8 @@ Follows R/prepare_atlasqtl.R:8-124 (``prepare_data_``, ``check_verbose_``,
 ``rm_constant_``, ``rm_collinear_``).  Error messages keep the reference's
 wording so tests read like the reference's own.  The argument checks run on the host;
 the O(n p) work itself -- scale(X), the removal of constant and duplicated columns,
-the centring of Y -- runs on the GPU (aq_prepare_data) and X stays there.
+the centring of Y -- runs on the GPU (aq_prepare_data) and X stays there.  Covariates, which the reference
+does not take, are regressed out of X and Y there as well (aq_prepare_data_cov).
 """
 from __future__ import annotations
 
@@ -110,10 +111,13 @@ class PreparedData:
     """The standardised compact X (n x p) and the centred Y resident on the GPU (aq_prepare_data).  VbRun takes it in place
     of the X array; `Y` is the host copy of the centred responses (n x q, small) that the hyper-parameter rules need."""
 
-    def __init__(self, handle, n, p, q, Y, device, genotype_counts=None):
+    def __init__(self, handle, n, p, q, Y, device, genotype_counts=None, n_cov=0, cov_absorbed=None, cov_r2=None):
         self.handle, self.n, self.p, self.q, self.Y, self.device = handle, n, p, q, Y, device
         self.shape = (n, p)
         self.genotype_counts = genotype_counts      # 4 x p_given int32 (hom A1, het, hom A2, missing): PlinkBed input only
+        # covariates regressed out of X and Y (0: none); per column given: absorbed by them (bool), and the share of its
+        # variance they explain (NaN for a constant column).  None without covariates.
+        self.n_cov, self.cov_absorbed, self.cov_r2 = n_cov, cov_absorbed, cov_r2
 
     @property
     def x_ptr(self):
@@ -140,18 +144,39 @@ class PreparedData:
             pass
 
 
-def prepare_on_device(Y, X, device=0):
+def _covariates_arg(covariates, n):
+    """The covariates as aq_prepare_data_cov takes them: (AqPrepCov, the n x d Fortran array it points into), or (None, None)."""
+    if covariates is None:
+        return None, None
+    try:
+        Z = np.asfortranarray(covariates, dtype=np.float64)
+    except (TypeError, ValueError):
+        Z = None
+    if Z is None or Z.ndim != 2 or Z.shape[1] < 1 or not np.all(np.isfinite(Z)):
+        raise AtlasqtlError("covariates must be a non-empty a numeric matrix, finite without missing value.")
+    if Z.shape[0] != n:
+        raise AtlasqtlError(f"covariates and Y must have the same number of samples ({Z.shape[0]} and {n} rows).")
+    cov = _lib.AqPrepCov()
+    cov.d, cov.Z = Z.shape[1], _lib.as_dp(Z)
+    return cov, Z
+
+
+def prepare_on_device(Y, X, device=0, covariates=None):
     """scale(X), constant / duplicate-column removal and the centring of Y on the GPU (R/prepare_atlasqtl.R:57-83).
     X: float64 (n x p), int8 dosages (1 byte per genotype: the fp64 matrix is then never formed on the host), or a
     plink.PlinkBed (2 bits per genotype: the packed blocks of the .bed are uploaded and unpacked on the GPU; the returned
     PreparedData then carries genotype_counts).
+    covariates: n x d (1 <= d <= 96, finite, rows as in Y), regressed with an intercept out of every column of X (over all
+    rows) and of Y (over the column's observed rows) before the above; a column of X that they explain (1 - R^2 <= 1e-10) is
+    reported constant and flagged in PreparedData.cov_absorbed.
     Returns (PreparedData, bool_cst_x [p], bool_coll_x [p, original numbering], dup_of [p])."""
     import ctypes as C
     from .plink import PlinkBed
     Y = np.asfortranarray(Y, dtype=np.float64)
     n, q = Y.shape
+    cov, Z = _covariates_arg(covariates, n)
     if isinstance(X, PlinkBed):
-        return _prepare_bed_on_device(Y, X, device)
+        return _prepare_bed_on_device(Y, X, device, cov)
     pin = _lib.AqPrepInput()
     if np.asarray(X).dtype == np.int8:
         Xa = np.asfortranarray(X)
@@ -164,11 +189,14 @@ def prepare_on_device(Y, X, device=0):
     p = Xa.shape[1]
     pin.n, pin.p, pin.q, pin.Y, pin.device = n, p, q, _lib.as_dp(Y), int(device)
     h = C.c_void_p()
-    rc = _lib.lib().aq_prepare_data(C.byref(pin), C.byref(h))
-    return _prepared_from_handle(rc, h, "aq_prepare_data", n, p, q, device)
+    if cov is None:
+        rc = _lib.lib().aq_prepare_data(C.byref(pin), C.byref(h))
+        return _prepared_from_handle(rc, h, "aq_prepare_data", n, p, q, device)
+    rc = _lib.lib().aq_prepare_data_cov(C.byref(pin), C.byref(cov), C.byref(h))
+    return _prepared_from_handle(rc, h, "aq_prepare_data_cov", n, p, q, device, cov=True)
 
 
-def _prepared_from_handle(rc, h, what, n, p, q, device, bed=False):
+def _prepared_from_handle(rc, h, what, n, p, q, device, bed=False, cov=False):
     """The return value of prepare_on_device from the handle aq_prepare_data / aq_prepare_data_bed made (or their error)."""
     import ctypes as C
     if rc != 0:
@@ -186,11 +214,18 @@ def _prepared_from_handle(rc, h, what, n, p, q, device, bed=False):
     if bed:
         counts = np.zeros((4, p), dtype=np.int32, order="F")
         _lib.check(_lib.lib().aq_prep_genotype_counts(h, _lib.as_ip(counts)), "aq_prep_genotype_counts")
-    return (PreparedData(h, n, int(pk.value), q, Yc, int(device), genotype_counts=counts), cst.astype(bool),
-            coll.astype(bool), dup)
+    n_cov, absorbed, r2 = 0, None, None
+    if cov:
+        d = C.c_int32(0)
+        absorbed = np.zeros(p, dtype=np.uint8); r2 = np.zeros(p)
+        _lib.check(_lib.lib().aq_prep_cov_info(h, C.byref(d), absorbed.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.as_dp(r2)),
+                   "aq_prep_cov_info")
+        n_cov, absorbed = int(d.value), absorbed.astype(bool)
+    return (PreparedData(h, n, int(pk.value), q, Yc, int(device), genotype_counts=counts, n_cov=n_cov, cov_absorbed=absorbed,
+                         cov_r2=r2), cst.astype(bool), coll.astype(bool), dup)
 
 
-def _prepare_bed_on_device(Y, bed, device):
+def _prepare_bed_on_device(Y, bed, device, cov=None):
     """prepare_on_device for a plink.PlinkBed: the packed blocks go to aq_prepare_data_bed as they are."""
     import ctypes as C
     n, q = Y.shape
@@ -204,16 +239,22 @@ def _prepare_bed_on_device(Y, bed, device):
     pin.Y, pin.device = _lib.as_dp(Y), int(device)
     pin.count_a2, pin.missing = int(bed.count == "A2"), int(bed.missing == "mean")
     h = C.c_void_p()
-    rc = _lib.lib().aq_prepare_data_bed(C.byref(pin), C.byref(h))
+    if cov is None:
+        rc = _lib.lib().aq_prepare_data_bed(C.byref(pin), C.byref(h))
+    else:
+        rc = _lib.lib().aq_prepare_data_bed_cov(C.byref(pin), C.byref(cov), C.byref(h))
     del blocks
-    return _prepared_from_handle(rc, h, "aq_prepare_data_bed", n, bed.p, q, device, bed=True)
+    return _prepared_from_handle(rc, h, "aq_prepare_data_bed" + ("" if cov is None else "_cov"), n, bed.p, q, device, bed=True,
+                                 cov=cov is not None)
 
 
 def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path,
-                  names_x=None, names_y=None, device=0):
+                  names_x=None, names_y=None, device=0, covariates=None):
     """R/prepare_atlasqtl.R:8-87.  Returns dict(Y, X, bool_rmvd_x, initial_colnames_X,
-    rmvd_cst_x, rmvd_coll_x, names_x, names_y, genotype_counts); X is a PreparedData (the standardised matrix lives on the
-    GPU), Y the centred responses on the host.  X may be float64, int8 dosages or a plink.PlinkBed, whose variant IDs are
+    rmvd_cst_x, rmvd_coll_x, names_x, names_y, genotype_counts, n_covariates, rmvd_cov_x, cov_r2_x); X is a PreparedData (the
+    standardised matrix lives on the GPU), Y the centred responses on the host.  With covariates (prepare_on_device) both are
+    residuals; rmvd_cov_x names the predictors that the covariates absorb (they are in rmvd_cst_x too) and cov_r2_x holds, per
+    predictor given, the share of its variance that they explain.  X may be float64, int8 dosages or a plink.PlinkBed, whose variant IDs are
     the default names_x and whose per-variant genotype counts are returned as genotype_counts (None otherwise)."""
     from .plink import PlinkBed
     is_bed = isinstance(X, PlinkBed)
@@ -247,11 +288,13 @@ def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_p
         names_y = [f"Resp_{k + 1}" for k in range(q)]
 
     # scale(X), rm_constant_, rm_collinear_, centring of Y: on the device (aq_prepare.hip); X stays there
-    prep, bool_cst_x, bool_coll_full, dup_of = prepare_on_device(Y, X, device)
+    prep, bool_cst_x, bool_coll_full, dup_of = prepare_on_device(Y, X, device, covariates)
     rmvd_cst_x = [names_x[j] for j in np.where(bool_cst_x)[0]] if bool_cst_x.any() else None
     names_after_cst = [nm for nm, b in zip(names_x, bool_cst_x) if not b]
     bool_rmvd_x = bool_cst_x | bool_coll_full
     rmvd_coll_x = {names_x[j]: names_x[dup_of[j]] for j in np.where(bool_coll_full)[0]} or None   # removed name -> kept name
     return dict(Y=prep.Y, X=prep, bool_rmvd_x=bool_rmvd_x, initial_colnames_X=names_after_cst,
                 rmvd_cst_x=rmvd_cst_x, rmvd_coll_x=rmvd_coll_x, genotype_counts=prep.genotype_counts,
+                n_covariates=prep.n_cov, cov_r2_x=prep.cov_r2,
+                rmvd_cov_x=[names_x[j] for j in np.where(prep.cov_absorbed)[0]] if prep.n_cov and prep.cov_absorbed.any() else None,
                 names_x=[nm for nm, b in zip(names_x, bool_rmvd_x) if not b], names_y=list(names_y))

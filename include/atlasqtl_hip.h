@@ -442,6 +442,41 @@ int aq_prep_genotype_counts(aq_prep_handle h, int32_t *counts);   /* 4 x p colum
                                                                      over the n rows used; AQ_ERR_ARG for a handle that
                                                                      aq_prepare_data made                              */
 
+/* ------------------------------------------------------------------------------------------
+ * Covariates: aq_prepare_data / aq_prepare_data_bed on the residuals of X and Y after regression on W = [1, Z], Z an
+ * n x d matrix of covariates (age, sex, genotype PCs, PEER or batch factors ...), finite, 1 <= d <= 96, d + 1 < n.  The fit
+ * is the fit of the unchanged code to the residualised data; the reference has no such argument (its users residualise in R).
+ * Q is an orthonormal basis of W's columns taken in order (Q[:, 0] = 1 / sqrt(n)).
+ *   X   x_j <- x_j - Q (Q' x_j) over all n rows, applied twice.  With s0 = sum_i (x_ij - mean_j)^2 and s1 = sum_i xr_ij^2, a
+ *       non-constant column with s1 <= 1e-10 s0 is ABSORBED by the covariates: it is written as all 0.0 and the pipeline then
+ *       reports it constant (bool_cst).  (The error of xr is about eps |x|, so at 1 - R^2 = 1e-10 the standardised column is
+ *       still good to about 1e-11; below that it is rounding noise which scale() would blow up to unit variance.)  The fp64
+ *       pipeline of aq_prepare_data then runs on the residuals unchanged; identical columns give bit-identical residuals.
+ *   Y   for trait k with observed rows O_k: y_k[O_k] <- y_k[O_k] - W[O_k] b_k, b_k the least-squares solution on those rows
+ *       (Cholesky of Q[O_k]' Q[O_k], one step of refinement); NaN stays NaN.  This replaces the centring.  |O_k| <= d + 1 or a
+ *       Cholesky pivot <= 1e-10: AQ_ERR_ARG, "covariates are collinear on the samples observed for column k of Y" (k 1-based),
+ *       after the two missingness guards.
+ * For a trait with missing rows the residual genotypes are orthogonal to the covariates over all n rows, not over O_k (as in
+ * every tool that residualises the genotypes once), and the model is not told about the d + 1 degrees of freedom removed.
+ *   aq_prepare_data_cov, aq_prepare_data_bed_cov   cov == NULL or cov->d == 0: exactly aq_prepare_data / aq_prepare_data_bed.
+ *       On the bed path the decoded int8 dosages (missing = 1 with missing calls: the imputed fp64 matrix) are residualised.
+ *   aq_prep_cov_info   d (0: the handle was made without covariates, nothing else is written); absorbed[p]; r2[p] = 1 - s1 / s0
+ *       per column given (NaN for a constant column).  Any pointer may be NULL.
+ *   aq_cov_basis       host only: Q (n x (d + 1) column-major) by modified Gram-Schmidt applied twice.  Covariate l (0-based)
+ *       is collinear when what is left of it after the intercept and the covariates before it has a squared norm <= 1e-10
+ *       times its own (a constant covariate is collinear with the intercept): AQ_ERR_ARG, *bad_col = l, the message names
+ *       column l + 1.  Otherwise *bad_col = -1.  bad_col may be NULL.
+ * NULL, d > 96, d + 1 >= n, a non-finite entry of Z and a collinear covariate are AQ_ERR_ARG before any device call.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_prep_cov {
+  int32_t d;
+  const double *Z;   /* n x d column-major, host */
+} aq_prep_cov;
+int aq_prepare_data_cov(const aq_prep_input *in, const aq_prep_cov *cov, aq_prep_handle *out);
+int aq_prepare_data_bed_cov(const aq_prep_bed_input *in, const aq_prep_cov *cov, aq_prep_handle *out);
+int aq_prep_cov_info(aq_prep_handle h, int32_t *d, uint8_t *absorbed, double *r2);
+int aq_cov_basis(const double *Z, int32_t n, int32_t d, double *Q, int32_t *bad_col);
+
 #ifdef __cplusplus
 }
 #endif
