@@ -53,6 +53,10 @@ class AqPrepCov(C.Structure):
     _fields_ = [("d", C.c_int32), ("Z", dp)]
 
 
+class AqPrepLd(C.Structure):
+    _fields_ = [("window", C.c_int32), ("r2", C.c_double), ("group", ip), ("pos", C.POINTER(C.c_int64)), ("window_bp", C.c_int64)]
+
+
 class AqVbMultiOut(C.Structure):
     _fields_ = [
         ("beta_vb", dp), ("gam_vb", dp), ("mu_beta_vb", dp), ("theta_vb", dp), ("zeta_vb", dp), ("lam2_inv_vb", dp),
@@ -145,6 +149,9 @@ SYMBOLS = {
     "aq_prepare_data_bed_cov": (C.c_int, [C.POINTER(AqPrepBedInput), C.POINTER(AqPrepCov), C.POINTER(C.c_void_p)]),
     "aq_prep_cov_info": (C.c_int, [C.c_void_p, ip, C.POINTER(C.c_uint8), dp]),
     "aq_cov_basis": (C.c_int, [dp, C.c_int32, C.c_int32, dp, ip]),
+    "aq_prep_ld_prune": (C.c_int, [C.c_void_p, C.POINTER(AqPrepLd)]),
+    "aq_prep_ld_info": (C.c_int, [C.c_void_p, ip, C.POINTER(C.c_uint8), ip, dp]),
+    "aq_prep_ld_band": (C.c_int, [C.c_void_p, C.c_int32, dp]),
 }
 
 _lib = None

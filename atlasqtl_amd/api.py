@@ -64,7 +64,7 @@ def add_collinear_back_pairs_(assoc, rs_thres, theta_vb, initial_colnames_X, rmv
 def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, verbose=1, list_hyper=None,
              list_init=None, save_hyper=False, save_init=False, full_output=False, thinned_elbo_eval=True,
              checkpoint_path=None, trace_path=None, add_collinear_back=False, device=0, device_init=False,
-             sparse_output=None, covariates=None):
+             sparse_output=None, covariates=None, ld_prune=None):
     """R/atlasqtl.R:179-322.
 
     X: a float64 matrix, int8 dosages, or a plink.PlinkBed (a PLINK 1 .bed / .bim / .fam fileset, unpacked on the GPU): the
@@ -83,7 +83,21 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
     the fit is the fit to those residuals.  The result then carries `n_covariates`, `rmvd_cov_x` (names of the predictors
     that the covariates explain entirely, or None; they are among `rmvd_cst_x`) and `cov_r2_x` (per predictor given, the
     share of its variance that the covariates explain).  For a response with missing values the predictors are adjusted
-    over all samples, not over its observed ones, and the model is not told about the d + 1 degrees of freedom removed."""
+    over all samples, not over its observed ones, and the model is not told about the d + 1 degrees of freedom removed.
+
+    ld_prune = {"r2": 0.8, "window": 500, "window_bp": None, "groups": None, "positions": None} (missing keys take these
+    values): prune the predictors for linkage disequilibrium on the GPU before the fit, on the standardised columns the fit
+    sees (after constant and duplicate removal, with covariates on the residuals).  Going through the predictors in order, one
+    is removed when a kept predictor at most `window` columns before it, in the same group (one label per predictor given; a
+    PlinkBed's chromosomes by default) and, with window_bp, at most that many base pairs away (`positions`; a PlinkBed's by
+    default) has a squared correlation above r2 with it.  The result then carries `rmvd_ld_x` (removed name -> the kept
+    predictor that tags it, or None) and `ld_r2_x` (per predictor given, its r^2 with that predictor, NaN otherwise);
+    `names_x` is the pruned list, and a list_hyper / list_init of the original p is cut accordingly.  Not with
+    add_collinear_back=True."""
+    if ld_prune is not None and add_collinear_back:
+        raise ValueError("add_collinear_back=True cannot be combined with ld_prune: a predictor removed for LD is not a copy of "
+                         "the predictor that tags it, and the add-back maps assume copies (they would hand it the tag's "
+                         "estimates).  Read the tags off rmvd_ld_x, or fit without pruning.")
     sparse = None if sparse_output is None else sparse_output_options(sparse_output)
     if sparse is not None and add_collinear_back and sparse["fdr_adjust"]:
         raise ValueError("add_collinear_back=True cannot be combined with sparse_output in FDR mode: the re-inserted copies "
@@ -95,7 +109,8 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
                          "cannot reproduce.  Use the dense output.")
     check_verbose_(verbose)
     check_annealing_(anneal)
-    dat = prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path, covariates=covariates)
+    dat = prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path, covariates=covariates,
+                        ld_prune=ld_prune)
     bool_rmvd_x = dat["bool_rmvd_x"]
     Xs, Yc = dat["X"], dat["Y"]
     n, p = Xs.shape
@@ -128,6 +143,8 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
         res["genotype_counts"] = dat["genotype_counts"]
     if covariates is not None:
         res["n_covariates"], res["rmvd_cov_x"], res["cov_r2_x"] = dat["n_covariates"], dat["rmvd_cov_x"], dat["cov_r2_x"]
+    if ld_prune is not None:
+        res["rmvd_ld_x"], res["ld_r2_x"] = dat["rmvd_ld_x"], dat["ld_r2_x"]
     names_snp = dat["names_x"]
     if sparse is not None:
         if sparse["summary"]:

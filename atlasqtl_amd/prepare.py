@@ -6,7 +6,8 @@ Follows R/prepare_atlasqtl.R:8-124 (``prepare_data_``, ``check_verbose_``,
 wording so tests read like the reference's own.  The argument checks run on the host;
 the O(n p) work itself -- scale(X), the removal of constant and duplicated columns,
 the centring of Y -- runs on the GPU (aq_prepare_data) and X stays there.  Covariates, which the reference
-does not take, are regressed out of X and Y there as well (aq_prepare_data_cov).
+does not take, are regressed out of X and Y there as well (aq_prepare_data_cov), and the compact matrix can be pruned for
+linkage disequilibrium there before the fit (aq_prep_ld_prune).
 """
 from __future__ import annotations
 
@@ -114,6 +115,9 @@ class PreparedData:
     def __init__(self, handle, n, p, q, Y, device, genotype_counts=None, n_cov=0, cov_absorbed=None, cov_r2=None):
         self.handle, self.n, self.p, self.q, self.Y, self.device = handle, n, p, q, Y, device
         self.shape = (n, p)
+        # LD pruning (prepare_on_device(ld_prune=)), per column given: removed for LD (bool), the index of the kept column that
+        # tags it (-1: none) and its r^2 with that column (NaN: not removed for LD).  None without pruning.
+        self.ld_removed = self.ld_of = self.ld_r2 = None
         self.genotype_counts = genotype_counts      # 4 x p_given int32 (hom A1, het, hom A2, missing): PlinkBed input only
         # covariates regressed out of X and Y (0: none); per column given: absorbed by them (bool), and the share of its
         # variance they explain (NaN for a constant column).  None without covariates.
@@ -130,6 +134,12 @@ class PreparedData:
     def X_host(self):
         out = np.empty((self.n, self.p), order="F")
         _lib.check(_lib.lib().aq_prep_get(self.handle, _lib.as_dp(out), None), "aq_prep_get")
+        return out
+
+    def ld_band(self, window):
+        """r(j - 1 - b, j) of the matrix as it stands, p x window (NaN where j - 1 - b < 0): aq_prep_ld_band."""
+        out = np.empty((self.p, int(window)), order="F")
+        _lib.check(_lib.lib().aq_prep_ld_band(self.handle, int(window), _lib.as_dp(out)), "aq_prep_ld_band")
         return out
 
     def close(self):
@@ -161,7 +171,106 @@ def _covariates_arg(covariates, n):
     return cov, Z
 
 
-def prepare_on_device(Y, X, device=0, covariates=None):
+LD_PRUNE_DEFAULTS = {"r2": 0.8, "window": 500, "window_bp": None, "groups": None, "positions": None}
+LD_MAX_WINDOW = 4096          # AQ_LD_MAX_WINDOW of csrc/aq_ld_kernels.h
+
+
+def _is_whole(x):
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
+def ld_prune_options(ld_prune):
+    """The `ld_prune` argument of atlasqtl() / prepare_on_device with its defaults filled in and checked on the host:
+    r2 in (0, 1], window a whole number in [1, 4096], window_bp None or a whole number >= 1, groups None or one label per
+    predictor given, positions None or one whole number per predictor given."""
+    if not isinstance(ld_prune, dict) or set(ld_prune) - set(LD_PRUNE_DEFAULTS):
+        raise AtlasqtlError("ld_prune must be None or a dict with keys among 'r2', 'window', 'window_bp', 'groups', 'positions'.")
+    o = {**LD_PRUNE_DEFAULTS, **ld_prune}
+    r2 = o["r2"]
+    if isinstance(r2, (bool, np.bool_)) or not isinstance(r2, (int, float, np.integer, np.floating)) or not (0.0 < float(r2) <= 1.0):
+        raise AtlasqtlError(f"ld_prune: r2 must be a number in (0, 1], not {r2!r}.")
+    if not _is_whole(o["window"]) or not (1 <= int(o["window"]) <= LD_MAX_WINDOW):
+        raise AtlasqtlError(f"ld_prune: window must be a whole number in [1, {LD_MAX_WINDOW}], not {o['window']!r}.")
+    if o["window_bp"] is not None and (not _is_whole(o["window_bp"]) or int(o["window_bp"]) < 1):
+        raise AtlasqtlError(f"ld_prune: window_bp must be None or a whole number >= 1, not {o['window_bp']!r}.")
+    if o["groups"] is not None:
+        g = np.asarray(o["groups"])
+        if g.ndim != 1 or g.size == 0:
+            raise AtlasqtlError("ld_prune: groups must be None or a one-dimensional array with one label per predictor.")
+    if o["positions"] is not None:
+        try:
+            pos = np.asarray(o["positions"])
+            ok = pos.ndim == 1 and pos.size > 0 and (np.issubdtype(pos.dtype, np.integer) or
+                                                      (np.issubdtype(pos.dtype, np.floating) and bool(np.all(np.isfinite(pos)))
+                                                       and bool(np.all(pos == np.round(pos)))))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise AtlasqtlError("ld_prune: positions must be None or a one-dimensional array of whole numbers, one per predictor.")
+    o["r2"], o["window"] = float(r2), int(o["window"])
+    o["window_bp"] = None if o["window_bp"] is None else int(o["window_bp"])
+    return o
+
+
+def _ld_arg(ld_prune, X):
+    """The pruning as aq_prep_ld_prune takes it: (AqPrepLd, the arrays it points into), or (None, None).  For a PlinkBed the
+    groups default to its chromosomes and, with window_bp, the positions to its base-pair positions.  All checks are here,
+    before the first device call."""
+    if ld_prune is None:
+        return None, None
+    import ctypes as C
+    from .plink import PlinkBed
+    o = ld_prune_options(ld_prune)
+    p = X.p if isinstance(X, PlinkBed) else (np.shape(X)[1] if np.ndim(X) == 2 else -1)
+    groups, positions = o["groups"], o["positions"]
+    if isinstance(X, PlinkBed):
+        if groups is None:
+            groups = X.chrom
+        if positions is None and o["window_bp"] is not None:
+            positions = X.pos
+    if o["window_bp"] is not None and positions is None:
+        raise AtlasqtlError("ld_prune: window_bp needs positions (one per predictor given).")
+    ld = _lib.AqPrepLd()
+    ld.window, ld.r2, ld.window_bp = o["window"], o["r2"], 0 if o["window_bp"] is None else o["window_bp"]
+    ld.group, ld.pos = None, None
+    keep = []
+    for name, arr in (("groups", groups), ("positions", positions)):
+        if arr is not None and np.asarray(arr).shape != (p,):
+            raise AtlasqtlError(f"ld_prune: {name} must hold one entry per predictor given ({p}), not {np.asarray(arr).shape}.")
+    if groups is not None:
+        codes = np.ascontiguousarray(np.unique(np.asarray(groups), return_inverse=True)[1].reshape(-1), dtype=np.int32)
+        ld.group = _lib.as_ip(codes)
+        keep.append(codes)
+    if positions is not None:
+        pos = np.ascontiguousarray(positions, dtype=np.int64)
+        ld.pos = pos.ctypes.data_as(C.POINTER(C.c_int64))
+        keep.append(pos)
+    return ld, keep
+
+
+def _ld_prune_handle(ret, ld):
+    """aq_prep_ld_prune on the PreparedData of a prepare_on_device return value; fills its ld_* fields."""
+    import ctypes as C
+    prep = ret[0]
+    L = _lib.lib()
+    p = len(ret[1])
+    rc = L.aq_prep_ld_prune(prep.handle, C.byref(ld))
+    if rc != 0:
+        msg = L.aq_last_error().decode("utf-8", "replace")
+        prep.close()
+        if rc == 1:
+            raise AtlasqtlError(msg)
+        raise _lib.AtlasqtlHipError(f"aq_prep_ld_prune: [{rc}] {msg}")
+    pk = C.c_int32(0)
+    rm = np.zeros(p, dtype=np.uint8); of = np.zeros(p, dtype=np.int32); r2 = np.zeros(p)
+    _lib.check(L.aq_prep_ld_info(prep.handle, C.byref(pk), rm.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.as_ip(of), _lib.as_dp(r2)),
+               "aq_prep_ld_info")
+    prep.p, prep.shape = int(pk.value), (prep.n, int(pk.value))
+    prep.ld_removed, prep.ld_of, prep.ld_r2 = rm.astype(bool), of, r2
+    return ret
+
+
+def prepare_on_device(Y, X, device=0, covariates=None, ld_prune=None):
     """scale(X), constant / duplicate-column removal and the centring of Y on the GPU (R/prepare_atlasqtl.R:57-83).
     X: float64 (n x p), int8 dosages (1 byte per genotype: the fp64 matrix is then never formed on the host), or a
     plink.PlinkBed (2 bits per genotype: the packed blocks of the .bed are uploaded and unpacked on the GPU; the returned
@@ -169,12 +278,27 @@ def prepare_on_device(Y, X, device=0, covariates=None):
     covariates: n x d (1 <= d <= 96, finite, rows as in Y), regressed with an intercept out of every column of X (over all
     rows) and of Y (over the column's observed rows) before the above; a column of X that they explain (1 - R^2 <= 1e-10) is
     reported constant and flagged in PreparedData.cov_absorbed.
+    ld_prune: None, or a dict (ld_prune_options: r2 0.8, window 500, window_bp, groups, positions).  After the above, column j of
+    the compact matrix is removed when a kept column i < j with j - i <= window, the same group and, with window_bp, a
+    position within window_bp of its own has r(i, j)^2 > r2; the first one wins.  The PreparedData then holds the pruned matrix
+    and ld_removed / ld_of / ld_r2 per column given.  A PlinkBed's chromosomes are the default groups, its base-pair positions
+    the default positions.
     Returns (PreparedData, bool_cst_x [p], bool_coll_x [p, original numbering], dup_of [p])."""
     import ctypes as C
     from .plink import PlinkBed
     Y = np.asfortranarray(Y, dtype=np.float64)
     n, q = Y.shape
     cov, Z = _covariates_arg(covariates, n)
+    ld, ld_arrays = _ld_arg(ld_prune, X)                       # checked here, before the first device call
+    ret = _prepare_unpruned(Y, X, device, cov)
+    return ret if ld is None else _ld_prune_handle(ret, ld)
+
+
+def _prepare_unpruned(Y, X, device, cov):
+    """prepare_on_device before any pruning: Y float64 in Fortran order, cov from _covariates_arg."""
+    import ctypes as C
+    from .plink import PlinkBed
+    n, q = Y.shape
     if isinstance(X, PlinkBed):
         return _prepare_bed_on_device(Y, X, device, cov)
     pin = _lib.AqPrepInput()
@@ -249,13 +373,16 @@ def _prepare_bed_on_device(Y, bed, device, cov=None):
 
 
 def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path,
-                  names_x=None, names_y=None, device=0, covariates=None):
+                  names_x=None, names_y=None, device=0, covariates=None, ld_prune=None):
     """R/prepare_atlasqtl.R:8-87.  Returns dict(Y, X, bool_rmvd_x, initial_colnames_X,
     rmvd_cst_x, rmvd_coll_x, names_x, names_y, genotype_counts, n_covariates, rmvd_cov_x, cov_r2_x); X is a PreparedData (the
     standardised matrix lives on the GPU), Y the centred responses on the host.  With covariates (prepare_on_device) both are
     residuals; rmvd_cov_x names the predictors that the covariates absorb (they are in rmvd_cst_x too) and cov_r2_x holds, per
     predictor given, the share of its variance that they explain.  X may be float64, int8 dosages or a plink.PlinkBed, whose variant IDs are
-    the default names_x and whose per-variant genotype counts are returned as genotype_counts (None otherwise)."""
+    the default names_x and whose per-variant genotype counts are returned as genotype_counts (None otherwise).
+    With ld_prune (prepare_on_device) bool_rmvd_x and names_x account for the predictors removed for LD as well; rmvd_ld_x maps
+    each of them to the kept predictor that tags it and ld_r2_x holds, per predictor given, its r^2 with that one (NaN: kept or
+    removed for another reason).  Both are None without pruning."""
     from .plink import PlinkBed
     is_bed = isinstance(X, PlinkBed)
     check_vector_(user_seed, "user_seed", size=1, null_ok=True)
@@ -288,13 +415,17 @@ def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_p
         names_y = [f"Resp_{k + 1}" for k in range(q)]
 
     # scale(X), rm_constant_, rm_collinear_, centring of Y: on the device (aq_prepare.hip); X stays there
-    prep, bool_cst_x, bool_coll_full, dup_of = prepare_on_device(Y, X, device, covariates)
+    prep, bool_cst_x, bool_coll_full, dup_of = prepare_on_device(Y, X, device, covariates, ld_prune)
     rmvd_cst_x = [names_x[j] for j in np.where(bool_cst_x)[0]] if bool_cst_x.any() else None
     names_after_cst = [nm for nm, b in zip(names_x, bool_cst_x) if not b]
     bool_rmvd_x = bool_cst_x | bool_coll_full
+    rmvd_ld_x = None
+    if prep.ld_removed is not None:
+        bool_rmvd_x = bool_rmvd_x | prep.ld_removed
+        rmvd_ld_x = {names_x[j]: names_x[prep.ld_of[j]] for j in np.where(prep.ld_removed)[0]} or None   # removed name -> tag name
     rmvd_coll_x = {names_x[j]: names_x[dup_of[j]] for j in np.where(bool_coll_full)[0]} or None   # removed name -> kept name
     return dict(Y=prep.Y, X=prep, bool_rmvd_x=bool_rmvd_x, initial_colnames_X=names_after_cst,
                 rmvd_cst_x=rmvd_cst_x, rmvd_coll_x=rmvd_coll_x, genotype_counts=prep.genotype_counts,
-                n_covariates=prep.n_cov, cov_r2_x=prep.cov_r2,
+                n_covariates=prep.n_cov, cov_r2_x=prep.cov_r2, rmvd_ld_x=rmvd_ld_x, ld_r2_x=prep.ld_r2,
                 rmvd_cov_x=[names_x[j] for j in np.where(prep.cov_absorbed)[0]] if prep.n_cov and prep.cov_absorbed.any() else None,
                 names_x=[nm for nm, b in zip(names_x, bool_rmvd_x) if not b], names_y=list(names_y))

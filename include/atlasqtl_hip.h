@@ -477,6 +477,44 @@ int aq_prepare_data_bed_cov(const aq_prep_bed_input *in, const aq_prep_cov *cov,
 int aq_prep_cov_info(aq_prep_handle h, int32_t *d, uint8_t *absorbed, double *r2);
 int aq_cov_basis(const double *Z, int32_t n, int32_t d, double *Q, int32_t *bad_col);
 
+/* ------------------------------------------------------------------------------------------
+ * LD pruning: thins the compact standardised matrix of a handle that any of the four aq_prepare_data* entries returned, so
+ * that no two kept predictors within `window` columns of each other correlate above a threshold.  The model splits a signal's
+ * posterior inclusion probability over every variant of an LD block; the reference's authors prune before they fit.  It runs
+ * on the columns the fit sees (after constant and duplicate removal, with covariates on the residuals) and where they lie.
+ * Xs is n x p1, every column with mean 0 and sum of squares n - 1; i, j below are compact indices.
+ *   r(i, j) = (Xs_i . Xs_j) / (n - 1).
+ *   A pair i < j is ELIGIBLE when j - i <= window, group[i] == group[j] (NULL: one group) and, if window_bp > 0,
+ *   |pos_j - pos_i| <= window_bp.
+ *   Columns are visited in increasing j.  Column j is REMOVED iff some KEPT column i < j forms an eligible pair with it and
+ *   r(i, j)^2 > r2 (strictly).  Its tag is the smallest such i.  The first column is always kept.  With r^2(A, B) > r2,
+ *   r^2(B, C) > r2 and r^2(A, C) <= r2 the result is A and C kept, B removed: first one wins, as rm_collinear_ does.
+ * The banded Gram matrix is formed on the f64 matrix pipe (2 n p1 window flop) and thresholded in registers: one bit per
+ * (column, band entry) is stored, never the p1 x window values.  One wave scans the bit rows; the kept columns are gathered
+ * into a new n x p_kept matrix, a copy of their bits, and the old one is released.
+ *   aq_prep_ld_prune   in place, once per handle.  Afterwards aq_prep_x_device, aq_prep_get and the p_kept of aq_prep_info
+ *                      describe the pruned matrix; bool_cst, bool_coll and dup_of are unchanged.
+ *   aq_prep_ld_info    in the ORIGINAL column numbering (p entries each, any pointer may be NULL): bool_ld[j] = 1 removed for
+ *                      LD; ld_of[j] the original index of its tag, else -1; ld_r2[j] = r(tag, j)^2, NaN where the column was
+ *                      not removed for LD.
+ *   aq_prep_ld_band    the band of the handle's current matrix, for inspection and tests: r_band[b p_kept + j] =
+ *                      r(j - 1 - b, j) for 0 <= b < window, NaN where j - 1 - b < 0.  Every entry is within (n + 2) 2^-53 of
+ *                      the exact quotient.  This entry does write the p_kept x window doubles.
+ * A NULL handle, struct or output, window outside [1, 4096], r2 outside (0, 1] or NaN, window_bp > 0 without pos, a second
+ * aq_prep_ld_prune on one handle and aq_prep_ld_info on an unpruned handle are AQ_ERR_ARG, with the entry's name in
+ * aq_last_error(), before any device call.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_prep_ld {
+  int32_t window;         /* 1 ... 4096 columns                                             */
+  double r2;              /* threshold on r^2, in (0, 1]; 1 removes nothing beyond rounding */
+  const int32_t *group;   /* p entries, original column numbering, or NULL: one group       */
+  const int64_t *pos;     /* p entries, original column numbering, or NULL                  */
+  int64_t window_bp;      /* <= 0: no distance limit; > 0 needs pos                         */
+} aq_prep_ld;
+int aq_prep_ld_prune(aq_prep_handle h, const aq_prep_ld *ld);
+int aq_prep_ld_info(aq_prep_handle h, int32_t *p_kept, uint8_t *bool_ld, int32_t *ld_of, double *ld_r2);
+int aq_prep_ld_band(aq_prep_handle h, int32_t window, double *r_band);
+
 #ifdef __cplusplus
 }
 #endif
