@@ -181,6 +181,43 @@ __global__ __launch_bounds__(512) void aq_k_gk_blocks(const double *__restrict__
   }
 }
 
+// ---- the diagonal of the per-trait Gram blocks where the subtraction cancels ---------------------------------------------------
+// X_norm_sq(j, k) = G_jj - sum over trait k's missing samples of x_ij^2 is the diagonal of the blocks above.  When the missing
+// samples carry almost all of x_j' x_j -- a rare variant whose carriers are all missing in trait k: G_jj = n - 1, X_norm_sq(j, k)
+// about 1 -- the difference keeps an absolute error of a few ulp of n, 4e-13 of its own size at n = 4000, and that entry's
+// sig2_beta_vb, mu_beta_vb and the trait's tau_vb inherit it (tests/test_gpu_regimes.py, mask-n1000-*, mask-wide-c12-*: tau_vb off
+// by up to 4e-12 after three sweeps, where the n-space reference holds 6e-15).  Such entries -- less than an eighth of G_jj left
+// -- are redone here with both sums carried in double-double (error-free products by FMA, two-sum accumulation), so that the
+// difference is exact to the last place.  One thread per (tile, block, SNP, trait); only the few affected threads loop.  Once per handle.
+__global__ void aq_k_gk_diag_exact(const double *__restrict__ XR, const double *__restrict__ G, const int *__restrict__ midx,
+                                   const int *__restrict__ mcnt4, const int *__restrict__ obs, double *__restrict__ GK, int n, int nb,
+                                   int ntile, int NR, int Mmax) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (size_t)ntile * nb * 256) return;
+  const int k = (int)(e & 15), jj = (int)((e >> 4) & 15);
+  const size_t tb = e >> 8;
+  const int b = (int)(tb % nb), tile = (int)(tb / nb);
+  if (obs && obs[tile * 16 + k]) return;               // summed over the observed samples directly: nothing cancels
+  double *dst = GK + ((size_t)tile * nb + b) * AQ_GK_STRIDE + (size_t)(jj * (jj + 1) / 2 + jj) * 16 + k;
+  const double gjj = G[(size_t)b * 256 + jj * 17];
+  if (!(*dst < 0.125 * gjj)) return;
+  const double *x = XR + (size_t)b * NR * 16 + jj;
+  double hi[2] = {0.0, 0.0}, lo[2] = {0.0, 0.0};
+  const int *ix = midx + ((size_t)tile * 16 + k) * Mmax;
+  const int m = 4 * mcnt4[tile * 16 + k];
+  for (int pass = 0; pass < 2; pass++) {
+    const int cnt = pass == 0 ? n : m;
+    for (int t = 0; t < cnt; t++) {
+      const double v = x[(size_t)(pass == 0 ? t : ix[t]) * 16];
+      const double pr = __dmul_rn(v, v), pe = __fma_rn(v, v, -pr);    // v^2 = pr + pe exactly (_rn: never contracted)
+      const double sm = __dadd_rn(hi[pass], pr), bb = __dsub_rn(sm, hi[pass]);
+      lo[pass] += __dadd_rn(__dadd_rn(__dsub_rn(hi[pass], __dsub_rn(sm, bb)), __dsub_rn(pr, bb)), pe);
+      hi[pass] = sm;
+    }
+  }
+  *dst = (hi[0] - hi[1]) + (lo[0] - lo[1]);
+}
+
 // ---- per-trait Gram blocks for the wide sample split (n > 10240): the same blocks as aq_k_gk_blocks, for any missingness ------
 // The index lists stay in global memory (int32, [ntile][16][Mmax], padded to groups of 16 with the all-zero row n_pad of XR), and
 // each trait uses the shorter of its two lists: obs[k] = 0 -- the missing samples, blocks = G - Xm' Xm as above; obs[k] = 1 -- the

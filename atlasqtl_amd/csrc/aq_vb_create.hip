@@ -306,6 +306,12 @@ extern "C" int aq_vb_create(const aq_vb_problem *pr, aq_vb_handle *out) {
         else
         hipLaunchKernelGGL(aq_k_gk_blocks, dim3((s->nb + bchunk - 1) / bchunk, s->ntile), dim3(512), aq_midx_lds_bytes(s->Mmax), 0, s->XR.get(),
                            s->G.get(), s->Gx.get(), s->midx.get(), s->mcnt4.get(), s->GK.get(), s->nb, s->NR, s->Mmax, bchunk);
+        {   // X_norm_sq(j, k) where that subtraction cancels (aq_setup_kernels.h::aq_k_gk_diag_exact)
+          const size_t tot = (size_t)s->ntile * s->nb * 256;
+          hipLaunchKernelGGL(aq_k_gk_diag_exact, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, s->XR.get(), s->G.get(), s->midx.get(),
+                             s->mcnt4.get(), s->la_wide ? s->mobs.get() : (const int *)nullptr, s->GK.get(), s->n, s->nb, s->ntile, s->NR,
+                             s->Mmax);
+        }
         AQ_HIP(hipGetLastError());
         AQ_HIP(hipDeviceSynchronize());
         s->XR.reset();

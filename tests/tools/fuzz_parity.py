@@ -5,7 +5,12 @@ AQ_FUZZ_LINK=1, or run(..., link_spread=True): every case also replaces the init
 and theta_vb by one in +-T, so that the probit link leaves the few table intervals the automatic init stays in.  T is drawn in
 0 ... 40 without annealing; with annealing in 0 ... min(1, sqrt(1000 / (sig02_inv_vb q))), which keeps L_vb of the reference's
 annealed update of lam2_inv_vb below 250 -- it returns NaN from about 745 on.  The gam_vb error is then reported on the logit
-scale as well: tests/test_gpu_link_range.py says why and how.)"""
+scale as well: tests/test_gpu_link_range.py says why and how.
+AQ_FUZZ_REGIME=ld+rare+scale[:per_trait], or run(..., regime=("ld", "rare", "scale"), hyper="per_trait"): the cases are drawn
+from tests/util.make_regime_problem instead of make_problem -- neighbouring SNPs in LD, rare variants, traits scaled by
+10^U(-4, 4), optionally per-trait hyper-parameters; p is then at least 96, q at least 18 with a last trait tile of two, n at least
+100, and mu_beta_vb is compared in the scale-following metric of tests/test_gpu_regimes.py.  Off by default: the cases of a
+given seed are unchanged without it.)"""
 import os
 import sys
 import time
@@ -15,13 +20,16 @@ import numpy as np
 
 import atlasqtl_amd as A
 from oracle import atlasqtl_oracle as O
-from tests.util import make_problem
+from tests.util import make_problem, make_regime_problem
 
 
-def run(ncases=30, seed=2024, link_spread=None):
+def run(ncases=30, seed=2024, link_spread=None, regime=None, hyper="auto"):
     """Returns the worst errors; raises AssertionError on the first mismatch."""
     if link_spread is None:
         link_spread = os.environ.get("AQ_FUZZ_LINK", "0") not in ("", "0")
+    if regime is None and os.environ.get("AQ_FUZZ_REGIME"):
+        spec = os.environ["AQ_FUZZ_REGIME"].split(":")
+        regime, hyper = tuple(spec[0].split("+")), (spec[1] if len(spec) > 1 else "auto")
     rng = np.random.default_rng(seed)
     worst = dict(elbo=0.0, mu=0.0, gam=0.0)
     if link_spread:
@@ -33,8 +41,14 @@ def run(ncases=30, seed=2024, link_spread=None):
         q = int(rng.integers(1, int(os.environ.get("AQ_FUZZ_QMAX", 70))))
         na = float(rng.choice([0.0, 0.0, 0.05, 0.2]))
         anneal = [None, (1, 2, 10), (2, 3, 5), (3, 2, 4)][int(rng.integers(0, 4))]
-        prob = make_problem(n, p, q, p_act=max(1, min(8, p // 3)), prob_assoc=0.4, na_frac=na, seed=int(rng.integers(1, 10**6)),
-                            init_seed=int(rng.integers(1, 10**6)), p0=(2, 6))
+        data_seed, init_seed = int(rng.integers(1, 10**6)), int(rng.integers(1, 10**6))
+        if regime:       # (after the case's draws, which stay what they are without the knob)
+            n, p = max(n, 100), max(p, 96)
+            q = max(q, 18) + (2 if max(q, 18) % 16 in (0, 1) else 0)
+            prob = make_regime_problem(n, p, q, regime, na_frac=na, hyper=hyper, seed=data_seed, init_seed=init_seed)
+        else:
+            prob = make_problem(n, p, q, p_act=max(1, min(8, p // 3)), prob_assoc=0.4, na_frac=na, seed=data_seed,
+                                init_seed=init_seed, p0=(2, 6))
         spread = ""
         if link_spread:      # (drawn after everything else of the case, so that the knob leaves the cases' shapes and data as they are)
             li = dict(prob["list_init"])
@@ -65,7 +79,14 @@ def run(ncases=30, seed=2024, link_spread=None):
             continue
         lref = np.array([r["lb"] for r in tr if r["lb"] is not None])
         e_elbo = float(np.max(np.abs(got["elbo_trace"][1] - lref) / np.abs(lref))) if lref.size else 0.0
-        e_mu = float(np.max(np.abs(got["mu_beta_vb"] - ref["mu_beta_vb"]) / np.maximum(np.abs(ref["mu_beta_vb"]), 1e-8)))
+        if regime:
+            from tests.test_gpu_regimes import MU_ATOL_OVER_RTOL, NO_CARRIER, x_norm_sq
+            xn, scale = x_norm_sq(prob), np.abs(ref["mu_beta_vb"])
+            sd_post = 1.0 / np.sqrt((xn + ref["sig2_inv_vb"]) * ref["tau_vb"][None, :])
+            scale = np.where(xn < NO_CARRIER, np.maximum(scale, sd_post), scale) + MU_ATOL_OVER_RTOL * np.nanstd(prob["Y"], axis=0, ddof=1)
+            e_mu = float(np.max(np.abs(got["mu_beta_vb"] - ref["mu_beta_vb"]) / scale))
+        else:
+            e_mu = float(np.max(np.abs(got["mu_beta_vb"] - ref["mu_beta_vb"]) / np.maximum(np.abs(ref["mu_beta_vb"]), 1e-8)))
         e_g = float(np.max(np.abs(got["gam_vb"] - ref["gam_vb"])))
         ok = got["it"] == ref["it"] and e_elbo < 1e-8 and e_mu < 1e-6 and e_g < 1e-8
         worst.update(elbo=max(worst["elbo"], e_elbo), mu=max(worst["mu"], e_mu), gam=max(worst["gam"], e_g))

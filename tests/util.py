@@ -173,6 +173,157 @@ def link_wave_classes(theta, zeta, sqrt_c=1.0):
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# Inputs along the axes that make_problem never leaves: the Gram structure of X (linkage disequilibrium), the per-entry
+# X_norm_sq(j, k) (rare variants whose carriers are missing in a trait), the per-trait scale, and per-trait hyper-parameters
+# (tests/test_regime_coverage_host.py asserts what they hold, tests/test_gpu_regimes.py runs them).
+REGIMES = ("ld", "rare", "scale")
+REGIME_BLOCK = 16                           # SNPs per block of the sweep kernels, traits per trait tile
+RARE_STEP, RARE_FIRST = 5, 4                # the rare columns: 4, 9, 14, ...: column 79 is the last of block 4, and the borders
+                                            # 16, 32, 48, 96, 112, 128 keep both of their columns for the LD pairs
+LD_RHO = (0.002, 0.2)                       # per-SNP flip probabilities of the haplotype copying, log-uniform
+LD_BORDER_RHO = 0.002                       # the first SNP of every block copies its neighbour at the lower end: r^2 about 0.99
+
+
+def block_borders(p):
+    """First columns of the SNP blocks 1, 2, ...: a border lies between columns c - 1 and c."""
+    return list(range(REGIME_BLOCK, p, REGIME_BLOCK))
+
+
+def chain_borders(p, nseg):
+    """First columns of the chained segments 1 ... nseg - 1 (aq_core_sweep_la.h: segment s starts at block nb s / nseg)."""
+    nb = -(-p // REGIME_BLOCK)
+    return [REGIME_BLOCK * (nb * s // nseg) for s in range(1, nseg)]
+
+
+def rare_columns(p):
+    return list(range(RARE_FIRST, p, RARE_STEP))
+
+
+def r2_pair(X, i, j):
+    """Squared correlation of two columns."""
+    a, b = X[:, i] - X[:, i].mean(), X[:, j] - X[:, j].mean()
+    return float((a @ b) ** 2 / ((a @ a) * (b @ b)))
+
+
+def _regime_genotypes(n, p, regime, rng):
+    """n x p dosages and the rare columns with their carriers {column: rows}."""
+    from tests.ld_util import haplotype_copy_genotypes
+    if "ld" in regime:
+        rho = np.exp(rng.uniform(np.log(LD_RHO[0]), np.log(LD_RHO[1]), size=p))
+        rho[block_borders(p)] = LD_BORDER_RHO
+        G = haplotype_copy_genotypes(n, p, rng, rho, maf=0.3).astype(np.float64)
+    else:
+        G = rng.binomial(2, 0.2, size=(n, p)).astype(np.float64)
+    carriers = {}
+    if "rare" in regime:
+        cols = rare_columns(p)
+        rows = rng.permutation(n)                   # disjoint carriers: no two rare columns are copies of each other
+        if 3 * len(cols) > n:
+            raise ValueError("make_regime_problem: n is too small for disjoint carriers")
+        for i, j in enumerate(cols):
+            m = 1 + i % 3                           # 1, 2 or 3 heterozygous carriers
+            carriers[j] = np.sort(rows[3 * i:3 * i + m])
+            G[:, j] = 0.0
+            G[carriers[j], j] = 1.0
+    # a column that came out constant or as a copy of an earlier one is drawn again (prepare_xy would drop it and shift the
+    # block borders).  In LD that is the usual fate of a SNP with a small flip probability at small n: it is redrawn as its left
+    # neighbour with two samples' dosages changed by one, which keeps the link; otherwise independently
+    for _ in range(100):
+        Xs = prepare_oracle.scale_columns(G)
+        bad = [j for j in range(p) if not np.all(np.isfinite(Xs[:, j]))]
+        seen = {}
+        for j in range(p):
+            if j not in bad and seen.setdefault(Xs[:, j].tobytes(), j) != j:
+                bad.append(j)
+        if not bad:
+            return G, carriers
+        for j in sorted(bad):
+            if j in carriers:
+                raise ValueError("make_regime_problem: a rare column is a copy")
+            if "ld" in regime and j > 0 and j - 1 not in carriers:
+                G[:, j] = G[:, j - 1]
+                rows = rng.choice(n, size=2, replace=False)
+                G[rows, j] = np.where(G[rows, j] < 2.0, G[rows, j] + 1.0, 1.0)
+            else:
+                G[:, j] = rng.binomial(2, 0.3, size=n)
+    raise ValueError("make_regime_problem: cannot draw distinct columns")
+
+
+def regime_scales(q, rng):
+    """s_k of Y[:, k] *= 10^s_k: uniform in [-4, 4], with both ends next to each other in the first trait tile and in the
+    last (ragged) one."""
+    s = rng.uniform(-4.0, 4.0, size=q)
+    t_last = REGIME_BLOCK * ((q - 1) // REGIME_BLOCK)
+    if q - t_last < 2 or t_last == 0:
+        raise ValueError("make_regime_problem: q needs a full trait tile and a last tile of at least two traits")
+    s[1], s[14] = -4.0, 4.0
+    s[q - 2], s[q - 1] = 4.0, -4.0
+    return s
+
+
+def make_regime_problem(n, p, q, regime, na_frac=0.0, hyper="auto", seed=31, init_seed=456, p0=(5, 25)):
+    """A problem in the form of make_problem whose inputs leave what make_problem always gives (independent common SNPs, traits
+    of variance about 1, hyper-parameters and init constant over the traits).  regime: a set of
+      "ld"     genotypes from haplotype copying with per-SNP flip probabilities in LD_RHO; the first SNP of every 16-SNP block
+               copies its left neighbour with LD_BORDER_RHO, so r^2 >= 0.95 straddles the block borders (and every border of
+               chained segments, which are block borders); the active SNPs include such a pair, 47 and 48;
+      "rare"   every 5th column (4, 9, ...) has 1, 2 or 3 heterozygous carriers; column 79 is the last of its block; with
+               na_frac > 0 all carriers of three of them -- 79 among them -- are missing in one trait each, the traits in
+               different trait tiles (as far as q has tiles);
+      "scale"  Y[:, k] *= 10^s_k, s_k from regime_scales.
+    hyper = "per_trait": set_hyper with eta_k ~ U(0.5, 20), kappa_k = v_k U(0.2, 5) (v_k: the trait's variance), n0_k = the
+    automatic n0 + U(-1.5, 1.5), nu = 0.5, rho = 3, t02 = 2.5 x the automatic one, and list_init["tau_vb"] = U(0.5, 2) / v_k:
+    every q-vector distinct in every entry.  Extra keys of the result: carriers, dropped = [(SNP, trait)], active, scales."""
+    regime = frozenset(regime)
+    if not regime <= set(REGIMES):
+        raise ValueError(f"regime must be a subset of {REGIMES}")
+    if hyper not in ("auto", "per_trait"):
+        raise ValueError("hyper must be 'auto' or 'per_trait'")
+    if p <= 80:
+        raise ValueError("make_regime_problem: p must exceed 80 (the rare column 79, the active pair 47 / 48)")
+    rng = np.random.default_rng(seed)
+    G, carriers = _regime_genotypes(n, p, regime, rng)
+    # effects: the neighbours 47 and 48 (in LD they share their signal, across a block border), a rare SNP, and five others
+    others = [j for j in rng.permutation(p) if j not in (47, 48, 79) and j not in carriers][:5]
+    active = np.sort(np.array([47, 48, 79 if "rare" in regime else 80] + others))
+    sub = rng.random((active.size, q)) < 0.3
+    beta = np.where(sub, rng.normal(size=sub.shape), 0.0)
+    Gs = (G - G.mean(0)) / G.std(0, ddof=1)
+    Y = rng.normal(size=(n, q)) + Gs[:, active] @ (beta * 0.5)
+    scales = regime_scales(q, rng) if "scale" in regime else np.zeros(q)
+    Y = Y * 10.0 ** scales[None, :]
+    dropped = []
+    if na_frac > 0:
+        Y[rng.random((n, q)) < na_frac] = np.nan
+        if "rare" in regime:
+            nt = -(-q // REGIME_BLOCK)
+            snps = [79] + [j for j in sorted(carriers) if len(carriers[j]) == 3 and j != 79][:2]
+            for i, j in enumerate(snps):
+                k = min(q - 1, REGIME_BLOCK * (i % nt) + 3 + i)
+                Y[carriers[j], k] = np.nan
+                dropped.append((j, k))
+    X, Yc, bool_cst, bool_coll = prepare_oracle.prepare_xy(Y, G)
+    bool_rmvd_x = bool_cst.copy()
+    bool_rmvd_x[~bool_cst] = bool_coll
+    pp = X.shape[1]
+    auto = H.auto_set_hyper_(Yc, pp, p0)
+    li = H.prepare_list_init_(None, Yc, pp, p0, bool_rmvd_x, q, init_seed)
+    if hyper == "per_trait":
+        v = np.nanvar(Yc, axis=0, ddof=1)
+        hr = np.random.default_rng(seed + 1000)
+        lh = H.set_hyper(q, p, eta=hr.uniform(0.5, 20.0, size=q), kappa=v * hr.uniform(0.2, 5.0, size=q),
+                         n0=auto["n0"] + hr.uniform(-1.5, 1.5, size=q), nu=0.5, rho=3.0, t02=2.5 * auto["t02"])
+        lh = H.prepare_list_hyper_(lh, Yc, pp, p0, bool_rmvd_x)
+        li = H.ListInit(li)
+        li.cls = "out_init"
+        li["tau_vb"] = hr.uniform(0.5, 2.0, size=q) / v
+    else:
+        lh = H.prepare_list_hyper_(None, Yc, pp, p0, bool_rmvd_x)
+    return dict(X=X, Y=Yc, list_hyper=lh, list_init=li, truth=dict(X=G, Y=Y, beta=beta), n=n, p=pp, q=q, p_drawn=p,
+                carriers=carriers, dropped=dropped, active=active, scales=scales, regime=regime, hyper=hyper)
+
+
 def operator_inputs(p, q, n=60, seed=0, mis=False, c=1.0):
     """Random but well-formed inputs of coreDualLoop / coreDualMisLoop (R layout)."""
     rng = np.random.default_rng(seed)
