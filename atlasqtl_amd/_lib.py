@@ -57,6 +57,11 @@ class AqPrepLd(C.Structure):
     _fields_ = [("window", C.c_int32), ("r2", C.c_double), ("group", ip), ("pos", C.POINTER(C.c_int64)), ("window_bp", C.c_int64)]
 
 
+class AqGrmPlan(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("tiles_per_edge", C.c_int32), ("n_tiles", C.c_int32), ("splits", C.c_int32),
+                ("chunk", C.c_int32), ("chunks_per_split", C.c_int32), ("scratch_bytes", C.c_int64), ("k_bytes", C.c_int64)]
+
+
 class AqVbMultiOut(C.Structure):
     _fields_ = [
         ("beta_vb", dp), ("gam_vb", dp), ("mu_beta_vb", dp), ("theta_vb", dp), ("zeta_vb", dp), ("lam2_inv_vb", dp),
@@ -152,6 +157,9 @@ SYMBOLS = {
     "aq_prep_ld_prune": (C.c_int, [C.c_void_p, C.POINTER(AqPrepLd)]),
     "aq_prep_ld_info": (C.c_int, [C.c_void_p, ip, C.POINTER(C.c_uint8), ip, dp]),
     "aq_prep_ld_band": (C.c_int, [C.c_void_p, C.c_int32, dp]),
+    "aq_prep_grm": (C.c_int, [C.c_void_p, dp, dp]),
+    "aq_grm_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(AqGrmPlan)]),
+    "aq_prep_grm_time": (C.c_int, [C.c_void_p, C.c_int32, dp, C.POINTER(AqGrmPlan)]),
 }
 
 _lib = None

@@ -14,7 +14,8 @@ import numpy as np
 from .core import atlasqtl_global_local_core_
 from .postproc import hotspot_sizes, six_numbers_host_, sparse_output_options, value_summary
 from .hyper_init import prepare_list_hyper_, prepare_list_init_
-from .prepare import check_annealing_, check_positive_, check_vector_, check_verbose_, prepare_data_
+from .prepare import (check_annealing_, check_positive_, check_vector_, check_verbose_, covariates_with_genotype_pcs,
+                      prepare_data_)
 
 
 class AtlasqtlResult(dict):
@@ -64,7 +65,7 @@ def add_collinear_back_pairs_(assoc, rs_thres, theta_vb, initial_colnames_X, rmv
 def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, verbose=1, list_hyper=None,
              list_init=None, save_hyper=False, save_init=False, full_output=False, thinned_elbo_eval=True,
              checkpoint_path=None, trace_path=None, add_collinear_back=False, device=0, device_init=False,
-             sparse_output=None, covariates=None, ld_prune=None):
+             sparse_output=None, covariates=None, ld_prune=None, genotype_pcs=None):
     """R/atlasqtl.R:179-322.
 
     X: a float64 matrix, int8 dosages, or a plink.PlinkBed (a PLINK 1 .bed / .bim / .fam fileset, unpacked on the GPU): the
@@ -93,7 +94,14 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
     default) has a squared correlation above r2 with it.  The result then carries `rmvd_ld_x` (removed name -> the kept
     predictor that tags it, or None) and `ld_r2_x` (per predictor given, its r^2 with that predictor, NaN otherwise);
     `names_x` is the pruned list, and a list_hyper / list_init of the original p is cut accordingly.  Not with
-    add_collinear_back=True."""
+    add_collinear_back=True.
+
+    genotype_pcs = k or {"k": k, "ld_prune": None}: take the k leading genotype principal components of X on the GPU
+    (genotype_pcs(): the n x n relationship matrix of the standardised, unresidualised predictors, its eigenvectors on the
+    host) and append them to `covariates`.  1 <= k <= min(n - 2, 96 - d) with d user covariates; n <= 10240.  The option's own
+    "ld_prune" (the dict ld_prune= takes) thins only the matrix the PCs are taken from, the usual prune-then-PCA; the fit's
+    predictors are governed by ld_prune= alone.  X is prepared twice.  The result then carries `genotype_pcs` (n x k),
+    `pc_eigenvalues`, `pc_var_explained`, and `n_covariates` counts d + k."""
     if ld_prune is not None and add_collinear_back:
         raise ValueError("add_collinear_back=True cannot be combined with ld_prune: a predictor removed for LD is not a copy of "
                          "the predictor that tags it, and the add-back maps assume copies (they would hand it the tag's "
@@ -109,6 +117,9 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
                          "cannot reproduce.  Use the dense output.")
     check_verbose_(verbose)
     check_annealing_(anneal)
+    pcs = None
+    if genotype_pcs is not None:
+        covariates, pcs = covariates_with_genotype_pcs(Y, X, covariates, genotype_pcs, device)
     dat = prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path, covariates=covariates,
                         ld_prune=ld_prune)
     bool_rmvd_x = dat["bool_rmvd_x"]
@@ -143,6 +154,8 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
         res["genotype_counts"] = dat["genotype_counts"]
     if covariates is not None:
         res["n_covariates"], res["rmvd_cov_x"], res["cov_r2_x"] = dat["n_covariates"], dat["rmvd_cov_x"], dat["cov_r2_x"]
+    if pcs is not None:
+        res["genotype_pcs"], res["pc_eigenvalues"], res["pc_var_explained"] = pcs["pcs"], pcs["eigenvalues"], pcs["var_explained"]
     if ld_prune is not None:
         res["rmvd_ld_x"], res["ld_r2_x"] = dat["rmvd_ld_x"], dat["ld_r2_x"]
     names_snp = dat["names_x"]

@@ -15,6 +15,8 @@
 // X are formed as fp64 on the device, enter the fp64 pipeline unchanged and are freed once the compact matrix is written.
 // aq_prep_ld_prune thins the compact matrix of a finished handle for linkage disequilibrium (aq_ld_kernels.h): the banded
 // correlation matrix on the f64 matrix pipe, thresholded into bits, a first-one-wins scan, and a gather of the kept columns.
+// aq_prep_grm forms the n x n genetic relationship matrix Xs Xs' / p1 of a finished handle's current matrix on the same pipe
+// (aq_grm_kernels.h, planned by aq_grm_plan.h) and copies it to the host.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <memory>
@@ -63,6 +65,7 @@ __device__ __forceinline__ double aq_block_sum(double v, double *sh) {
 
 #include "aq_cov_kernels.h"   // aq_k_cov_residualise, aq_k_cov_residualise_y
 #include "aq_ld_kernels.h"    // aq_k_ld_band, aq_k_ld_scan, aq_k_ld_tag_r2, aq_k_ld_gather
+#include "aq_grm_kernels.h"   // aq_k_grm_partial, aq_k_grm_reduce; aq_grm_make_plan
 
 // one workgroup per column: mean (sum / n, then one refinement pass as R's long-double colMeans would give), the n - 1
 // standard deviation of the centred values, and whether the column is constant
@@ -805,6 +808,109 @@ extern "C" int aq_prep_ld_band(aq_prep_handle h, int32_t window, double *r_band)
                      (const int32_t *)nullptr, (const long long *)nullptr, 0ll, dband.get(), (unsigned long long *)nullptr, 0);
   AQ_HIP(hipGetLastError());
   AQ_HIP(hipMemcpy(r_band, dband.get(), len * sizeof(double), hipMemcpyDeviceToHost));
+  return AQ_OK;
+}
+
+// ---- the genetic relationship matrix of a finished handle (include/atlasqtl_hip.h, aq_prep_grm; kernels in aq_grm_kernels.h) ----
+extern "C" int aq_grm_plan_query(int32_t n, int32_t p1, int32_t ncu, int64_t free_bytes, aq_grm_plan *out) {
+  if (!out) return aq_fail(AQ_ERR_ARG, "aq_grm_plan_query: NULL argument");
+  *out = aq_grm_plan{};
+  std::string err;
+  const int rc = aq_grm_make_plan(n, p1, ncu, (long long)free_bytes, 0, "aq_grm_plan_query", out, &err);
+  return rc == AQ_OK ? AQ_OK : aq_fail(rc, err);
+}
+
+template <int T, bool A16>
+static void aq_grm_launch_partial(const aq_grm_plan &pl, const double *Xs, int n, int p1, double *scratch) {
+  hipLaunchKernelGGL((aq_k_grm_partial<T, A16>), dim3((unsigned)pl.n_tiles, (unsigned)pl.splits), dim3(256), 0, 0, Xs, n, p1, pl.splits,
+                     pl.chunks_per_split, scratch);
+}
+
+// the two kernels on the handle's current matrix: K (n x n) in dK, the partial tiles in scratch.  Asynchronous.
+static int aq_grm_launch(aq_prep *h, const aq_grm_plan &pl, double *scratch, double *dK) {
+  const bool a16 = (h->n & 1) == 0;            // even n: every column starts at a multiple of 16 bytes
+  auto launch = pl.tile == 128 ? (a16 ? aq_grm_launch_partial<128, true> : aq_grm_launch_partial<128, false>)
+                               : (a16 ? aq_grm_launch_partial<64, true> : aq_grm_launch_partial<64, false>);
+  launch(pl, h->Xs.get(), h->n, h->p_kept, scratch);
+  const int nb = pl.tile / 16;
+  hipLaunchKernelGGL(aq_k_grm_reduce, dim3((unsigned)pl.n_tiles, (unsigned)(nb * nb)), dim3(256), 0, 0, scratch, pl.tile, h->n, h->p_kept,
+                     pl.splits, dK);
+  AQ_HIP(hipGetLastError());
+  return AQ_OK;
+}
+
+// the plan of a handle on its device: CU count and free memory from the runtime, AQ_GRM_SPLITS from the environment
+static int aq_grm_plan_for(aq_prep *h, const char *who, aq_grm_plan *pl) {
+  hipDeviceProp_t prop;
+  size_t free_b = 0, tot_b = 0;
+  AQ_HIP(hipGetDeviceProperties(&prop, h->device));
+  AQ_HIP(hipMemGetInfo(&free_b, &tot_b));
+  int force = 0;
+  if (const char *e = getenv("AQ_GRM_SPLITS")) {   // test hook: that many splits whatever p1 is
+    force = atoi(e);
+    if (force < 1) return aq_fail(AQ_ERR_ARG, std::string(who) + ": AQ_GRM_SPLITS must lie in [1, " + std::to_string(AQ_GRM_MAX_SPLITS) + "]");
+  }
+  std::string err;
+  const int rc = aq_grm_make_plan(h->n, h->p_kept, prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256, (long long)free_b, force,
+                                  who, pl, &err);
+  return rc == AQ_OK ? AQ_OK : aq_fail(rc, err);
+}
+
+extern "C" int aq_prep_grm(aq_prep_handle h, double *K_out, double *trace_out) {
+  if (!h) return aq_fail(AQ_ERR_ARG, "aq_prep_grm: NULL handle");
+  if (!K_out) return aq_fail(AQ_ERR_ARG, "aq_prep_grm: NULL output");
+  std::string err;
+  if (aq_grm_check_n(h->n, "aq_prep_grm", &err) != AQ_OK) return aq_fail(AQ_ERR_UNSUPPORTED, err);
+  AQ_TRY(aq_need_device(h->device));
+  AQ_TRY(aq_ld_need_layout("aq_prep_grm"));
+  const size_t n = (size_t)h->n;
+  aq_grm_plan pl{};
+  AQ_TRY(aq_grm_plan_for(h, "aq_prep_grm", &pl));
+  AqDev<double> dK, scratch;
+  AQ_TRY(dK.alloc(n * n));
+  AQ_TRY(scratch.alloc((size_t)pl.scratch_bytes / sizeof(double)));
+  AQ_TRY(aq_grm_launch(h, pl, scratch.get(), dK.get()));
+  AQ_HIP(hipMemcpy(K_out, dK.get(), n * n * sizeof(double), hipMemcpyDeviceToHost));
+  if (trace_out) {                             // the diagonal as returned, added in index order
+    double tr = 0.0;
+    for (size_t i = 0; i < n; i++) tr += K_out[i * n + i];
+    *trace_out = tr;
+  }
+  return AQ_OK;
+}
+
+// Timing hook of aq_prep_grm: the two kernels alone, `reps` times between two events, without the copy to the host.
+extern "C" int aq_prep_grm_time(aq_prep_handle h, int32_t reps, double *ms_per_call, aq_grm_plan *plan_out) {
+  if (!h || !ms_per_call) return aq_fail(AQ_ERR_ARG, "aq_prep_grm_time: NULL argument");
+  if (reps < 1) return aq_fail(AQ_ERR_ARG, "aq_prep_grm_time: reps >= 1 required");
+  std::string err;
+  if (aq_grm_check_n(h->n, "aq_prep_grm_time", &err) != AQ_OK) return aq_fail(AQ_ERR_UNSUPPORTED, err);
+  AQ_TRY(aq_need_device(h->device));
+  AQ_TRY(aq_ld_need_layout("aq_prep_grm_time"));
+  aq_grm_plan pl{};
+  AQ_TRY(aq_grm_plan_for(h, "aq_prep_grm_time", &pl));
+  if (plan_out) *plan_out = pl;
+  AqDev<double> dK, scratch;
+  AQ_TRY(dK.alloc((size_t)h->n * h->n));
+  AQ_TRY(scratch.alloc((size_t)pl.scratch_bytes / sizeof(double)));
+  AQ_TRY(aq_grm_launch(h, pl, scratch.get(), dK.get()));   // warm-up
+  AQ_HIP(hipDeviceSynchronize());
+  struct Events {                              // both destroyed on every way out
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t ev : e)
+        if (ev) hipEventDestroy(ev);
+    }
+  } ev;
+  AQ_HIP(hipEventCreate(&ev.e[0]));
+  AQ_HIP(hipEventCreate(&ev.e[1]));
+  AQ_HIP(hipEventRecord(ev.e[0], 0));
+  for (int r = 0; r < reps; r++) AQ_TRY(aq_grm_launch(h, pl, scratch.get(), dK.get()));
+  AQ_HIP(hipEventRecord(ev.e[1], 0));
+  AQ_HIP(hipEventSynchronize(ev.e[1]));
+  float ms = 0.f;
+  AQ_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  *ms_per_call = (double)ms / reps;
   return AQ_OK;
 }
 

@@ -7,7 +7,8 @@ wording so tests read like the reference's own.  The argument checks run on the 
 the O(n p) work itself -- scale(X), the removal of constant and duplicated columns,
 the centring of Y -- runs on the GPU (aq_prepare_data) and X stays there.  Covariates, which the reference
 does not take, are regressed out of X and Y there as well (aq_prepare_data_cov), and the compact matrix can be pruned for
-linkage disequilibrium there before the fit (aq_prep_ld_prune).
+linkage disequilibrium there before the fit (aq_prep_ld_prune).  The genetic relationship matrix of the prepared matrix is
+formed there too (aq_prep_grm); its leading eigenvectors, the genotype principal components, are taken here on the host.
 """
 from __future__ import annotations
 
@@ -142,6 +143,15 @@ class PreparedData:
         _lib.check(_lib.lib().aq_prep_ld_band(self.handle, int(window), _lib.as_dp(out)), "aq_prep_ld_band")
         return out
 
+    def grm(self, return_trace=False):
+        """The genetic relationship matrix Xs Xs' / p of the matrix as it stands, n x n and exactly symmetric: aq_prep_grm.
+        return_trace: also the sum of its diagonal, added in index order."""
+        import ctypes as C
+        out = np.empty((self.n, self.n), order="F")
+        tr = C.c_double(0.0)
+        _lib.check(_lib.lib().aq_prep_grm(self.handle, _lib.as_dp(out), C.byref(tr)), "aq_prep_grm")
+        return (out, float(tr.value)) if return_trace else out
+
     def close(self):
         if self.handle is not None:
             _lib.lib().aq_prep_destroy(self.handle)
@@ -171,6 +181,8 @@ def _covariates_arg(covariates, n):
     return cov, Z
 
 
+GRM_MAX_N = 10240             # AQ_GRM_MAX_N of csrc/aq_grm_plan.h
+COV_MAX_D = 96                # AQ_COV_MAX_D: covariates that aq_prepare_data_cov takes
 LD_PRUNE_DEFAULTS = {"r2": 0.8, "window": 500, "window_bp": None, "groups": None, "positions": None}
 LD_MAX_WINDOW = 4096          # AQ_LD_MAX_WINDOW of csrc/aq_ld_kernels.h
 
@@ -429,3 +441,125 @@ def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_p
                 n_covariates=prep.n_cov, cov_r2_x=prep.cov_r2, rmvd_ld_x=rmvd_ld_x, ld_r2_x=prep.ld_r2,
                 rmvd_cov_x=[names_x[j] for j in np.where(prep.cov_absorbed)[0]] if prep.n_cov and prep.cov_absorbed.any() else None,
                 names_x=[nm for nm, b in zip(names_x, bool_rmvd_x) if not b], names_y=list(names_y))
+
+
+# ---- genotype principal components: the GRM on the device (aq_prep_grm), its leading eigenvectors on the host ----
+def pc_sign_(V):
+    """Each column of V with the sign that makes its entry of largest magnitude positive; on a tie the first such entry
+    decides.  Equal inputs therefore give equal bits."""
+    V = np.array(V, dtype=np.float64, order="F", ndmin=2)
+    for c in range(V.shape[1]):
+        if V[np.argmax(np.abs(V[:, c])), c] < 0:                 # argmax returns the first of equal magnitudes
+            V[:, c] = -V[:, c]
+    return V
+
+
+def pcs_from_grm_(K, k, trace=None):
+    """The k leading eigenpairs of the symmetric matrix K (numpy.linalg.eigh: n^3 on the host, against the n^2 p of the GRM on
+    the device with p >> n): dict(pcs n x k with unit-norm columns signed by pc_sign_, eigenvalues descending, var_explained =
+    eigenvalue / trace)."""
+    w, V = np.linalg.eigh(K)
+    top = np.arange(w.size - 1, w.size - 1 - int(k), -1)
+    lam = w[top]
+    tr = float(np.trace(K)) if trace is None else float(trace)
+    return dict(pcs=pc_sign_(V[:, top]), eigenvalues=lam, var_explained=lam / tr)
+
+
+def _n_of(X):
+    from .plink import PlinkBed
+    if isinstance(X, PlinkBed):
+        return X.n
+    if np.ndim(X) != 2 or np.shape(X)[0] < 1:
+        raise AtlasqtlError("X must be a non-empty a numeric matrix, finite without missing value.")
+    return int(np.shape(X)[0])
+
+
+def _check_grm_n(n, what):
+    if n > GRM_MAX_N:
+        raise AtlasqtlError(f"{what}: n = {n} samples given, at most {GRM_MAX_N} are supported (the n x n relationship matrix "
+                            "is decomposed on the host).")
+
+
+def _check_pc_count(k, n, d, what):
+    if not _is_whole(k):
+        raise AtlasqtlError(f"{what}: k must be a whole number, not {k!r}.")
+    kmax = min(n - 2, COV_MAX_D - d)
+    if not (1 <= int(k) <= kmax):
+        raise AtlasqtlError(f"{what}: k must lie in [1, {kmax}] = [1, min(n - 2, {COV_MAX_D} - d)] with n = {n} samples and "
+                            f"d = {d} covariates, not {k!r}.")
+    return int(k)
+
+
+def genotype_pcs_options(genotype_pcs, n, d=0):
+    """The `genotype_pcs` argument of atlasqtl() checked on the host: a whole number k or a dict with the keys 'k' and
+    'ld_prune' (None, or the dict ld_prune= takes), with 1 <= k <= min(n - 2, 96 - d) for n samples and d user covariates, and
+    n <= 10240.  Returns {"k": k, "ld_prune": dict or None}."""
+    if isinstance(genotype_pcs, dict):
+        if "k" not in genotype_pcs or set(genotype_pcs) - {"k", "ld_prune"}:
+            raise AtlasqtlError("genotype_pcs must be None, a whole number k or a dict with the key 'k' and, optionally, 'ld_prune'.")
+        o = {"k": genotype_pcs["k"], "ld_prune": genotype_pcs.get("ld_prune")}
+    elif _is_whole(genotype_pcs):
+        o = {"k": genotype_pcs, "ld_prune": None}
+    else:
+        raise AtlasqtlError("genotype_pcs must be None, a whole number k or a dict with the key 'k' and, optionally, 'ld_prune'.")
+    _check_grm_n(n, "genotype_pcs")
+    o["k"] = _check_pc_count(o["k"], n, d, "genotype_pcs")
+    if o["ld_prune"] is not None:
+        try:
+            ld_prune_options(o["ld_prune"])
+        except AtlasqtlError as e:
+            raise AtlasqtlError(f"genotype_pcs: {e}") from None
+    return o
+
+
+def _grm_of(X, device, covariates, ld_prune):
+    """(K, trace K, p1) of X as prepare_on_device prepares it, with a one-column dummy Y (all observed, so it passes the
+    missingness guards; all zero, so it is zero after centring or regression on any covariates).  The handle is closed."""
+    n = _n_of(X)
+    _check_grm_n(n, "genotype_grm")
+    prep = prepare_on_device(np.zeros((n, 1), order="F"), X, device, covariates, ld_prune)[0]
+    try:
+        K, tr = prep.grm(return_trace=True)
+        return K, tr, prep.p
+    finally:
+        prep.close()
+
+
+def genotype_grm(X, device=0, covariates=None, ld_prune=None):
+    """The n x n genetic relationship matrix K = Xs Xs' / p1 of X (float64, int8 dosages or a plink.PlinkBed) over the p1
+    standardised columns that prepare_on_device keeps -- after constant and duplicate removal, with `covariates` on the
+    residuals, with `ld_prune` on the pruned set -- formed on the GPU (aq_prep_grm).  Exactly symmetric; n <= 10240."""
+    return _grm_of(X, device, covariates, ld_prune)[0]
+
+
+def genotype_pcs(X, k, device=0, covariates=None, ld_prune=None):
+    """The k leading principal components of the genotypes X: eigenvectors of genotype_grm(X, ...).  Returns dict(pcs n x k,
+    unit norm, each signed so that its entry of largest magnitude is positive; eigenvalues (k, descending); var_explained =
+    eigenvalue / trace K; p_used = p1, the predictors K was formed over).  Every column of Xs is centred, so the PCs are
+    orthogonal to the intercept.  1 <= k <= n - 2 - d with d covariates: the residuals on them and the intercept span at most
+    n - 1 - d dimensions, and a PC beyond that would be an eigenvector of rounding noise."""
+    n = _n_of(X)
+    _check_grm_n(n, "genotype_pcs")
+    Z = _covariates_arg(covariates, n)[1]
+    d = 0 if Z is None else Z.shape[1]
+    if not _is_whole(k):
+        raise AtlasqtlError(f"genotype_pcs: k must be a whole number, not {k!r}.")
+    if not (1 <= int(k) <= n - 2 - d):
+        raise AtlasqtlError(f"genotype_pcs: k must lie in [1, {n - 2 - d}] = [1, n - 2 - d] with n = {n} samples and d = {d} "
+                            f"covariates regressed out of the genotypes, not {k!r}.")
+    K, tr, p1 = _grm_of(X, device, covariates, ld_prune)
+    return dict(pcs_from_grm_(K, int(k), tr), p_used=int(p1))
+
+
+def covariates_with_genotype_pcs(Y, X, covariates, genotype_pcs_arg, device=0):
+    """atlasqtl(genotype_pcs=): the PCs of the unresidualised standardised genotypes (pruned by the option's own ld_prune, if
+    any) appended to the user's covariates.  Every check runs before the first device call.  Returns ([Z, PCs], the dict of
+    genotype_pcs())."""
+    n = _n_of(X)
+    if np.ndim(Y) != 2 or np.shape(Y)[0] != n:
+        raise AtlasqtlError("X and Y must have the same number of samples.")
+    Z = _covariates_arg(covariates, n)[1]
+    o = genotype_pcs_options(genotype_pcs_arg, n, 0 if Z is None else Z.shape[1])
+    _ld_arg(o["ld_prune"], X)                                    # lengths of groups / positions against X
+    pcs = genotype_pcs(X, o["k"], device, ld_prune=o["ld_prune"])
+    return (pcs["pcs"] if Z is None else np.hstack([Z, pcs["pcs"]])), pcs

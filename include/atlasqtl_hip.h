@@ -515,6 +515,44 @@ int aq_prep_ld_prune(aq_prep_handle h, const aq_prep_ld *ld);
 int aq_prep_ld_info(aq_prep_handle h, int32_t *p_kept, uint8_t *bool_ld, int32_t *ld_of, double *ld_r2);
 int aq_prep_ld_band(aq_prep_handle h, int32_t window, double *r_band);
 
+/* ------------------------------------------------------------------------------------------
+ * Genetic relationship matrix (GRM) of a handle that any of the four aq_prepare_data* entries returned: the n x n matrix
+ *   K[a, b] = (sum_j Xs[a, j] Xs[b, j]) / p1
+ * over all p1 columns of the handle's CURRENT matrix Xs (what aq_prep_x_device shows: after constant and duplicate removal,
+ * with covariates the residuals, after aq_prep_ld_prune the kept columns), every column with mean 0 and sum of squares
+ * n - 1.  Its leading eigenvectors are the genotype principal components that a QTL analysis passes as covariates; they are
+ * taken on the host (atlasqtl_amd.genotype_pcs).  Every column is centred, so K 1 = 0 up to rounding and trace K = n - 1.
+ * The product is formed on the f64 matrix pipe (n^2 p1 useful flop): one triangle of output tiles, the predictors split over
+ * several workgroups per tile whose partial tiles a second kernel adds in a fixed order -- no floating-point atomics, so two
+ * calls on one handle return the same bits -- and both halves of K are written from the same registers, so K equals its
+ * transpose exactly.  Every entry is within (p1 + 2) 2^-53 (sum_j |Xs[a, j] Xs[b, j]|) / p1 of the exact value.
+ *   aq_prep_grm         K_out: n x n column-major, host.  trace_out (may be NULL): the diagonal of K_out added in index order.
+ *                       The handle is not changed.
+ *   aq_grm_plan_query   the launch plan without a device, a pure function of its arguments: tile edge, tiles of one triangle
+ *                       (tile t = ti (ti + 1) / 2 + tj, ti >= tj), splits, predictors per chunk and chunks per split; the
+ *                       grid is n_tiles x splits workgroups.  splits = 1 when the tiles alone give two workgroups per CU;
+ *                       k_bytes + scratch_bytes <= free_bytes.  The environment variable AQ_GRM_SPLITS (1 ... 64; tests)
+ *                       forces the splits of aq_prep_grm; the query does not read it.
+ *   aq_prep_grm_time    measurement: the two kernels `reps` times between two events after one warm-up, without the copy to
+ *                       the host; ms_per_call and, if not NULL, the plan used.
+ * n > 10240 is AQ_ERR_UNSUPPORTED (K is 0.84 GB there and its eigen-decomposition runs on the host); a NULL handle or output
+ * is AQ_ERR_ARG; both come before any device call.  A plan that does not fit the free memory is AQ_ERR_DEVICE.  Every error
+ * names the entry that was called (aq_prep_grm, aq_grm_plan_query, aq_prep_grm_time) in aq_last_error().
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_grm_plan {
+  int32_t tile;               /* edge of an output tile: 64 or 128 samples                   */
+  int32_t tiles_per_edge;     /* ceil(n / tile)                                              */
+  int32_t n_tiles;            /* tiles of one triangle: tiles_per_edge (tiles_per_edge + 1) / 2 */
+  int32_t splits;             /* workgroups per tile, each with its own predictors           */
+  int32_t chunk;              /* predictors staged per step                                  */
+  int32_t chunks_per_split;   /* split s owns chunks [s chunks_per_split, (s + 1) chunks_per_split) */
+  int64_t scratch_bytes;      /* the partial tiles: splits n_tiles tile^2 doubles            */
+  int64_t k_bytes;            /* K on the device: n^2 doubles                                */
+} aq_grm_plan;
+int aq_prep_grm(aq_prep_handle h, double *K_out, double *trace_out);
+int aq_grm_plan_query(int32_t n, int32_t p1, int32_t ncu, int64_t free_bytes, aq_grm_plan *out);
+int aq_prep_grm_time(aq_prep_handle h, int32_t reps, double *ms_per_call, aq_grm_plan *plan_out);
+
 #ifdef __cplusplus
 }
 #endif
