@@ -62,6 +62,12 @@ class AqGrmPlan(C.Structure):
                 ("chunk", C.c_int32), ("chunks_per_split", C.c_int32), ("scratch_bytes", C.c_int64), ("k_bytes", C.c_int64)]
 
 
+class AqPcsPlan(C.Structure):
+    _fields_ = [("lp", C.c_int32), ("panel", C.c_int32), ("n_panels", C.c_int32), ("sample_chunk", C.c_int32), ("n_pad", C.c_int32),
+                ("tile", C.c_int32), ("n_tiles", C.c_int32), ("splits", C.c_int32), ("chunk", C.c_int32),
+                ("chunks_per_split", C.c_int32), ("t_bytes", C.c_int64), ("scratch_bytes", C.c_int64), ("io_bytes", C.c_int64)]
+
+
 class AqVbMultiOut(C.Structure):
     _fields_ = [
         ("beta_vb", dp), ("gam_vb", dp), ("mu_beta_vb", dp), ("theta_vb", dp), ("zeta_vb", dp), ("lam2_inv_vb", dp),
@@ -160,6 +166,9 @@ SYMBOLS = {
     "aq_prep_grm": (C.c_int, [C.c_void_p, dp, dp]),
     "aq_grm_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(AqGrmPlan)]),
     "aq_prep_grm_time": (C.c_int, [C.c_void_p, C.c_int32, dp, C.POINTER(AqGrmPlan)]),
+    "aq_prep_grm_apply": (C.c_int, [C.c_void_p, dp, C.c_int32, dp, dp]),
+    "aq_pcs_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(AqPcsPlan)]),
+    "aq_prep_grm_apply_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, dp, C.POINTER(AqPcsPlan)]),
 }
 
 _lib = None

@@ -98,10 +98,12 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
 
     genotype_pcs = k or {"k": k, "ld_prune": None}: take the k leading genotype principal components of X on the GPU
     (genotype_pcs(): the n x n relationship matrix of the standardised, unresidualised predictors, its eigenvectors on the
-    host) and append them to `covariates`.  1 <= k <= min(n - 2, 96 - d) with d user covariates; n <= 10240.  The option's own
+    host) and append them to `covariates`.  1 <= k <= min(n - 2, 96 - d) with d user covariates; n <= 10240 -- or, with
+    {"k": k, "solver": "subspace"} and optionally "oversample", "tol", "max_iter", "seed" (genotype_pcs()), by subspace
+    iteration on the GPU without the n x n matrix, for every n a fit takes.  The option's own
     "ld_prune" (the dict ld_prune= takes) thins only the matrix the PCs are taken from, the usual prune-then-PCA; the fit's
     predictors are governed by ld_prune= alone.  X is prepared twice.  The result then carries `genotype_pcs` (n x k),
-    `pc_eigenvalues`, `pc_var_explained`, and `n_covariates` counts d + k."""
+    `pc_eigenvalues`, `pc_var_explained`, `pc_solver`, `pc_iterations`, `pc_converged`, and `n_covariates` counts d + k."""
     if ld_prune is not None and add_collinear_back:
         raise ValueError("add_collinear_back=True cannot be combined with ld_prune: a predictor removed for LD is not a copy of "
                          "the predictor that tags it, and the add-back maps assume copies (they would hand it the tag's "
@@ -156,6 +158,7 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
         res["n_covariates"], res["rmvd_cov_x"], res["cov_r2_x"] = dat["n_covariates"], dat["rmvd_cov_x"], dat["cov_r2_x"]
     if pcs is not None:
         res["genotype_pcs"], res["pc_eigenvalues"], res["pc_var_explained"] = pcs["pcs"], pcs["eigenvalues"], pcs["var_explained"]
+        res["pc_solver"], res["pc_iterations"], res["pc_converged"] = pcs["solver"], pcs["iterations"], pcs["converged"]
     if ld_prune is not None:
         res["rmvd_ld_x"], res["ld_r2_x"] = dat["rmvd_ld_x"], dat["ld_r2_x"]
     names_snp = dat["names_x"]

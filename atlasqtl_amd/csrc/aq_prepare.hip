@@ -17,6 +17,8 @@
 // correlation matrix on the f64 matrix pipe, thresholded into bits, a first-one-wins scan, and a gather of the kept columns.
 // aq_prep_grm forms the n x n genetic relationship matrix Xs Xs' / p1 of a finished handle's current matrix on the same pipe
 // (aq_grm_kernels.h, planned by aq_grm_plan.h) and copies it to the host.
+// aq_prep_grm_apply applies that matrix to a block of vectors without forming it, Xs (Xs' Q) / p1 (aq_pcs_kernels.h, planned by
+// aq_pcs_plan.h): the step of subspace iteration for its leading eigenvectors, for any n a handle holds.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <memory>
@@ -66,6 +68,7 @@ __device__ __forceinline__ double aq_block_sum(double v, double *sh) {
 #include "aq_cov_kernels.h"   // aq_k_cov_residualise, aq_k_cov_residualise_y
 #include "aq_ld_kernels.h"    // aq_k_ld_band, aq_k_ld_scan, aq_k_ld_tag_r2, aq_k_ld_gather
 #include "aq_grm_kernels.h"   // aq_k_grm_partial, aq_k_grm_reduce; aq_grm_make_plan
+#include "aq_pcs_kernels.h"   // aq_k_pcs_pack_q, aq_k_pcs_xtq, aq_k_pcs_xt, aq_k_pcs_reduce, aq_k_pcs_colss; aq_pcs_make_plan
 
 // one workgroup per column: mean (sum / n, then one refinement pass as R's long-double colMeans would give), the n - 1
 // standard deviation of the centred values, and whether the column is constant
@@ -906,6 +909,153 @@ extern "C" int aq_prep_grm_time(aq_prep_handle h, int32_t reps, double *ms_per_c
   AQ_HIP(hipEventCreate(&ev.e[1]));
   AQ_HIP(hipEventRecord(ev.e[0], 0));
   for (int r = 0; r < reps; r++) AQ_TRY(aq_grm_launch(h, pl, scratch.get(), dK.get()));
+  AQ_HIP(hipEventRecord(ev.e[1], 0));
+  AQ_HIP(hipEventSynchronize(ev.e[1]));
+  float ms = 0.f;
+  AQ_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  *ms_per_call = (double)ms / reps;
+  return AQ_OK;
+}
+
+// ---- the relationship operator applied to a block of vectors (include/atlasqtl_hip.h, aq_prep_grm_apply; kernels in aq_pcs_kernels.h) ----
+extern "C" int aq_pcs_plan_query(int32_t n, int32_t p1, int32_t L, int32_t ncu, int64_t free_bytes, aq_pcs_plan *out) {
+  if (!out) return aq_fail(AQ_ERR_ARG, "aq_pcs_plan_query: NULL argument");
+  *out = aq_pcs_plan{};
+  std::string err;
+  const int rc = aq_pcs_make_plan(n, p1, L, ncu, (long long)free_bytes, 0, "aq_pcs_plan_query", out, &err);
+  return rc == AQ_OK ? AQ_OK : aq_fail(rc, err);
+}
+
+static int aq_pcs_check_l(int32_t L, const char *who) {
+  if (L < 1 || L > AQ_PCS_MAX_L)
+    return aq_fail(AQ_ERR_ARG, std::string(who) + ": L must lie in [1, " + std::to_string(AQ_PCS_MAX_L) + "], " + std::to_string(L) + " given");
+  return AQ_OK;
+}
+
+// the plan of a handle on its device: CU count and free memory from the runtime, AQ_PCS_SPLITS from the environment
+static int aq_pcs_plan_for(aq_prep *h, int L, const char *who, aq_pcs_plan *pl) {
+  hipDeviceProp_t prop;
+  size_t free_b = 0, tot_b = 0;
+  AQ_HIP(hipGetDeviceProperties(&prop, h->device));
+  AQ_HIP(hipMemGetInfo(&free_b, &tot_b));
+  int force = 0;
+  if (const char *e = getenv("AQ_PCS_SPLITS")) {   // test hook: that many splits of the second product whatever p1 is
+    force = atoi(e);
+    if (force < 1) return aq_fail(AQ_ERR_ARG, std::string(who) + ": AQ_PCS_SPLITS must lie in [1, " + std::to_string(AQ_PCS_MAX_SPLITS) + "]");
+  }
+  std::string err;
+  const int rc = aq_pcs_make_plan(h->n, h->p_kept, L, prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256, (long long)free_b,
+                                  force, who, pl, &err);
+  return rc == AQ_OK ? AQ_OK : aq_fail(rc, err);
+}
+
+// the device buffers of one application: Q and Z as the caller has them, Q packed, T and the partial tiles
+struct AqPcsBuf {
+  AqDev<double> Q, Qt, T, scratch, Z;
+  int alloc(const aq_pcs_plan &pl, int n, int L) {
+    AQ_TRY(Q.alloc((size_t)n * L));
+    AQ_TRY(Z.alloc((size_t)n * L));
+    AQ_TRY(Qt.alloc((size_t)pl.n_pad * pl.lp));
+    AQ_TRY(T.alloc((size_t)pl.t_bytes / sizeof(double)));
+    AQ_TRY(scratch.alloc((size_t)pl.scratch_bytes / sizeof(double)));
+    return AQ_OK;
+  }
+};
+
+template <int NL, bool A16>
+static void aq_pcs_launch_products(const aq_pcs_plan &pl, const double *Xs, int n, int p1, AqPcsBuf &b) {
+  hipLaunchKernelGGL((aq_k_pcs_xtq<NL, A16>), dim3((unsigned)pl.n_panels), dim3(256), 0, 0, Xs, n, p1, pl.n_pad, b.Qt.get(), b.T.get());
+  hipLaunchKernelGGL((aq_k_pcs_xt<NL, A16>), dim3((unsigned)pl.n_tiles, (unsigned)pl.splits), dim3(256), 0, 0, Xs, n, p1, pl.splits,
+                     pl.chunks_per_split, b.T.get(), b.scratch.get());
+}
+
+template <bool A16>
+static void aq_pcs_launch_width(int nl, const aq_pcs_plan &pl, const double *Xs, int n, int p1, AqPcsBuf &b) {
+  switch (nl) {                                // one instance per padded width lp = 16 nl
+    case 1: return aq_pcs_launch_products<1, A16>(pl, Xs, n, p1, b);
+    case 2: return aq_pcs_launch_products<2, A16>(pl, Xs, n, p1, b);
+    case 3: return aq_pcs_launch_products<3, A16>(pl, Xs, n, p1, b);
+    case 4: return aq_pcs_launch_products<4, A16>(pl, Xs, n, p1, b);
+    case 5: return aq_pcs_launch_products<5, A16>(pl, Xs, n, p1, b);
+    case 6: return aq_pcs_launch_products<6, A16>(pl, Xs, n, p1, b);
+    case 7: return aq_pcs_launch_products<7, A16>(pl, Xs, n, p1, b);
+    default: return aq_pcs_launch_products<8, A16>(pl, Xs, n, p1, b);
+  }
+}
+
+// the four kernels on the handle's current matrix: b.Q (n x L) -> b.Z (n x L).  Asynchronous.
+static int aq_pcs_launch(aq_prep *h, const aq_pcs_plan &pl, int L, AqPcsBuf &b) {
+  const int n = h->n, p1 = h->p_kept, nl = pl.lp / 16;
+  const long long cells = (long long)pl.n_pad * pl.lp;
+  hipLaunchKernelGGL(aq_k_pcs_pack_q, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, 0, b.Q.get(), n, L, pl.n_pad, pl.lp, b.Qt.get());
+  if ((n & 1) == 0)                            // even n: every column starts at a multiple of 16 bytes
+    aq_pcs_launch_width<true>(nl, pl, h->Xs.get(), n, p1, b);
+  else
+    aq_pcs_launch_width<false>(nl, pl, h->Xs.get(), n, p1, b);
+  hipLaunchKernelGGL(aq_k_pcs_reduce, dim3((unsigned)pl.n_tiles, (unsigned)((L + 3) / 4)), dim3(256), 0, 0, b.scratch.get(), n, p1, L, pl.lp,
+                     pl.splits, b.Z.get());
+  AQ_HIP(hipGetLastError());
+  return AQ_OK;
+}
+
+extern "C" int aq_prep_grm_apply(aq_prep_handle h, const double *Q, int32_t L, double *Z_out, double *trace_out) {
+  if (!h) return aq_fail(AQ_ERR_ARG, "aq_prep_grm_apply: NULL handle");
+  if (!Q || !Z_out) return aq_fail(AQ_ERR_ARG, "aq_prep_grm_apply: NULL argument");
+  AQ_TRY(aq_pcs_check_l(L, "aq_prep_grm_apply"));
+  AQ_TRY(aq_need_device(h->device));
+  AQ_TRY(aq_ld_need_layout("aq_prep_grm_apply"));
+  const size_t n = (size_t)h->n, p1 = (size_t)h->p_kept;
+  aq_pcs_plan pl{};
+  AQ_TRY(aq_pcs_plan_for(h, L, "aq_prep_grm_apply", &pl));
+  AqPcsBuf b;
+  AQ_TRY(b.alloc(pl, h->n, L));
+  AQ_HIP(hipMemcpy(b.Q.get(), Q, n * L * sizeof(double), hipMemcpyHostToDevice));
+  AQ_TRY(aq_pcs_launch(h, pl, L, b));
+  AQ_HIP(hipMemcpy(Z_out, b.Z.get(), n * L * sizeof(double), hipMemcpyDeviceToHost));
+  if (trace_out) {                             // the columns' sums of squares, added in index order
+    AqDev<double> dss;
+    AQ_TRY(dss.alloc(p1));
+    hipLaunchKernelGGL(aq_k_pcs_colss, dim3((unsigned)p1), dim3(256), 0, 0, h->Xs.get(), h->n, dss.get());
+    AQ_HIP(hipGetLastError());
+    std::vector<double> ss(p1);
+    AQ_HIP(hipMemcpy(ss.data(), dss.get(), p1 * sizeof(double), hipMemcpyDeviceToHost));
+    double tr = 0.0;
+    for (size_t j = 0; j < p1; j++) tr += ss[j];
+    *trace_out = tr / (double)p1;
+  }
+  return AQ_OK;
+}
+
+// Timing hook of aq_prep_grm_apply: the four kernels alone on a block of ones, `reps` times between two events, without the
+// copies from and to the host.
+extern "C" int aq_prep_grm_apply_time(aq_prep_handle h, int32_t L, int32_t reps, double *ms_per_call, aq_pcs_plan *plan_out) {
+  if (!h || !ms_per_call) return aq_fail(AQ_ERR_ARG, "aq_prep_grm_apply_time: NULL argument");
+  if (reps < 1) return aq_fail(AQ_ERR_ARG, "aq_prep_grm_apply_time: reps >= 1 required");
+  AQ_TRY(aq_pcs_check_l(L, "aq_prep_grm_apply_time"));
+  AQ_TRY(aq_need_device(h->device));
+  AQ_TRY(aq_ld_need_layout("aq_prep_grm_apply_time"));
+  aq_pcs_plan pl{};
+  AQ_TRY(aq_pcs_plan_for(h, L, "aq_prep_grm_apply_time", &pl));
+  if (plan_out) *plan_out = pl;
+  AqPcsBuf b;
+  AQ_TRY(b.alloc(pl, h->n, L));
+  {
+    std::vector<double> ones((size_t)h->n * L, 1.0);
+    AQ_HIP(hipMemcpy(b.Q.get(), ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  AQ_TRY(aq_pcs_launch(h, pl, L, b));          // warm-up
+  AQ_HIP(hipDeviceSynchronize());
+  struct Events {                              // both destroyed on every way out
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t ev : e)
+        if (ev) hipEventDestroy(ev);
+    }
+  } ev;
+  AQ_HIP(hipEventCreate(&ev.e[0]));
+  AQ_HIP(hipEventCreate(&ev.e[1]));
+  AQ_HIP(hipEventRecord(ev.e[0], 0));
+  for (int r = 0; r < reps; r++) AQ_TRY(aq_pcs_launch(h, pl, L, b));
   AQ_HIP(hipEventRecord(ev.e[1], 0));
   AQ_HIP(hipEventSynchronize(ev.e[1]));
   float ms = 0.f;

@@ -8,7 +8,9 @@ the O(n p) work itself -- scale(X), the removal of constant and duplicated colum
 the centring of Y -- runs on the GPU (aq_prepare_data) and X stays there.  Covariates, which the reference
 does not take, are regressed out of X and Y there as well (aq_prepare_data_cov), and the compact matrix can be pruned for
 linkage disequilibrium there before the fit (aq_prep_ld_prune).  The genetic relationship matrix of the prepared matrix is
-formed there too (aq_prep_grm); its leading eigenvectors, the genotype principal components, are taken here on the host.
+formed there too (aq_prep_grm); its leading eigenvectors, the genotype principal components, are taken here on the host --
+or, with solver="subspace", by subspace iteration whose operator K Q = Xs (Xs' Q) / p1 runs there (aq_prep_grm_apply) without
+K ever being formed, for any n the fit takes.
 """
 from __future__ import annotations
 
@@ -152,6 +154,19 @@ class PreparedData:
         _lib.check(_lib.lib().aq_prep_grm(self.handle, _lib.as_dp(out), C.byref(tr)), "aq_prep_grm")
         return (out, float(tr.value)) if return_trace else out
 
+    def grm_apply(self, Q, return_trace=False):
+        """Z = Xs (Xs' Q) / p of the matrix as it stands, n x L for Q n x L (1 <= L <= 128), without the n x n matrix:
+        aq_prep_grm_apply.  return_trace: also the trace of the relationship matrix, (sum of Xs^2) / p."""
+        import ctypes as C
+        Q = np.asfortranarray(Q, dtype=np.float64)
+        if Q.ndim != 2 or Q.shape[0] != self.n:
+            raise AtlasqtlError(f"grm_apply: Q must be n x L with n = {self.n} rows, not {Q.shape}.")
+        out = np.empty(Q.shape, order="F")
+        tr = C.c_double(0.0)
+        _lib.check(_lib.lib().aq_prep_grm_apply(self.handle, _lib.as_dp(Q), Q.shape[1], _lib.as_dp(out),
+                                                C.byref(tr) if return_trace else None), "aq_prep_grm_apply")
+        return (out, float(tr.value)) if return_trace else out
+
     def close(self):
         if self.handle is not None:
             _lib.lib().aq_prep_destroy(self.handle)
@@ -182,6 +197,10 @@ def _covariates_arg(covariates, n):
 
 
 GRM_MAX_N = 10240             # AQ_GRM_MAX_N of csrc/aq_grm_plan.h
+N_MAX = 82944                 # AQ_N_MAX of csrc/aq_plan_const.h: the samples a fit takes
+PCS_MAX_L = 128               # AQ_PCS_MAX_L of csrc/aq_pcs_plan.h: vectors per block of aq_prep_grm_apply
+PC_SOLVERS = ("eigh", "subspace")
+PC_SOLVER_DEFAULTS = {"solver": "eigh", "oversample": None, "tol": 1e-8, "max_iter": 300, "seed": 0}
 COV_MAX_D = 96                # AQ_COV_MAX_D: covariates that aq_prepare_data_cov takes
 LD_PRUNE_DEFAULTS = {"r2": 0.8, "window": 500, "window_bp": None, "groups": None, "positions": None}
 LD_MAX_WINDOW = 4096          # AQ_LD_MAX_WINDOW of csrc/aq_ld_kernels.h
@@ -474,10 +493,79 @@ def _n_of(X):
     return int(np.shape(X)[0])
 
 
-def _check_grm_n(n, what):
+def _check_grm_n(n, what, pcs=False):
     if n > GRM_MAX_N:
+        hint = ' genotype_pcs with solver="subspace" takes the leading components without that matrix.' if pcs else ""
         raise AtlasqtlError(f"{what}: n = {n} samples given, at most {GRM_MAX_N} are supported (the n x n relationship matrix "
-                            "is decomposed on the host).")
+                            f"is decomposed on the host).{hint}")
+
+
+def pc_solver_options(k, n, what, solver="eigh", oversample=None, tol=1e-8, max_iter=300, seed=0):
+    """The solver arguments of genotype_pcs() checked on the host; returns them as a dict with `oversample` resolved: 16 unless
+    given, then clipped so that the block width L = k + oversample stays <= min(128, n - 1).  solver="eigh" is refused above
+    10240 samples, solver="subspace" above the 82944 a fit takes."""
+    if not isinstance(solver, str) or solver not in PC_SOLVERS:
+        raise AtlasqtlError(f"{what}: solver must be 'eigh' or 'subspace', not {solver!r}.")
+    if oversample is not None and (not _is_whole(oversample) or int(oversample) < 0):
+        raise AtlasqtlError(f"{what}: oversample must be None or a whole number >= 0, not {oversample!r}.")
+    if not _is_whole(max_iter) or int(max_iter) < 1:
+        raise AtlasqtlError(f"{what}: max_iter must be a whole number >= 1, not {max_iter!r}.")
+    if not _is_whole(seed) or int(seed) < 0:
+        raise AtlasqtlError(f"{what}: seed must be a whole number >= 0, not {seed!r}.")
+    if isinstance(tol, (bool, np.bool_)) or not isinstance(tol, (int, float, np.integer, np.floating)) or not (float(tol) > 0.0) \
+            or not np.isfinite(float(tol)):
+        raise AtlasqtlError(f"{what}: tol must be a number > 0, not {tol!r}.")
+    if _is_whole(k) and oversample is not None and int(k) + int(oversample) > PCS_MAX_L:
+        raise AtlasqtlError(f"{what}: k + oversample must be at most {PCS_MAX_L} (the block of vectors of solver='subspace'), "
+                            f"not {int(k)} + {int(oversample)}.")
+    if solver == "eigh":
+        _check_grm_n(n, what, pcs=True)
+    elif n > N_MAX:
+        raise AtlasqtlError(f"{what}: n = {n} samples given, at most {N_MAX} are supported.")
+    over = 16 if oversample is None else int(oversample)
+    if _is_whole(k):
+        over = max(0, min(over, min(PCS_MAX_L, n - 1) - int(k)))
+    return dict(solver=solver, oversample=over, tol=float(tol), max_iter=int(max_iter), seed=int(seed))
+
+
+def subspace_pcs_(apply, n, k, oversample=16, tol=1e-8, max_iter=300, seed=0, trace=None):
+    """The k leading eigenpairs of a symmetric positive semi-definite operator given only as `apply`: Q (n x L) -> K Q, by
+    subspace iteration with a Rayleigh-Ritz step on a block of L = k + oversample vectors.
+      Q_0 = the Q factor of numpy.random.default_rng(seed).standard_normal((n, L)); every iteration forms Z = apply(Q),
+      B = sym(Q' Z) and its eigenpairs (w descending, W), the Ritz vectors V = Q W and the residuals ||Z W - V diag(w)||_2 per
+      column divided by w_1; it stops when the largest of the first k residuals is <= tol, else Q = the Q factor of Z.
+    The n x L QR and the L x L eigh run on the host.  Returns dict(pcs n x k signed by pc_sign_, eigenvalues (k, descending),
+    var_explained = eigenvalue / trace (NaN without `trace`), iterations, converged, residuals (k)).
+    The error of Ritz vector i is at most 2 residual_i lambda_1 / gap_i (Davis-Kahan), gap_i the distance of lambda_i to the
+    nearest other eigenvalue, and the iteration contracts component i by lambda_(L+1) / lambda_i per step: a few steps for
+    components of population structure, which stand clear of the bulk.  Components INSIDE the noise bulk have tiny gaps, and
+    plain subspace iteration then needs hundreds of steps (146 ... 242 at n = 300 for k = 5 with two structural components); a
+    block Krylov method would be the tool, and is not built.  `max_iter` bounds the work: when it is reached a warning is
+    given, converged is False, and what is returned is still an orthonormal Ritz basis with its residuals -- never an
+    exception.  Equal inputs give equal bits."""
+    import warnings
+    n, k, L = int(n), int(k), int(k) + int(oversample)
+    Q = np.linalg.qr(np.random.default_rng(int(seed)).standard_normal((n, L)))[0]
+    converged, it = False, 0
+    for it in range(1, int(max_iter) + 1):
+        Z = np.asarray(apply(Q), dtype=np.float64)
+        B = Q.T @ Z
+        w, W = np.linalg.eigh(0.5 * (B + B.T))
+        w, W = w[::-1], W[:, ::-1]
+        V = Q @ W
+        res = np.linalg.norm(Z @ W - V * w, axis=0) / w[0]
+        if float(np.max(res[:k])) <= tol:
+            converged = True
+            break
+        Q = np.linalg.qr(Z)[0]
+    if not converged:
+        warnings.warn(f"subspace iteration for {k} genotype principal components has not converged after {it} iterations: the "
+                      f"largest residual is {float(np.max(res[:k])):.3e}, tol = {tol:.3e}.  Components inside the noise bulk "
+                      "converge slowly; raise max_iter or oversample, or ask for fewer components.")
+    lam = np.array(w[:k])
+    tr = float("nan") if trace is None else float(trace)
+    return dict(pcs=pc_sign_(V[:, :k]), eigenvalues=lam, var_explained=lam / tr, iterations=it, converged=converged,
+                residuals=np.array(res[:k]))
 
 
 def _check_pc_count(k, n, d, what):
@@ -491,24 +579,30 @@ def _check_pc_count(k, n, d, what):
 
 
 def genotype_pcs_options(genotype_pcs, n, d=0):
-    """The `genotype_pcs` argument of atlasqtl() checked on the host: a whole number k or a dict with the keys 'k' and
-    'ld_prune' (None, or the dict ld_prune= takes), with 1 <= k <= min(n - 2, 96 - d) for n samples and d user covariates, and
-    n <= 10240.  Returns {"k": k, "ld_prune": dict or None}."""
+    """The `genotype_pcs` argument of atlasqtl() checked on the host: a whole number k or a dict with the key 'k' and,
+    optionally, 'ld_prune' (None, or the dict ld_prune= takes) and the solver arguments of genotype_pcs() ('solver',
+    'oversample', 'tol', 'max_iter', 'seed'), with 1 <= k <= min(n - 2, 96 - d) for n samples and d user covariates, and
+    n <= 10240 unless solver is 'subspace'.  Returns {"k": k, "ld_prune": dict or None} and the solver keys that were given."""
+    form = ("genotype_pcs must be None, a whole number k or a dict with the key 'k' and, optionally, 'ld_prune', 'solver', "
+            "'oversample', 'tol', 'max_iter', 'seed'.")
+    given = {}
     if isinstance(genotype_pcs, dict):
-        if "k" not in genotype_pcs or set(genotype_pcs) - {"k", "ld_prune"}:
-            raise AtlasqtlError("genotype_pcs must be None, a whole number k or a dict with the key 'k' and, optionally, 'ld_prune'.")
+        if "k" not in genotype_pcs or set(genotype_pcs) - {"k", "ld_prune"} - set(PC_SOLVER_DEFAULTS):
+            raise AtlasqtlError(form)
         o = {"k": genotype_pcs["k"], "ld_prune": genotype_pcs.get("ld_prune")}
+        given = {key: genotype_pcs[key] for key in PC_SOLVER_DEFAULTS if key in genotype_pcs}
     elif _is_whole(genotype_pcs):
         o = {"k": genotype_pcs, "ld_prune": None}
     else:
-        raise AtlasqtlError("genotype_pcs must be None, a whole number k or a dict with the key 'k' and, optionally, 'ld_prune'.")
-    _check_grm_n(n, "genotype_pcs")
+        raise AtlasqtlError(form)
+    pc_solver_options(o["k"], n, "genotype_pcs", **given)
     o["k"] = _check_pc_count(o["k"], n, d, "genotype_pcs")
     if o["ld_prune"] is not None:
         try:
             ld_prune_options(o["ld_prune"])
         except AtlasqtlError as e:
             raise AtlasqtlError(f"genotype_pcs: {e}") from None
+    o.update(given)
     return o
 
 
@@ -532,23 +626,45 @@ def genotype_grm(X, device=0, covariates=None, ld_prune=None):
     return _grm_of(X, device, covariates, ld_prune)[0]
 
 
-def genotype_pcs(X, k, device=0, covariates=None, ld_prune=None):
+def genotype_pcs(X, k, device=0, covariates=None, ld_prune=None, solver="eigh", oversample=None, tol=1e-8, max_iter=300, seed=0):
     """The k leading principal components of the genotypes X: eigenvectors of genotype_grm(X, ...).  Returns dict(pcs n x k,
     unit norm, each signed so that its entry of largest magnitude is positive; eigenvalues (k, descending); var_explained =
-    eigenvalue / trace K; p_used = p1, the predictors K was formed over).  Every column of Xs is centred, so the PCs are
-    orthogonal to the intercept.  1 <= k <= n - 2 - d with d covariates: the residuals on them and the intercept span at most
-    n - 1 - d dimensions, and a PC beyond that would be an eigenvector of rounding noise."""
+    eigenvalue / trace K; p_used = p1, the predictors K was formed over; solver; iterations; converged; residuals (k)).  Every
+    column of Xs is centred, so the PCs are orthogonal to the intercept.  1 <= k <= n - 2 - d with d covariates: the residuals
+    on them and the intercept span at most n - 1 - d dimensions, and a PC beyond that would be an eigenvector of rounding noise.
+    solver="eigh" (the default): K is formed on the GPU and decomposed on the host, n <= 10240; iterations is 0, converged True
+    and residuals None.
+    solver="subspace": K is never formed.  subspace_pcs_ iterates a block of k + oversample vectors (oversample 16 unless
+    given, the block at most min(128, n - 1) wide) whose product with K runs on the GPU (aq_prep_grm_apply); n up to 82944.
+    It stops when the residuals of the k components are <= tol or after max_iter iterations (then with a warning and
+    converged False, see subspace_pcs_ on components inside the noise bulk); seed fixes the starting block."""
     n = _n_of(X)
-    _check_grm_n(n, "genotype_pcs")
-    Z = _covariates_arg(covariates, n)[1]
-    d = 0 if Z is None else Z.shape[1]
     if not _is_whole(k):
         raise AtlasqtlError(f"genotype_pcs: k must be a whole number, not {k!r}.")
+    so = pc_solver_options(k, n, "genotype_pcs", solver, oversample, tol, max_iter, seed)
+    Z = _covariates_arg(covariates, n)[1]
+    d = 0 if Z is None else Z.shape[1]
     if not (1 <= int(k) <= n - 2 - d):
         raise AtlasqtlError(f"genotype_pcs: k must lie in [1, {n - 2 - d}] = [1, n - 2 - d] with n = {n} samples and d = {d} "
                             f"covariates regressed out of the genotypes, not {k!r}.")
-    K, tr, p1 = _grm_of(X, device, covariates, ld_prune)
-    return dict(pcs_from_grm_(K, int(k), tr), p_used=int(p1))
+    if so["solver"] == "eigh":
+        K, tr, p1 = _grm_of(X, device, covariates, ld_prune)
+        return dict(pcs_from_grm_(K, int(k), tr), p_used=int(p1), solver="eigh", iterations=0, converged=True, residuals=None)
+    prep = prepare_on_device(np.zeros((n, 1), order="F"), X, device, covariates, ld_prune)[0]
+    try:
+        trace = []
+
+        def apply(Q):                                            # the first application also returns the trace of K
+            if trace:
+                return prep.grm_apply(Q)
+            Z, tr = prep.grm_apply(Q, return_trace=True)
+            trace.append(tr)
+            return Z
+
+        out = subspace_pcs_(apply, n, int(k), so["oversample"], so["tol"], so["max_iter"], so["seed"])
+        return dict(out, var_explained=out["eigenvalues"] / trace[0], p_used=int(prep.p), solver="subspace")
+    finally:
+        prep.close()
 
 
 def covariates_with_genotype_pcs(Y, X, covariates, genotype_pcs_arg, device=0):
@@ -561,5 +677,5 @@ def covariates_with_genotype_pcs(Y, X, covariates, genotype_pcs_arg, device=0):
     Z = _covariates_arg(covariates, n)[1]
     o = genotype_pcs_options(genotype_pcs_arg, n, 0 if Z is None else Z.shape[1])
     _ld_arg(o["ld_prune"], X)                                    # lengths of groups / positions against X
-    pcs = genotype_pcs(X, o["k"], device, ld_prune=o["ld_prune"])
+    pcs = genotype_pcs(X, o["k"], device, ld_prune=o["ld_prune"], **{key: o[key] for key in PC_SOLVER_DEFAULTS if key in o})
     return (pcs["pcs"] if Z is None else np.hstack([Z, pcs["pcs"]])), pcs

@@ -553,6 +553,52 @@ int aq_prep_grm(aq_prep_handle h, double *K_out, double *trace_out);
 int aq_grm_plan_query(int32_t n, int32_t p1, int32_t ncu, int64_t free_bytes, aq_grm_plan *out);
 int aq_prep_grm_time(aq_prep_handle h, int32_t reps, double *ms_per_call, aq_grm_plan *plan_out);
 
+/* ------------------------------------------------------------------------------------------
+ * The relationship operator applied to a block of vectors, without the n x n matrix: for a handle as above and Q (n x L),
+ *   Z = Xs (Xs' Q) / p1 = K Q
+ * over the same current matrix Xs that aq_prep_grm uses.  It is the step of subspace iteration for the leading eigenvectors
+ * of K (the genotype principal components), and it grows as n p1 L, not as n^2: every n a handle holds is taken (up to
+ * 82 944, AQ_N_MAX); the 10 240 of aq_prep_grm does not apply.
+ * Two tall-skinny products on the f64 matrix pipe (4 n p1 lp flop, two reads of Xs; lp = L padded to 16): T = Xs' Q
+ * (p1 x lp, kept in device memory), one workgroup per panel of predictors, the reduction over the samples; then Xs T over
+ * tiles of samples, the predictors split over several workgroups per tile whose partial tiles a third kernel adds in a fixed
+ * order and divides by p1 -- no floating-point atomics, so two calls on one handle return the same bits.  Rows >= n and
+ * columns >= L of the padded block contribute exact zeros; Q = 0 gives Z = 0 exactly.  Every entry is within
+ * (n + p1 + 4) 2^-53 (|Xs| (|Xs'| |Q|)) / p1 of the exact value.
+ *   aq_prep_grm_apply       Q, Z_out: n x L column-major, host, 1 <= L <= 128 (AQ_PCS_MAX_L).  trace_out (may be NULL): the
+ *                           trace of K, (sum of Xs^2) / p1, every column's sum of squares added in a fixed order and the
+ *                           columns in index order.  The handle is not changed.
+ *   aq_pcs_plan_query       the launch plan without a device, a pure function of its arguments: the padded width, the panels
+ *                           of the first product (grid n_panels), the sample tiles and predictor splits of the second (grid
+ *                           n_tiles x splits; split s owns the chunks [s chunks_per_split, (s + 1) chunks_per_split)) and the
+ *                           device memory: t_bytes + io_bytes + scratch_bytes <= free_bytes.  splits = 1 when the tiles alone
+ *                           give two workgroups per CU.  The environment variable AQ_PCS_SPLITS (1 ... 64; tests) forces the
+ *                           splits of aq_prep_grm_apply; the query does not read it.
+ *   aq_prep_grm_apply_time  measurement: the kernels of one application `reps` times between two events after one warm-up,
+ *                           without the copies from and to the host; ms_per_call and, if not NULL, the plan used.
+ * L outside [1, 128], a NULL handle or a NULL operand is AQ_ERR_ARG, before any device call.  A plan that does not fit the free
+ * memory is AQ_ERR_DEVICE.  Every error names the entry that was called (aq_prep_grm_apply, aq_pcs_plan_query,
+ * aq_prep_grm_apply_time) in aq_last_error().
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_pcs_plan {
+  int32_t lp;                 /* L padded to a multiple of 16: columns of T and of a partial tile */
+  int32_t panel;              /* predictors per workgroup of T = Xs' Q                        */
+  int32_t n_panels;           /* ceil(p1 / panel): the grid of the first product              */
+  int32_t sample_chunk;       /* samples of Q staged per step of the first product           */
+  int32_t n_pad;              /* n padded to a multiple of sample_chunk                       */
+  int32_t tile;               /* samples per workgroup of Xs T                                */
+  int32_t n_tiles;            /* ceil(n / tile)                                               */
+  int32_t splits;             /* workgroups per tile, each with its own predictors           */
+  int32_t chunk;              /* predictors staged per step of the second product            */
+  int32_t chunks_per_split;   /* split s owns chunks [s chunks_per_split, (s + 1) chunks_per_split) */
+  int64_t t_bytes;            /* T on the device: panel n_panels lp doubles                  */
+  int64_t scratch_bytes;      /* the partial tiles: splits n_tiles tile lp doubles           */
+  int64_t io_bytes;           /* Q, Z (n L doubles each) and the padded row-major Q (n_pad lp) */
+} aq_pcs_plan;
+int aq_prep_grm_apply(aq_prep_handle h, const double *Q, int32_t L, double *Z_out, double *trace_out);
+int aq_pcs_plan_query(int32_t n, int32_t p1, int32_t L, int32_t ncu, int64_t free_bytes, aq_pcs_plan *out);
+int aq_prep_grm_apply_time(aq_prep_handle h, int32_t L, int32_t reps, double *ms_per_call, aq_pcs_plan *plan_out);
+
 #ifdef __cplusplus
 }
 #endif
