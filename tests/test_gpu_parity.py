@@ -178,10 +178,12 @@ def test_recurrence_wave_tile_counts_match_oracle(tt, nt3, chain, monkeypatch):
 @pytest.mark.parametrize("tt", [1, 2])
 @pytest.mark.parametrize("n", [20, 100, 200, 330, 512, 600, 768, 860, 912, 1000, 1024, 1040])
 def test_look_ahead_kernel_every_tile_count_matches_oracle(n, tt, monkeypatch):
-    """Residual-tile geometries NT/NT2 = 1/1 ... 11/11 of the look-ahead kernel as the host picks them (two tiles per workgroup: 9 / 8 / 6 at
-    n = 860 and 912, 9 / 9 / 9 at 1000, 10 / 10 / 9 at 1024 and 1040, all with the helper wave at raised priority; n = 1040: 65 of the 66 tiles one workgroup
-    holds; beyond n = 1056 the sample axis is split over several workgroups, tests/test_gpu_sharded.py), one and two trait
-    tiles per workgroup, 12 sweeps each incl. the ladder and two ELBO evaluations."""
+    """The residual-tile geometries of the look-ahead kernel that the host picks at these twelve n -- some of 1/1 ... 11/11, not
+    all of them, never chained, complete Y only, and the instance that ran is not asserted: tests/test_gpu_unsplit_instances.py
+    runs every unsplit instance and proves each from the status.  (Two tiles per workgroup: 9 / 8 / 6 at n = 860 and 912,
+    9 / 9 / 9 at 1000, 10 / 10 / 9 at 1024 and 1040, all with the helper wave at raised priority; n = 1040: 65 of the 66 tiles
+    one workgroup holds; beyond n = 1056 the sample axis is split over several workgroups, tests/test_gpu_sharded.py.)  One and
+    two trait tiles per workgroup, 12 sweeps each incl. the ladder and two ELBO evaluations."""
     monkeypatch.setenv("AQ_TT", str(tt))
     prob = make_problem(n, 100, 24, p_act=6, prob_assoc=0.5)
     ref, got, tr = _run_both(prob, (1, 2, 10), 12, thinned=False)

@@ -5,7 +5,8 @@ aq_core_sweep_la_kernel is compiled once per residual-tile geometry, each instan
 schedule of its own.  The ISA proof (tools/check_isa_operands.py) shows that no instance has a load hazard; only a run shows
 that it computes the right numbers.  The families below walk
   a / b  the medium split's geometries 12/11 ... 18/18 (AQ_LB of aq_launch_la1.hip and aq_launch_la1m.hip), forced at small n
-         and as the planner picks them for 8448 < n <= 10 240 and for a shard of many traits,
+         and as the planner picks them for 8448 < n <= 10 240 and for a shard of many traits; and the split exchange inside
+         the geometries 1/1 ... 11/11 (AQ_LA of the same files), forced by the same rule,
   c      the wide split's NT = 1 ... 18 (AQ_LW of aq_launch_la1w.hip and aq_launch_la1wm.hip),
   d      every part count C = 9 ... 48 of split_exchange_wide (17 lane layouts, some with a dead last chunk),
   e      the geometric limit n = 82 944 = AQ_N_MAX: 48 parts of 18/18, no padding anywhere.
@@ -32,6 +33,12 @@ MEDIUM_FORCED = {23: (12, 11), 24: (12, 12), 25: (13, 12), 26: (13, 13), 27: (14
                  30: (15, 15), 31: (16, 15), 32: (16, 16), 33: (17, 16), 34: (17, 17), 35: (18, 17), 36: (18, 18)}
 MEDIUM_NA = 0.05
 MEDIUM_XHELPER_BOTH = (23, 30, 36)     # these also run with the exchange on the helper wave (AQ_LA_XHELPER = 1)
+# ... and the same rule below the AQ_LB list: the AQ_LA instances 1/1 ... 11/11 of the unsplit launches (which
+# tests/test_gpu_unsplit_instances.py runs unsplit), here in two parts: the exchange is a runtime path inside them
+MEDIUM_FORCED_SMALL = {2: (1, 1), 3: (2, 1), 4: (2, 2), 5: (3, 2), 6: (3, 3), 7: (4, 3), 8: (4, 4), 9: (5, 4), 10: (5, 5), 11: (6, 5),
+                       12: (6, 6), 13: (7, 6), 14: (7, 7), 15: (8, 7), 16: (8, 8), 17: (9, 8), 18: (9, 9), 19: (10, 9), 20: (10, 10),
+                       21: (11, 10), 22: (11, 11)}
+MEDIUM_SMALL_WHOLE = (2, 11, 22)       # whole runs, and the short form with AQ_LA_XHELPER = 1 as well
 
 # --- b. the planner's own choice on 256 CUs: (n, p, q, na, maxit) -> (C, NT, NT2)
 MEDIUM_NATURAL = [
@@ -73,7 +80,7 @@ def ledger():
     """What the tables above claim to reach: (medium instances, wide instances, part counts of the wide exchange), the
     instances as (mask, NT, NT2) and (mask, NT)."""
     medium, wide, parts = set(), set(), set()
-    for nt, nt2 in MEDIUM_FORCED.values():
+    for nt, nt2 in list(MEDIUM_FORCED.values()) + list(MEDIUM_FORCED_SMALL.values()):
         medium |= {(0, nt, nt2), (1, nt, nt2)}
     for (n, p, q, na, maxit), (C, nt, nt2) in MEDIUM_NATURAL:
         medium.add((int(na > 0), nt, nt2))
@@ -133,21 +140,29 @@ def _bar(a, b, rtol, atol):
     return float(np.max(np.abs(a - b) / (atol + rtol * np.abs(b))))
 
 
-def _check(family, prob, instance, maxit=SHORT, n_pad=None, keep=False):
+def _reference(prob, maxit=SHORT):
+    """The oracle's run of the problem, as _check holds a handle to it: (result, ELBO trace)."""
+    from oracle import atlasqtl_oracle as O
+    tr = []
+    ref = O.atlasqtl_global_local_core_(prob["Y"], prob["X"], prob["Y"].shape[1], ANNEAL, 1, 0.1, maxit, prob["list_hyper"],
+                                        prob["list_init"], thinned_elbo_eval=maxit != SHORT, debug=True, trace=tr, full_output=True)
+    return ref, np.array([r["lb"] for r in tr if r["lb"] is not None])
+
+
+def _check(family, prob, instance, maxit=SHORT, n_pad=None, keep=False, assert_instance=None, reference=None):
     """Create the handle, assert its instance, run, and hold the result to the bars of tests/test_gpu_large_n.py::_check.
     Short cases evaluate the ELBO after every non-annealed sweep (thinned = False), whole runs as the library does by default.
-    The observed deviations are printed before they are asserted."""
+    The observed deviations are printed before they are asserted.  assert_instance: what proves the instance from the handle
+    (_assert_instance unless given); reference: _reference(prob, maxit) computed earlier, for cases that share one."""
     from atlasqtl_amd.core import VbRun
-    from oracle import atlasqtl_oracle as O
     thinned = maxit != SHORT
     q = prob["Y"].shape[1]
-    tr = []
-    ref = O.atlasqtl_global_local_core_(prob["Y"], prob["X"], q, ANNEAL, 1, 0.1, maxit, prob["list_hyper"], prob["list_init"],
-                                        thinned_elbo_eval=thinned, debug=True, trace=tr, full_output=True)
-    lref = np.array([r["lb"] for r in tr if r["lb"] is not None])
+    ref, lref = reference if reference is not None else _reference(prob, maxit)
     run = VbRun(prob["Y"], prob["X"], prob["list_hyper"], prob["list_init"], ANNEAL, 0.1, maxit, thinned, True)
     try:
-        if instance is not None:
+        if instance is not None and assert_instance is not None:
+            assert_instance(run, *instance)
+        elif instance is not None:
             _assert_instance(run, *instance, n_pad=n_pad)
         run.run()
         st = run.status()
@@ -160,7 +175,8 @@ def _check(family, prob, instance, maxit=SHORT, n_pad=None, keep=False):
             assert st["converged"] and ref["converged"]
         assert lgot.shape == lref.shape
         print(f"\nDEV family={family} n={prob['n']} q={q} it={st['it']} flags={st['instance_flags']} C={st['split_parts']} "
-              f"NT={st['tiles_matrix']}/{st['tiles_matrix2']} elbo_rel={_rel(lgot, lref):.3e} "
+              f"NT={st['tiles_matrix']}/{st['tiles_matrix2']}/{st['tiles_recurrence']} TT={st['tiles_per_group']} "
+              f"S={st['chain_segments']} elbo_rel={_rel(lgot, lref):.3e} "
               f"mu_bar={_bar(got['mu_beta_vb'], ref['mu_beta_vb'], 1e-6, 1e-10):.3e} "
               f"mu_abs={np.max(np.abs(got['mu_beta_vb'] - ref['mu_beta_vb'])):.3e} "
               f"gam_abs={np.max(np.abs(got['gam_vb'] - ref['gam_vb'])):.3e} "
@@ -203,6 +219,37 @@ def test_medium_split_exchange_on_helper_wave_matches_oracle(k, na, monkeypatch)
     prob = _problem(96 * k - 5, 61, 27, na)
     assert _max_missing(prob) <= MIS_MMAX
     _check("a", prob, (MASK if na else 0, 2, nt, nt2))
+
+
+@pytest.mark.parametrize("na", [0.0, MEDIUM_NA])
+@pytest.mark.parametrize("k", sorted(MEDIUM_FORCED_SMALL))
+def test_medium_split_every_small_geometry_matches_oracle(k, na, monkeypatch):
+    """The 21 AQ_LA geometries 1/1 ... 11/11 in two parts, complete Y and MASK, exchange on the recurrence wave: the ladder and
+    two ELBO evaluations."""
+    monkeypatch.setenv("AQ_LA_C", "2")
+    monkeypatch.setenv("AQ_LA_XHELPER", "0")
+    nt, nt2 = MEDIUM_FORCED_SMALL[k]
+    _check("a", _problem(96 * k - 5, 70, 33, na), (MASK if na else 0, 2, nt, nt2))
+
+
+@pytest.mark.parametrize("na", [0.0, MEDIUM_NA])
+@pytest.mark.parametrize("k", MEDIUM_SMALL_WHOLE)
+def test_medium_split_small_geometry_whole_run_matches_oracle(k, na, monkeypatch):
+    """1/1, 6/5 and 11/11 in two parts to convergence."""
+    monkeypatch.setenv("AQ_LA_C", "2")
+    monkeypatch.setenv("AQ_LA_XHELPER", "0")
+    nt, nt2 = MEDIUM_FORCED_SMALL[k]
+    _check("a", _problem(96 * k - 5, 70, 33, na), (MASK if na else 0, 2, nt, nt2), maxit=WHOLE)
+
+
+@pytest.mark.parametrize("na", [0.0, MEDIUM_NA])
+@pytest.mark.parametrize("k", MEDIUM_SMALL_WHOLE)
+def test_medium_split_small_geometry_exchange_on_helper_wave_matches_oracle(k, na, monkeypatch):
+    """1/1, 6/5 and 11/11 with the exchange a block ahead on the helper wave: the ladder and two ELBO evaluations."""
+    monkeypatch.setenv("AQ_LA_C", "2")
+    monkeypatch.setenv("AQ_LA_XHELPER", "1")
+    nt, nt2 = MEDIUM_FORCED_SMALL[k]
+    _check("a", _problem(96 * k - 5, 70, 33, na), (MASK if na else 0, 2, nt, nt2))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

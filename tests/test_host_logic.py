@@ -197,11 +197,19 @@ def test_split_instance_ledger_is_complete():
     """tests/test_gpu_split_instances.py claims to run every sample-split instance of the look-ahead kernel and every part count
     of the wide exchange against the oracle.  Its tables must name the complete set -- wide: NT = 1 ... 18, medium split: NT =
     12 ... 18 with NT2 in {NT, NT - 1}, each for complete Y and MASK; C = 9 ... 48 -- and that set must be the one the launch
-    files compile: an instance added to an AQ_LB / AQ_LW list fails here until a case runs it."""
+    files compile: an instance added to an AQ_LB / AQ_LW list fails here until a case runs it.  So must the split inside the
+    geometries of the unsplit launches, NT = 1 ... 11 of AQ_LA (MEDIUM_FORCED_SMALL)."""
     import os
     import re
     from tests import test_gpu_split_instances as T
-    medium, wide, parts = T.ledger()
+    medium_all, wide, parts = T.ledger()
+    # below the AQ_LB list the split runs inside the AQ_LA instances of the unsplit launches (NT <= 11): every one of them too
+    medium, medium_small = {g for g in medium_all if g[1] >= 12}, {g for g in medium_all if g[1] <= 11}
+    want_small = {(m, nt, nt2) for m in (0, 1) for nt in range(1, 12) for nt2 in (nt, nt - 1) if nt2 >= 1}
+    assert medium_small == want_small and len(want_small) == 42, sorted(want_small ^ medium_small)
+    assert {(m, nt, nt2) for m in (0, 1) for nt, nt2 in T.MEDIUM_FORCED_SMALL.values()} == want_small
+    assert all(nt + nt2 == k for k, (nt, nt2) in T.MEDIUM_FORCED_SMALL.items()) and sorted(T.MEDIUM_FORCED_SMALL) == list(range(2, 23))
+    assert set(T.MEDIUM_SMALL_WHOLE) == {2, 11, 22}
     want_medium = {(m, nt, nt2) for m in (0, 1) for nt in range(12, 19) for nt2 in (nt, nt - 1)}
     want_wide = {(m, nt) for m in (0, 1) for nt in range(1, 19)}
     assert medium == want_medium, sorted(want_medium ^ medium)
@@ -232,5 +240,6 @@ def test_split_instance_ledger_is_complete():
         return sorted(int(x) for x in re.findall(macro + r"\((\d+)\)", body))
     for name in ("aq_launch_la1.hip", "aq_launch_la1m.hip"):
         assert listed(name, "AQ_LB") == sorted({nt for _, nt, _ in medium}), name
+        assert listed(name, "AQ_LA") == sorted({nt for _, nt, _ in medium_small}), name
     for m, name in ((0, "aq_launch_la1w.hip"), (1, "aq_launch_la1wm.hip")):
         assert listed(name, "AQ_LW") == sorted(nt for mm, nt in wide if mm == m), name

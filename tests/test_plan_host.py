@@ -172,6 +172,23 @@ def _compiled():
     return ok
 
 
+def compiled_unsplit():
+    """The kernels the three launch files of the unsplit launches compile from AQ_LA, AQ_L3 and aq_la_go9, each plain and
+    chained: (mask, TT, NT, NT2, NT3, seg), NT3 as aq_vb_status reports it (aq_la_nt3 of a two-tile workgroup).  (AQ_LB is the
+    split's: tests/test_host_logic.py::test_split_instance_ledger_is_complete.)"""
+    def pairs(nts):
+        return {(nt, nt2) for nt in nts for nt2 in (nt, nt - 1) if nt2 >= 1}
+    with open(os.path.join(CSRC, "aq_launch_la2.hip")) as f:
+        go9 = {int(x) for x in re.findall(r"case (\d+): aq_la_go9<\1>", f.read())}
+    geo = {(0, 1, nt, nt2, 0) for nt, nt2 in pairs(_listed("aq_launch_la1.hip", "AQ_LA"))}
+    for nt in _listed("aq_launch_la1.hip", "AQ_L3"):
+        geo |= {(0, 1, nt, nt, 3), (0, 1, nt, nt - 1, 6), (0, 1, nt, nt, 9)}
+    geo |= {(0, 2, nt, nt2, (3 if nt2 == nt else 6) if nt >= 8 else 0) for nt, nt2 in pairs(_listed("aq_launch_la2.hip", "AQ_LA"))}
+    geo |= {(0, 2, nt, nt, 9) for nt in go9}
+    geo |= {(1, 1, nt, nt2, 0) for nt, nt2 in pairs(_listed("aq_launch_la1m.hip", "AQ_LA"))}
+    return {g + (seg,) for g in geo for seg in (0, 1)}
+
+
 def _sweep_n():
     return list(range(2, 1101)) + list(range(1101, N_MAX, 97)) + [N_MAX]
 
