@@ -68,6 +68,15 @@ class AqPcsPlan(C.Structure):
                 ("chunks_per_split", C.c_int32), ("t_bytes", C.c_int64), ("scratch_bytes", C.c_int64), ("io_bytes", C.c_int64)]
 
 
+class AqPrepYtrans(C.Structure):
+    _fields_ = [("method", C.c_int32), ("offset", C.c_double)]
+
+
+class AqYtransPlan(C.Structure):
+    _fields_ = [("path", C.c_int32), ("n_pad", C.c_int32), ("lds_bytes", C.c_int32), ("traits_per_batch", C.c_int32),
+                ("scratch_bytes", C.c_int64)]
+
+
 class AqVbMultiOut(C.Structure):
     _fields_ = [
         ("beta_vb", dp), ("gam_vb", dp), ("mu_beta_vb", dp), ("theta_vb", dp), ("zeta_vb", dp), ("lam2_inv_vb", dp),
@@ -169,6 +178,11 @@ SYMBOLS = {
     "aq_prep_grm_apply": (C.c_int, [C.c_void_p, dp, C.c_int32, dp, dp]),
     "aq_pcs_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(AqPcsPlan)]),
     "aq_prep_grm_apply_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, dp, C.POINTER(AqPcsPlan)]),
+    "aq_prepare_data_opt": (C.c_int, [C.POINTER(AqPrepInput), C.POINTER(AqPrepBedInput), C.POINTER(AqPrepCov), C.POINTER(AqPrepYtrans),
+                                      C.POINTER(C.c_void_p)]),
+    "aq_prep_ytrans_info": (C.c_int, [C.c_void_p, ip, dp, ip, ip]),
+    "aq_rank_int": (C.c_int, [dp, C.c_int32, C.c_int32, C.c_double, dp, ip, ip, C.c_int32]),
+    "aq_ytrans_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(AqYtransPlan)]),
 }
 
 _lib = None

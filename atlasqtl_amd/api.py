@@ -15,7 +15,7 @@ from .core import atlasqtl_global_local_core_
 from .postproc import hotspot_sizes, six_numbers_host_, sparse_output_options, value_summary
 from .hyper_init import prepare_list_hyper_, prepare_list_init_
 from .prepare import (check_annealing_, check_positive_, check_vector_, check_verbose_, covariates_with_genotype_pcs,
-                      prepare_data_)
+                      prepare_data_, transform_y_options)
 
 
 class AtlasqtlResult(dict):
@@ -62,10 +62,19 @@ def add_collinear_back_pairs_(assoc, rs_thres, theta_vb, initial_colnames_X, rmv
     return out, np.asarray(rs_thres)[rows], np.asarray(theta_vb)[rows]
 
 
+def warn_tied_traits_(n_obs, n_tied, names_y):
+    """One warning that names the responses (the first ten) more than half of whose observed values are tied."""
+    bad = np.where(2 * np.asarray(n_tied, dtype=np.int64) > np.asarray(n_obs, dtype=np.int64))[0]
+    if bad.size:
+        shown = ", ".join(str(names_y[k]) for k in bad[:10]) + (", ..." if bad.size > 10 else "")
+        warnings.warn(f"transform_y: more than half of the observed values are tied in {bad.size} response(s) ({shown}); ranks do not "
+                      "make such a response normal.")
+
+
 def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, verbose=1, list_hyper=None,
              list_init=None, save_hyper=False, save_init=False, full_output=False, thinned_elbo_eval=True,
              checkpoint_path=None, trace_path=None, add_collinear_back=False, device=0, device_init=False,
-             sparse_output=None, covariates=None, ld_prune=None, genotype_pcs=None):
+             sparse_output=None, covariates=None, ld_prune=None, genotype_pcs=None, transform_y=None):
     """R/atlasqtl.R:179-322.
 
     X: a float64 matrix, int8 dosages, or a plink.PlinkBed (a PLINK 1 .bed / .bim / .fam fileset, unpacked on the GPU): the
@@ -103,7 +112,15 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
     iteration on the GPU without the n x n matrix, for every n a fit takes.  The option's own
     "ld_prune" (the dict ld_prune= takes) thins only the matrix the PCs are taken from, the usual prune-then-PCA; the fit's
     predictors are governed by ld_prune= alone.  X is prepared twice.  The result then carries `genotype_pcs` (n x k),
-    `pc_eigenvalues`, `pc_var_explained`, `pc_solver`, `pc_iterations`, `pc_converged`, and `n_covariates` counts d + k."""
+    `pc_eigenvalues`, `pc_var_explained`, `pc_solver`, `pc_iterations`, `pc_converged`, and `n_covariates` counts d + k.
+
+    transform_y = "int" or {"method": "int", "offset": 0.375}: the rank-based inverse normal transform of every response on the
+    GPU before anything else is done to Y (rank_normalize(): Phi^-1((r - offset) / (m + 1 - 2 offset)) over the m observed values
+    of the response, ties given their average rank, missing values left missing) -- what expression, protein and metabolite
+    levels go through before a QTL analysis; with covariates the transformed response is residualised.  The genotype PCs
+    never see Y.  The result then carries `transform_y` (the options used), `y_n_obs` and `y_n_tied` (per response, its observed
+    values and those among them that share their value with another one).  A response more than half of whose observed
+    values are tied is not made normal by ranks: one warning names such responses (the first ten)."""
     if ld_prune is not None and add_collinear_back:
         raise ValueError("add_collinear_back=True cannot be combined with ld_prune: a predictor removed for LD is not a copy of "
                          "the predictor that tags it, and the add-back maps assume copies (they would hand it the tag's "
@@ -119,11 +136,17 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
                          "cannot reproduce.  Use the dense output.")
     check_verbose_(verbose)
     check_annealing_(anneal)
+    yt_opts = transform_y_options(transform_y)                              # before the first device call
     pcs = None
     if genotype_pcs is not None:
         covariates, pcs = covariates_with_genotype_pcs(Y, X, covariates, genotype_pcs, device)
-    dat = prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path, covariates=covariates,
-                        ld_prune=ld_prune)
+    if yt_opts is None:
+        dat = prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path, covariates=covariates,
+                            ld_prune=ld_prune)
+    else:
+        dat = prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path, covariates=covariates,
+                            ld_prune=ld_prune, transform_y=yt_opts)
+        warn_tied_traits_(dat["y_n_obs"], dat["y_n_tied"], dat["names_y"])
     bool_rmvd_x = dat["bool_rmvd_x"]
     Xs, Yc = dat["X"], dat["Y"]
     n, p = Xs.shape
@@ -161,6 +184,8 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
         res["pc_solver"], res["pc_iterations"], res["pc_converged"] = pcs["solver"], pcs["iterations"], pcs["converged"]
     if ld_prune is not None:
         res["rmvd_ld_x"], res["ld_r2_x"] = dat["rmvd_ld_x"], dat["ld_r2_x"]
+    if yt_opts is not None:
+        res["transform_y"], res["y_n_obs"], res["y_n_tied"] = dict(yt_opts), dat["y_n_obs"], dat["y_n_tied"]
     names_snp = dat["names_x"]
     if sparse is not None:
         if sparse["summary"]:

@@ -82,6 +82,10 @@ class AqDev {
 };
 
 // --------------------------------------------- functions shared by the units ----
+// IEEE double -> key whose unsigned order is the order of the values (negative: all bits flipped; otherwise: sign bit set):
+// the radix select of aq_summary.hip and the column sort of aq_ytrans_kernels.h
+__host__ __device__ inline uint64_t aq_key_of_bits(uint64_t b) { return (b >> 63) ? ~b : (b | 0x8000000000000000ull); }
+
 struct aq_vb;
 
 // aq_ops.hip

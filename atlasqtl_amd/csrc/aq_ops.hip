@@ -264,6 +264,8 @@ __host__ __device__ static inline bool aq_special_one(int which, double x, doubl
     // log Phi(x), log(1 - Phi(x)) from the tables, as the ELBO pass takes them (aq_log_ndtr_pair_tab)
     case 24: aq_log_ndtr_pair_tab(x, aq_pt_table(), aq_ptn_table(), &a_, &b_); *out = a_; return true;
     case 25: aq_log_ndtr_pair_tab(x, aq_pt_table(), aq_ptn_table(), &a_, &b_); *out = b_; return true;
+    // Phi^-1(x) for 0 < x <= 1/2, as the rank-based inverse normal transform of Y takes it (aq_ytrans_kernels.h)
+    case 26: *out = aq_ndtri(x); return true;
     default: return false;
   }
 }
@@ -283,7 +285,7 @@ __global__ void aq_k_special_eval(int which, const double *x, const double *x2, 
 
 extern "C" int aq_special_eval_device(int32_t which, const double *x, const double *x2, double *out, int64_t len, int32_t device) {
   if (!x || !out || len < 0) return aq_fail(AQ_ERR_ARG, "aq_special_eval_device: bad argument");
-  if (which < 0 || which > 25) return aq_fail(AQ_ERR_ARG, "aq_special_eval_device: unknown function id");
+  if (which < 0 || which > 26) return aq_fail(AQ_ERR_ARG, "aq_special_eval_device: unknown function id");
   if ((which == 3 || (which >= 14 && which <= 17) || (which >= 21 && which <= 23)) && !x2) return aq_fail(AQ_ERR_ARG, "aq_special_eval_device: x2 required");
   AQ_TRY(aq_need_device(device));
   if (len == 0) return AQ_OK;

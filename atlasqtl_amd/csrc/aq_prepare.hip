@@ -19,6 +19,9 @@
 // (aq_grm_kernels.h, planned by aq_grm_plan.h) and copies it to the host.
 // aq_prep_grm_apply applies that matrix to a block of vectors without forming it, Xs (Xs' Q) / p1 (aq_pcs_kernels.h, planned by
 // aq_pcs_plan.h): the step of subspace iteration for its leading eigenvectors, for any n a handle holds.
+// aq_prepare_data_opt is the four aq_prepare_data* entries in one and can put the rank-based inverse normal transform of the
+// traits (aq_ytrans_kernels.h, planned by aq_ytrans_plan.h) in front of everything that is done to Y; aq_rank_int is that
+// transform alone.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <memory>
@@ -46,6 +49,9 @@ struct aq_prep {
   std::vector<uint8_t> ld_removed;            // p: removed by aq_prep_ld_prune (original numbering, like the two below)
   std::vector<int32_t> ld_of;                 // p: original index of the kept column that tags a removed one, else -1
   std::vector<double> ld_r2;                  // p: r^2 of a removed column with its tag, else NaN
+  int yt_method = 0;                          // transform of Y before everything else (0: none, 1: rank-based inverse normal)
+  double yt_offset = 0.0;                     // its c
+  std::vector<int32_t> yt_nobs, yt_ntied;     // q each: observed values of the trait, and those that share their value
 };
 
 template <typename T>
@@ -69,6 +75,7 @@ __device__ __forceinline__ double aq_block_sum(double v, double *sh) {
 #include "aq_ld_kernels.h"    // aq_k_ld_band, aq_k_ld_scan, aq_k_ld_tag_r2, aq_k_ld_gather
 #include "aq_grm_kernels.h"   // aq_k_grm_partial, aq_k_grm_reduce; aq_grm_make_plan
 #include "aq_pcs_kernels.h"   // aq_k_pcs_pack_q, aq_k_pcs_xtq, aq_k_pcs_xt, aq_k_pcs_reduce, aq_k_pcs_colss; aq_pcs_make_plan
+#include "aq_ytrans_kernels.h"   // aq_k_yt_lds, aq_k_yt_global; aq_ytrans_device, aq_ytrans_make_plan
 
 // one workgroup per column: mean (sum / n, then one refinement pass as R's long-double colMeans would give), the n - 1
 // standard deviation of the centred values, and whether the column is constant
@@ -389,10 +396,25 @@ extern "C" void aq_prep_destroy(aq_prep_handle h) {
   delete h;
 }
 
+// the transform argument of aq_prepare_data_opt, before any device call (method 0 asks for nothing and is not looked at further)
+static int aq_ytrans_check_args(const aq_prep_ytrans *yt, int n, const char *who) {
+  if (yt->method == 0) return AQ_OK;
+  if (yt->method != 1)
+    return aq_fail(AQ_ERR_ARG, std::string(who) + ": unknown transform of Y, method = " + std::to_string(yt->method) +
+                                   " (0 none, 1 rank-based inverse normal)");
+  AQ_TRY(aq_ytrans_check_offset(yt->offset, who));
+  if (n > AQ_N_MAX)
+    return aq_fail(AQ_ERR_ARG, std::string(who) + ": n = " + std::to_string(n) + " exceeds the largest supported sample count, n <= " +
+                                   std::to_string(AQ_N_MAX) + " (AQ_N_MAX)");
+  return AQ_OK;
+}
+
 // Y <- scale(Y, center = TRUE, scale = FALSE) into h->Yc and the two missingness guards (R/prepare_atlasqtl.R:39-45, :83)
 // With covariates (dQt: their basis [D][n] on the device) the residuals on [1, Z] over each column's observed rows take the
 // place of the centring, and a column on whose observed rows the covariates are collinear is an error after the two guards.
-static int aq_prepare_y(aq_prep *h, const double *Y_host, const double *dQt = nullptr, int D = 0) {
+// With a transform (yt, checked by the caller) the columns are rank-normalised in place on the device before either, and a
+// column without two distinct observed values is an error after the two guards.
+static int aq_prepare_y(aq_prep *h, const double *Y_host, const double *dQt = nullptr, int D = 0, const aq_prep_ytrans *yt = nullptr) {
   const int n = h->n, q = h->q;
   const size_t nq = (size_t)n * q;
   AqDev<double> dY;
@@ -402,6 +424,20 @@ static int aq_prepare_y(aq_prep *h, const double *Y_host, const double *dQt = nu
   AQ_TRY(h->Yc.alloc(nq));
   AQ_TRY(dnobs.alloc((size_t)q));
   AQ_HIP(hipMemcpy(dY.get(), Y_host, nq * sizeof(double), hipMemcpyHostToDevice));
+  std::vector<int> yt_deg;
+  if (yt && yt->method != 0) {
+    AqDev<int> dyo, dyt, dyd;
+    AQ_TRY(dyo.alloc((size_t)q));
+    AQ_TRY(dyt.alloc((size_t)q));
+    AQ_TRY(dyd.alloc((size_t)q));
+    AQ_TRY(aq_ytrans_device(dY.get(), dY.get(), n, q, yt->offset, dyo.get(), dyt.get(), dyd.get(), "aq_prepare_data_opt", nullptr));
+    h->yt_method = yt->method;
+    h->yt_offset = yt->offset;
+    h->yt_nobs.resize(q); h->yt_ntied.resize(q); yt_deg.resize(q);
+    AQ_HIP(hipMemcpy(h->yt_nobs.data(), dyo.get(), (size_t)q * sizeof(int), hipMemcpyDeviceToHost));
+    AQ_HIP(hipMemcpy(h->yt_ntied.data(), dyt.get(), (size_t)q * sizeof(int), hipMemcpyDeviceToHost));
+    AQ_HIP(hipMemcpy(yt_deg.data(), dyd.get(), (size_t)q * sizeof(int), hipMemcpyDeviceToHost));
+  }
   if (dQt) {
     AQ_TRY(dflag.alloc_zeroed((size_t)q));
     hipLaunchKernelGGL(aq_k_cov_residualise_y, dim3(q), dim3(256), aq_cov_y_lds_bytes(D), 0, dY.get(), n, D, dQt, h->Yc.get(), dnobs.get(),
@@ -425,6 +461,7 @@ static int aq_prepare_y(aq_prep *h, const double *Y_host, const double *dQt = nu
     if (!low.empty())
       return aq_fail(AQ_ERR_ARG, "Column(s) " + low + " of matrix Y have more than 97.5% missing values, and should be removed. Exit.");
   }
+  if (!yt_deg.empty()) AQ_TRY(aq_ytrans_check_degenerate(yt_deg.data(), q));
   for (size_t k = 0; k < flag.size(); k++)
     if (flag[k])
       return aq_fail(AQ_ERR_ARG, "covariates are collinear on the samples observed for column " + std::to_string(k + 1) + " of Y (" +
@@ -433,11 +470,13 @@ static int aq_prepare_y(aq_prep *h, const double *Y_host, const double *dQt = nu
 }
 
 // cov == NULL or cov->d == 0: no covariates, the path of aq_prepare_data
-static int aq_prepare_data_impl(const aq_prep_input *in, const aq_prep_cov *cov, aq_prep_handle *out, const std::string &who) {
+static int aq_prepare_data_impl(const aq_prep_input *in, const aq_prep_cov *cov, aq_prep_handle *out, const std::string &who,
+                                const aq_prep_ytrans *yt = nullptr) {
   if (!in || !out) return aq_fail(AQ_ERR_ARG, who + ": NULL argument");
   *out = nullptr;
   if (in->n < 2 || in->p < 1 || in->q < 1) return aq_fail(AQ_ERR_ARG, who + ": n >= 2, p >= 1, q >= 1 required");
   if ((!in->X && !in->X_i8) || !in->Y) return aq_fail(AQ_ERR_ARG, who + ": NULL data pointer");
+  if (yt) AQ_TRY(aq_ytrans_check_args(yt, in->n, who.c_str()));
   const bool with_cov = cov && cov->d != 0;
   std::vector<double> Q;
   if (with_cov) AQ_TRY(aq_cov_host_basis(cov, in->n, who.c_str(), &Q));
@@ -454,10 +493,10 @@ static int aq_prepare_data_impl(const aq_prep_input *in, const aq_prep_cov *cov,
     AQ_TRY(dQt.alloc(Q.size()));
     AQ_HIP(hipMemcpy(dQt.get(), Q.data(), Q.size() * sizeof(double), hipMemcpyHostToDevice));
     AQ_TRY(in->X ? aq_prepare_x_cov<double>(h.get(), in->X, dQt.get(), D) : aq_prepare_x_cov<int8_t>(h.get(), in->X_i8, dQt.get(), D));
-    AQ_TRY(aq_prepare_y(h.get(), in->Y, dQt.get(), D));
+    AQ_TRY(aq_prepare_y(h.get(), in->Y, dQt.get(), D, yt));
   } else {
     AQ_TRY(in->X ? aq_prepare_x<double>(h.get(), in->X) : aq_prepare_x<int8_t>(h.get(), in->X_i8));
-    AQ_TRY(aq_prepare_y(h.get(), in->Y));
+    AQ_TRY(aq_prepare_y(h.get(), in->Y, nullptr, 0, yt));
   }
   *out = h.release();
   return AQ_OK;
@@ -605,7 +644,8 @@ static int aq_bed_decode(aq_prep *h, const aq_prep_bed_input *in, AqDev<int8_t> 
   return AQ_OK;
 }
 
-static int aq_prepare_data_bed_impl(const aq_prep_bed_input *in, const aq_prep_cov *cov, aq_prep_handle *out) {
+static int aq_prepare_data_bed_impl(const aq_prep_bed_input *in, const aq_prep_cov *cov, aq_prep_handle *out,
+                                    const aq_prep_ytrans *yt = nullptr) {
   if (!in || !out) return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: NULL argument");
   *out = nullptr;
   if (in->n < 2 || in->p < 1 || in->q < 1) return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: n >= 2, p >= 1, q >= 1 required");
@@ -623,6 +663,7 @@ static int aq_prepare_data_bed_impl(const aq_prep_bed_input *in, const aq_prep_c
                                            std::to_string(in->sample_idx[i]) + " is out of range [0, " + std::to_string(in->n_file) + ")");
   if ((in->count_a2 != 0 && in->count_a2 != 1) || (in->missing != 0 && in->missing != 1))
     return aq_fail(AQ_ERR_ARG, "aq_prepare_data_bed: count_a2 and missing must be 0 or 1");
+  if (yt) AQ_TRY(aq_ytrans_check_args(yt, in->n, "aq_prepare_data_bed"));
   const bool with_cov = cov && cov->d != 0;
   const int D = with_cov ? cov->d + 1 : 0;
   std::vector<double> Q;
@@ -674,7 +715,7 @@ static int aq_prepare_data_bed_impl(const aq_prep_bed_input *in, const aq_prep_c
   }
   dG.reset();
   dX.reset();
-  AQ_TRY(with_cov ? aq_prepare_y(h.get(), in->Y, dQt.get(), D) : aq_prepare_y(h.get(), in->Y));
+  AQ_TRY(with_cov ? aq_prepare_y(h.get(), in->Y, dQt.get(), D, yt) : aq_prepare_y(h.get(), in->Y, nullptr, 0, yt));
   *out = h.release();
   return AQ_OK;
 }
@@ -691,6 +732,61 @@ extern "C" int aq_prep_cov_info(aq_prep_handle h, int32_t *d, uint8_t *absorbed,
   if (absorbed) std::copy(h->cov_absorbed.begin(), h->cov_absorbed.end(), absorbed);
   if (r2) std::copy(h->cov_r2.begin(), h->cov_r2.end(), r2);
   return AQ_OK;
+}
+
+// ---- the four entries in one, with the transform of Y (include/atlasqtl_hip.h, aq_prepare_data_opt; kernels in aq_ytrans_kernels.h) ----
+extern "C" int aq_prepare_data_opt(const aq_prep_input *in, const aq_prep_bed_input *bed, const aq_prep_cov *cov, const aq_prep_ytrans *yt,
+                                   aq_prep_handle *out) {
+  if (!out) return aq_fail(AQ_ERR_ARG, "aq_prepare_data_opt: NULL argument");
+  *out = nullptr;
+  if ((in == nullptr) == (bed == nullptr)) return aq_fail(AQ_ERR_ARG, "aq_prepare_data_opt: exactly one of in and bed must be non-NULL");
+  const bool with_cov = cov && cov->d != 0;
+  if (!yt || yt->method == 0) {                // exactly the entry that the other arguments name
+    if (in) return aq_prepare_data_impl(in, cov, out, with_cov ? "aq_prepare_data_cov" : "aq_prepare_data");
+    return aq_prepare_data_bed_impl(bed, cov, out);
+  }
+  if (in) return aq_prepare_data_impl(in, cov, out, "aq_prepare_data_opt", yt);
+  return aq_prepare_data_bed_impl(bed, cov, out, yt);
+}
+
+extern "C" int aq_prep_ytrans_info(aq_prep_handle h, int32_t *method, double *offset, int32_t *n_obs, int32_t *n_tied) {
+  if (!h) return aq_fail(AQ_ERR_ARG, "aq_prep_ytrans_info: NULL handle");
+  if (method) *method = h->yt_method;
+  if (h->yt_method == 0) return AQ_OK;
+  if (offset) *offset = h->yt_offset;
+  if (n_obs) std::copy(h->yt_nobs.begin(), h->yt_nobs.end(), n_obs);
+  if (n_tied) std::copy(h->yt_ntied.begin(), h->yt_ntied.end(), n_tied);
+  return AQ_OK;
+}
+
+extern "C" int aq_rank_int(const double *Y, int32_t n, int32_t q, double offset, double *out, int32_t *n_obs, int32_t *n_tied, int32_t device) {
+  if (!Y || !out) return aq_fail(AQ_ERR_ARG, "aq_rank_int: NULL argument");
+  if (n < 2 || q < 1) return aq_fail(AQ_ERR_ARG, "aq_rank_int: n >= 2, q >= 1 required");
+  const aq_prep_ytrans yt{1, offset};
+  AQ_TRY(aq_ytrans_check_args(&yt, n, "aq_rank_int"));
+  AQ_TRY(aq_need_device(device));
+  const size_t nq = (size_t)n * q;
+  AqDev<double> dY;
+  AqDev<int> dcnt;                             // n_obs, n_tied, degenerate: q each
+  std::vector<int> cnt((size_t)3 * q);
+  AQ_TRY(dY.alloc(nq));
+  AQ_TRY(dcnt.alloc(cnt.size()));
+  AQ_HIP(hipMemcpy(dY.get(), Y, nq * sizeof(double), hipMemcpyHostToDevice));
+  AQ_TRY(aq_ytrans_device(dY.get(), dY.get(), n, q, offset, dcnt.get(), dcnt.get() + q, dcnt.get() + 2 * (size_t)q, "aq_rank_int", nullptr));
+  AQ_HIP(hipMemcpy(cnt.data(), dcnt.get(), cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
+  AQ_TRY(aq_ytrans_check_degenerate(cnt.data() + 2 * (size_t)q, q));
+  AQ_HIP(hipMemcpy(out, dY.get(), nq * sizeof(double), hipMemcpyDeviceToHost));
+  if (n_obs) std::copy(cnt.begin(), cnt.begin() + q, n_obs);
+  if (n_tied) std::copy(cnt.begin() + q, cnt.begin() + 2 * (size_t)q, n_tied);
+  return AQ_OK;
+}
+
+extern "C" int aq_ytrans_plan_query(int32_t n, int32_t q, int64_t free_bytes, aq_ytrans_plan *out) {
+  if (!out) return aq_fail(AQ_ERR_ARG, "aq_ytrans_plan_query: NULL argument");
+  *out = aq_ytrans_plan{};
+  std::string err;
+  const int rc = aq_ytrans_make_plan(n, q, (long long)free_bytes, aq_ytrans_env_force(), "aq_ytrans_plan_query", out, &err);
+  return rc == AQ_OK ? AQ_OK : aq_fail(rc, err);
 }
 
 // ---- LD pruning of a finished handle (include/atlasqtl_hip.h, aq_prep_ld_prune; kernels in aq_ld_kernels.h) ----

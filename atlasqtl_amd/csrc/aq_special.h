@@ -39,6 +39,43 @@ AQ_HD double aq_log_ndtr(double x) {
   return -0.5 * x * x - log(-x) - AQ_LOG_SQRT_2PI + log(ser);
 }
 
+// Phi^-1(u) for 0 < u <= 1/2 (the lower half: the caller mirrors the upper one, so that u and 1 - u give exact negatives);
+// u = 1/2 gives exactly 0, u = 0 gives -inf, anything else outside the range NaN.  qnorm(u) of R.
+// No table: the three-term rational start of Abramowitz & Stegun 26.2.23 (|error| < 4.5e-4), then three Halley steps on
+// f(x) = Phi(x) - u, f'' / f' = -x:  s = f / phi(x),  x <- x - s / (1 + s x / 2).  The error is cubed per step with a constant
+// x^2 / 12 + 1 / 6 (4.5e-4 -> 2e-10 -> below rounding), so the third step is the polish and what is left is the error of the
+// residual f.  That is taken without cancellation: 0.5 erfc(-x / sqrt2) - u in the tail (the subtraction of two nearly equal
+// numbers is exact, the error is erfc's relative one, and in x it is that over |x| M(x), M the Mills ratio phi / Phi), and
+// (1/2 - u) - 0.5 erf(-x / sqrt2) for u >= 1/4 (1/2 - u is exact there, and erf keeps its relative accuracy as x -> 0, so
+// the result is good RELATIVE to x down to x = 0).  Below u = 1e-290 erfc runs out of normal numbers and the same steps are
+// taken on log Phi(x) - log u with aq_log_ndtr and the Mills ratio.
+#define AQ_SQRT_2PI 2.50662827463100050241576528481105
+AQ_HD double aq_ndtri(double u) {
+  if (!(u > 0.0) || u > 0.5) return u == 0.0 ? -INFINITY : NAN;
+  if (u == 0.5) return 0.0;
+  const double lu = log(u);
+  const double t = sqrt(-2.0 * lu);
+  double x = (2.515517 + t * (0.802853 + t * 0.010328)) / (1.0 + t * (1.432788 + t * (0.189269 + t * 0.001308))) - t;
+  if (u < 1e-290) {
+    for (int it = 0; it < 3; it++) {
+      const double lp = aq_log_ndtr(x);
+      const double f = lp - lu;
+      const double M = exp(-0.5 * x * x - AQ_LOG_SQRT_2PI - lp);
+      x -= f / (M + 0.5 * f * (x + M));
+    }
+    return x;
+  }
+  const bool mid = u >= 0.25;
+  const double d = 0.5 - u;
+  for (int it = 0; it < 3; it++) {
+    const double z = -x * AQ_INV_SQRT2;
+    const double f = mid ? d - 0.5 * erf(z) : 0.5 * erfc(z) - u;
+    const double s = f * (AQ_SQRT_2PI * exp(0.5 * x * x));
+    x -= s / (1.0 + 0.5 * s * x);
+  }
+  return x;
+}
+
 // The same function with a short dependency chain, for the sequential SNP recursion where every dependent fp64
 // operation costs ~10 ns per SNP and trait tile: exp(-|x|) by a two-step Cody-Waite reduction and a degree-12
 // Taylor polynomial in Estrin form (depth 4 instead of 11), the reciprocal of 1 + e in [1, 2] by v_rcp_f64 and two

@@ -24,8 +24,7 @@
 static_assert(64 % AQ_RSEL_BITS == 0, "AQ_RSEL_BITS must divide 64");
 static_assert(AQ_RSEL_MAX_PREFIX * AQS_NBIN * 8 <= 32768, "histogram must fit 32 KB of LDS");
 
-// IEEE double -> key whose unsigned order is the order of the values (negative: all bits flipped; otherwise: sign bit set)
-__host__ __device__ inline uint64_t aq_key_of_bits(uint64_t b) { return (b >> 63) ? ~b : (b | 0x8000000000000000ull); }
+// (aq_key_of_bits, the order-preserving key of a double: aq_internal.h)
 static double aq_value_of_key(uint64_t k) {
   const uint64_t b = (k >> 63) ? (k ^ 0x8000000000000000ull) : ~k;
   double v;

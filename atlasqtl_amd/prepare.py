@@ -10,7 +10,8 @@ does not take, are regressed out of X and Y there as well (aq_prepare_data_cov),
 linkage disequilibrium there before the fit (aq_prep_ld_prune).  The genetic relationship matrix of the prepared matrix is
 formed there too (aq_prep_grm); its leading eigenvectors, the genotype principal components, are taken here on the host --
 or, with solver="subspace", by subspace iteration whose operator K Q = Xs (Xs' Q) / p1 runs there (aq_prep_grm_apply) without
-K ever being formed, for any n the fit takes.
+K ever being formed, for any n the fit takes.  The rank-based inverse normal transform of the traits (transform_y=, rank_normalize)
+runs there as well, before everything else that is done to Y (aq_prepare_data_opt, aq_rank_int).
 """
 from __future__ import annotations
 
@@ -115,7 +116,8 @@ class PreparedData:
     """The standardised compact X (n x p) and the centred Y resident on the GPU (aq_prepare_data).  VbRun takes it in place
     of the X array; `Y` is the host copy of the centred responses (n x q, small) that the hyper-parameter rules need."""
 
-    def __init__(self, handle, n, p, q, Y, device, genotype_counts=None, n_cov=0, cov_absorbed=None, cov_r2=None):
+    def __init__(self, handle, n, p, q, Y, device, genotype_counts=None, n_cov=0, cov_absorbed=None, cov_r2=None, y_n_obs=None,
+                 y_n_tied=None):
         self.handle, self.n, self.p, self.q, self.Y, self.device = handle, n, p, q, Y, device
         self.shape = (n, p)
         # LD pruning (prepare_on_device(ld_prune=)), per column given: removed for LD (bool), the index of the kept column that
@@ -125,6 +127,9 @@ class PreparedData:
         # covariates regressed out of X and Y (0: none); per column given: absorbed by them (bool), and the share of its
         # variance they explain (NaN for a constant column).  None without covariates.
         self.n_cov, self.cov_absorbed, self.cov_r2 = n_cov, cov_absorbed, cov_r2
+        # transform_y: per trait, its observed values and those among them that share their value with another one.  None
+        # without the transform.
+        self.y_n_obs, self.y_n_tied = y_n_obs, y_n_tied
 
     @property
     def x_ptr(self):
@@ -204,6 +209,69 @@ PC_SOLVER_DEFAULTS = {"solver": "eigh", "oversample": None, "tol": 1e-8, "max_it
 COV_MAX_D = 96                # AQ_COV_MAX_D: covariates that aq_prepare_data_cov takes
 LD_PRUNE_DEFAULTS = {"r2": 0.8, "window": 500, "window_bp": None, "groups": None, "positions": None}
 LD_MAX_WINDOW = 4096          # AQ_LD_MAX_WINDOW of csrc/aq_ld_kernels.h
+
+
+TRANSFORM_Y_DEFAULTS = {"method": "int", "offset": 0.375}
+
+
+def transform_y_options(transform_y):
+    """The `transform_y` argument of atlasqtl() / prepare_on_device checked on the host: None (no transform), "int", or a dict
+    with the keys 'method' ("int", the rank-based inverse normal transform) and, optionally, 'offset' (c in [0, 1/2]: 3/8 Blom,
+    the default; 0 van der Waerden; 1/2 rankit).  Returns None or {"method": "int", "offset": c}."""
+    if transform_y is None:
+        return None
+    if isinstance(transform_y, str):
+        transform_y = {"method": transform_y}
+    if not isinstance(transform_y, dict) or "method" not in transform_y or set(transform_y) - set(TRANSFORM_Y_DEFAULTS):
+        raise AtlasqtlError("transform_y must be None, 'int' or a dict with the key 'method' and, optionally, 'offset'.")
+    o = {**TRANSFORM_Y_DEFAULTS, **transform_y}
+    if not isinstance(o["method"], str) or o["method"] != "int":
+        raise AtlasqtlError(f"transform_y: method must be 'int' (the rank-based inverse normal transform), not {o['method']!r}.")
+    o["offset"] = _check_int_offset(o["offset"], "transform_y")
+    return o
+
+
+def _check_int_offset(c, what):
+    if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, float, np.integer, np.floating)) or not (0.0 <= float(c) <= 0.5):
+        raise AtlasqtlError(f"{what}: offset must be a number in [0, 1/2], not {c!r}.")
+    return float(c)
+
+
+def _ytrans_arg(transform_y):
+    """The transform as aq_prepare_data_opt takes it: (AqPrepYtrans, the options), or (None, None)."""
+    o = transform_y_options(transform_y)
+    if o is None:
+        return None, None
+    yt = _lib.AqPrepYtrans()
+    yt.method, yt.offset = 1, o["offset"]
+    return yt, o
+
+
+def rank_normalize(Y, offset=0.375, device=0):
+    """The rank-based inverse normal transform of every column of Y (n x q, NaN = missing and stays NaN) on the GPU
+    (aq_rank_int): Phi^-1((r - offset) / (m + 1 - 2 offset)) with r the 1-based rank among the m observed values of the column,
+    ties given their average rank.  Returns dict(Y n x q, n_obs (q), n_tied (q): the observed values of a column that share
+    their value with another one).  A column with fewer than two distinct observed values raises AtlasqtlError."""
+    c = _check_int_offset(offset, "rank_normalize")
+    try:
+        Ya = np.asfortranarray(Y, dtype=np.float64)
+    except (TypeError, ValueError):
+        Ya = None
+    if Ya is None or Ya.ndim != 2 or Ya.shape[0] < 2 or Ya.shape[1] < 1:
+        raise AtlasqtlError("rank_normalize: Y must be a numeric matrix with at least 2 rows and 1 column.")
+    n, q = Ya.shape
+    if n > N_MAX:
+        raise AtlasqtlError(f"rank_normalize: n = {n} samples given, at most {N_MAX} are supported.")
+    out = np.empty((n, q), order="F")
+    n_obs = np.zeros(q, dtype=np.int32); n_tied = np.zeros(q, dtype=np.int32)
+    L = _lib.lib()
+    rc = L.aq_rank_int(_lib.as_dp(Ya), n, q, c, _lib.as_dp(out), _lib.as_ip(n_obs), _lib.as_ip(n_tied), int(device))
+    if rc != 0:
+        msg = L.aq_last_error().decode("utf-8", "replace")
+        if rc == 1:
+            raise AtlasqtlError(msg)
+        raise _lib.AtlasqtlHipError(f"aq_rank_int: [{rc}] {msg}")
+    return dict(Y=out, n_obs=n_obs, n_tied=n_tied)
 
 
 def _is_whole(x):
@@ -301,7 +369,7 @@ def _ld_prune_handle(ret, ld):
     return ret
 
 
-def prepare_on_device(Y, X, device=0, covariates=None, ld_prune=None):
+def prepare_on_device(Y, X, device=0, covariates=None, ld_prune=None, transform_y=None):
     """scale(X), constant / duplicate-column removal and the centring of Y on the GPU (R/prepare_atlasqtl.R:57-83).
     X: float64 (n x p), int8 dosages (1 byte per genotype: the fp64 matrix is then never formed on the host), or a
     plink.PlinkBed (2 bits per genotype: the packed blocks of the .bed are uploaded and unpacked on the GPU; the returned
@@ -314,6 +382,9 @@ def prepare_on_device(Y, X, device=0, covariates=None, ld_prune=None):
     position within window_bp of its own has r(i, j)^2 > r2; the first one wins.  The PreparedData then holds the pruned matrix
     and ld_removed / ld_of / ld_r2 per column given.  A PlinkBed's chromosomes are the default groups, its base-pair positions
     the default positions.
+    transform_y: None, "int" or {"method": "int", "offset": 0.375} (transform_y_options): the rank-based inverse normal transform
+    of every column of Y over its observed rows, before the regression on the covariates or the centring (rank_normalize); the
+    PreparedData then carries y_n_obs and y_n_tied.  X is prepared as without it.
     Returns (PreparedData, bool_cst_x [p], bool_coll_x [p, original numbering], dup_of [p])."""
     import ctypes as C
     from .plink import PlinkBed
@@ -321,17 +392,18 @@ def prepare_on_device(Y, X, device=0, covariates=None, ld_prune=None):
     n, q = Y.shape
     cov, Z = _covariates_arg(covariates, n)
     ld, ld_arrays = _ld_arg(ld_prune, X)                       # checked here, before the first device call
-    ret = _prepare_unpruned(Y, X, device, cov)
+    yt = _ytrans_arg(transform_y)[0]
+    ret = _prepare_unpruned(Y, X, device, cov, yt)
     return ret if ld is None else _ld_prune_handle(ret, ld)
 
 
-def _prepare_unpruned(Y, X, device, cov):
-    """prepare_on_device before any pruning: Y float64 in Fortran order, cov from _covariates_arg."""
+def _prepare_unpruned(Y, X, device, cov, yt=None):
+    """prepare_on_device before any pruning: Y float64 in Fortran order, cov from _covariates_arg, yt from _ytrans_arg."""
     import ctypes as C
     from .plink import PlinkBed
     n, q = Y.shape
     if isinstance(X, PlinkBed):
-        return _prepare_bed_on_device(Y, X, device, cov)
+        return _prepare_bed_on_device(Y, X, device, cov, yt)
     pin = _lib.AqPrepInput()
     if np.asarray(X).dtype == np.int8:
         Xa = np.asfortranarray(X)
@@ -344,6 +416,9 @@ def _prepare_unpruned(Y, X, device, cov):
     p = Xa.shape[1]
     pin.n, pin.p, pin.q, pin.Y, pin.device = n, p, q, _lib.as_dp(Y), int(device)
     h = C.c_void_p()
+    if yt is not None:
+        rc = _lib.lib().aq_prepare_data_opt(C.byref(pin), None, None if cov is None else C.byref(cov), C.byref(yt), C.byref(h))
+        return _prepared_from_handle(rc, h, "aq_prepare_data_opt", n, p, q, device, cov=cov is not None, ytrans=True)
     if cov is None:
         rc = _lib.lib().aq_prepare_data(C.byref(pin), C.byref(h))
         return _prepared_from_handle(rc, h, "aq_prepare_data", n, p, q, device)
@@ -351,7 +426,7 @@ def _prepare_unpruned(Y, X, device, cov):
     return _prepared_from_handle(rc, h, "aq_prepare_data_cov", n, p, q, device, cov=True)
 
 
-def _prepared_from_handle(rc, h, what, n, p, q, device, bed=False, cov=False):
+def _prepared_from_handle(rc, h, what, n, p, q, device, bed=False, cov=False, ytrans=False):
     """The return value of prepare_on_device from the handle aq_prepare_data / aq_prepare_data_bed made (or their error)."""
     import ctypes as C
     if rc != 0:
@@ -376,11 +451,15 @@ def _prepared_from_handle(rc, h, what, n, p, q, device, bed=False, cov=False):
         _lib.check(_lib.lib().aq_prep_cov_info(h, C.byref(d), absorbed.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.as_dp(r2)),
                    "aq_prep_cov_info")
         n_cov, absorbed = int(d.value), absorbed.astype(bool)
+    y_n_obs = y_n_tied = None
+    if ytrans:
+        y_n_obs = np.zeros(q, dtype=np.int32); y_n_tied = np.zeros(q, dtype=np.int32)
+        _lib.check(_lib.lib().aq_prep_ytrans_info(h, None, None, _lib.as_ip(y_n_obs), _lib.as_ip(y_n_tied)), "aq_prep_ytrans_info")
     return (PreparedData(h, n, int(pk.value), q, Yc, int(device), genotype_counts=counts, n_cov=n_cov, cov_absorbed=absorbed,
-                         cov_r2=r2), cst.astype(bool), coll.astype(bool), dup)
+                         cov_r2=r2, y_n_obs=y_n_obs, y_n_tied=y_n_tied), cst.astype(bool), coll.astype(bool), dup)
 
 
-def _prepare_bed_on_device(Y, bed, device, cov=None):
+def _prepare_bed_on_device(Y, bed, device, cov=None, yt=None):
     """prepare_on_device for a plink.PlinkBed: the packed blocks go to aq_prepare_data_bed as they are."""
     import ctypes as C
     n, q = Y.shape
@@ -394,17 +473,20 @@ def _prepare_bed_on_device(Y, bed, device, cov=None):
     pin.Y, pin.device = _lib.as_dp(Y), int(device)
     pin.count_a2, pin.missing = int(bed.count == "A2"), int(bed.missing == "mean")
     h = C.c_void_p()
-    if cov is None:
+    what = "aq_prepare_data_bed" + ("" if cov is None else "_cov")
+    if yt is not None:
+        what = "aq_prepare_data_opt"
+        rc = _lib.lib().aq_prepare_data_opt(None, C.byref(pin), None if cov is None else C.byref(cov), C.byref(yt), C.byref(h))
+    elif cov is None:
         rc = _lib.lib().aq_prepare_data_bed(C.byref(pin), C.byref(h))
     else:
         rc = _lib.lib().aq_prepare_data_bed_cov(C.byref(pin), C.byref(cov), C.byref(h))
     del blocks
-    return _prepared_from_handle(rc, h, "aq_prepare_data_bed" + ("" if cov is None else "_cov"), n, bed.p, q, device, bed=True,
-                                 cov=cov is not None)
+    return _prepared_from_handle(rc, h, what, n, bed.p, q, device, bed=True, cov=cov is not None, ytrans=yt is not None)
 
 
 def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path,
-                  names_x=None, names_y=None, device=0, covariates=None, ld_prune=None):
+                  names_x=None, names_y=None, device=0, covariates=None, ld_prune=None, transform_y=None):
     """R/prepare_atlasqtl.R:8-87.  Returns dict(Y, X, bool_rmvd_x, initial_colnames_X,
     rmvd_cst_x, rmvd_coll_x, names_x, names_y, genotype_counts, n_covariates, rmvd_cov_x, cov_r2_x); X is a PreparedData (the
     standardised matrix lives on the GPU), Y the centred responses on the host.  With covariates (prepare_on_device) both are
@@ -413,7 +495,9 @@ def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_p
     the default names_x and whose per-variant genotype counts are returned as genotype_counts (None otherwise).
     With ld_prune (prepare_on_device) bool_rmvd_x and names_x account for the predictors removed for LD as well; rmvd_ld_x maps
     each of them to the kept predictor that tags it and ld_r2_x holds, per predictor given, its r^2 with that one (NaN: kept or
-    removed for another reason).  Both are None without pruning."""
+    removed for another reason).  Both are None without pruning.
+    With transform_y (prepare_on_device) Y is rank-normalised before all that; transform_y holds the options used and y_n_obs /
+    y_n_tied the observed and the tied values per trait.  All three are None without it."""
     from .plink import PlinkBed
     is_bed = isinstance(X, PlinkBed)
     check_vector_(user_seed, "user_seed", size=1, null_ok=True)
@@ -446,7 +530,11 @@ def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_p
         names_y = [f"Resp_{k + 1}" for k in range(q)]
 
     # scale(X), rm_constant_, rm_collinear_, centring of Y: on the device (aq_prepare.hip); X stays there
-    prep, bool_cst_x, bool_coll_full, dup_of = prepare_on_device(Y, X, device, covariates, ld_prune)
+    yt_opts = transform_y_options(transform_y)
+    if yt_opts is None:
+        prep, bool_cst_x, bool_coll_full, dup_of = prepare_on_device(Y, X, device, covariates, ld_prune)
+    else:
+        prep, bool_cst_x, bool_coll_full, dup_of = prepare_on_device(Y, X, device, covariates, ld_prune, transform_y=yt_opts)
     rmvd_cst_x = [names_x[j] for j in np.where(bool_cst_x)[0]] if bool_cst_x.any() else None
     names_after_cst = [nm for nm, b in zip(names_x, bool_cst_x) if not b]
     bool_rmvd_x = bool_cst_x | bool_coll_full
@@ -458,6 +546,7 @@ def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_p
     return dict(Y=prep.Y, X=prep, bool_rmvd_x=bool_rmvd_x, initial_colnames_X=names_after_cst,
                 rmvd_cst_x=rmvd_cst_x, rmvd_coll_x=rmvd_coll_x, genotype_counts=prep.genotype_counts,
                 n_covariates=prep.n_cov, cov_r2_x=prep.cov_r2, rmvd_ld_x=rmvd_ld_x, ld_r2_x=prep.ld_r2,
+                transform_y=yt_opts, y_n_obs=prep.y_n_obs, y_n_tied=prep.y_n_tied,
                 rmvd_cov_x=[names_x[j] for j in np.where(prep.cov_absorbed)[0]] if prep.n_cov and prep.cov_absorbed.any() else None,
                 names_x=[nm for nm, b in zip(names_x, bool_rmvd_x) if not b], names_y=list(names_y))
 

@@ -599,6 +599,55 @@ int aq_prep_grm_apply(aq_prep_handle h, const double *Q, int32_t L, double *Z_ou
 int aq_pcs_plan_query(int32_t n, int32_t p1, int32_t L, int32_t ncu, int64_t free_bytes, aq_pcs_plan *out);
 int aq_prep_grm_apply_time(aq_prep_handle h, int32_t L, int32_t reps, double *ms_per_call, aq_pcs_plan *plan_out);
 
+/* ------------------------------------------------------------------------------------------
+ * Rank-based inverse normal transform (INT) of the traits, the step every molecular-QTL pipeline applies to expression,
+ * protein or metabolite levels before anything else: the model is Gaussian per trait, and a handful of outlying samples in
+ * a few skewed traits otherwise show up as spurious hotspots.  The reference has no such argument (its users transform in R).
+ * For trait k with observed rows O_k, m = |O_k| (NaN is missing and stays NaN): r_i is the 1-based rank of y_ik among the
+ * observed values of the column, ties given their AVERAGE rank; -0.0 and +0.0 are equal and tie; -inf and +inf rank as the
+ * extremes.  Then
+ *   y_ik <- Phi^-1((r_i - c) / (m + 1 - 2 c)),   0 <= c <= 1/2:  c = 3/8 Blom (the usual choice), 0 van der Waerden, 1/2 rankit.
+ * It runs BEFORE everything else that is done to Y: with covariates the transformed column is residualised, without them it
+ * is centred, and the two missingness guards keep their messages and their order.  A column with fewer than two distinct
+ * observed values is AQ_ERR_ARG, "column k of Y has fewer than two distinct observed values; it cannot be rank-normalised"
+ * (k 1-based), after the two guards.
+ * One workgroup per trait sorts the column's order-preserving 64-bit keys (NaN above every value) by a bitonic network --
+ * in LDS up to 16 384 samples, beyond that (up to 82 944, AQ_N_MAX) in device memory, chunk by chunk through LDS -- and every
+ * sample finds the number of keys below and not above its own by two binary searches: the doubled rank 2 r is an exact
+ * integer whatever the ties, and the argument of Phi^-1 is ONE fp64 division, (t - 2 c) / (2 m + 2 - 4 c) with t = min(2 r,
+ * 2 m + 2 - 2 r), the sign applied afterwards: ranks r and m + 1 - r give exact negatives of each other, the middle rank
+ * exactly 0, and the two paths the same bits.  The environment variable AQ_YT_PATH (lds | global; tests) forces a path where
+ * the column fits both.
+ *   aq_prepare_data_opt    the four aq_prepare_data* entries in one: exactly one of in / bed is non-NULL; cov and yt may be
+ *                          NULL.  yt == NULL or yt->method == 0: exactly the entry that the other arguments name.
+ *   aq_prep_ytrans_info    method (0: the handle was made without a transform, nothing else is written), offset = c, and per
+ *                          trait n_obs[q] = m and n_tied[q] = the observed values that share their value with another one.
+ *                          Any pointer may be NULL.
+ *   aq_rank_int            the transform alone.  Y, out: n x q column-major, host (out may be Y); n_obs, n_tied: q each, may
+ *                          be NULL.  No missingness guard: only the column without two distinct observed values is refused.
+ *   aq_ytrans_plan_query   the launch plan without a device: path 0 (LDS) or 1 (device memory), the padded key count, the
+ *                          dynamic LDS of a workgroup, the traits per launch and the scratch for their keys, scratch_bytes <=
+ *                          free_bytes.  It reads AQ_YT_PATH as the entries do.  A column whose keys do not fit free_bytes and
+ *                          n > 82 944 are AQ_ERR_UNSUPPORTED, as in aq_plan_query.
+ * An unknown method, c outside [0, 1/2] or NaN, a NULL argument and n > 82 944 are AQ_ERR_ARG before any device call.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_prep_ytrans {
+  int32_t method;   /* 0 none, 1 rank-based inverse normal */
+  double offset;    /* c */
+} aq_prep_ytrans;
+typedef struct aq_ytrans_plan {
+  int32_t path;               /* 0: keys in LDS; 1: keys in device memory                    */
+  int32_t n_pad;              /* keys per column: n padded to a power of two                 */
+  int32_t lds_bytes;          /* dynamic LDS of a workgroup: 8 min(n_pad, 16 384) <= 160 KiB */
+  int32_t traits_per_batch;   /* workgroups per launch                                       */
+  int64_t scratch_bytes;      /* path 1: 8 n_pad traits_per_batch; path 0: 0                 */
+} aq_ytrans_plan;
+int aq_prepare_data_opt(const aq_prep_input *in, const aq_prep_bed_input *bed, const aq_prep_cov *cov, const aq_prep_ytrans *yt,
+                        aq_prep_handle *out);
+int aq_prep_ytrans_info(aq_prep_handle h, int32_t *method, double *offset, int32_t *n_obs, int32_t *n_tied);
+int aq_rank_int(const double *Y, int32_t n, int32_t q, double offset, double *out, int32_t *n_obs, int32_t *n_tied, int32_t device);
+int aq_ytrans_plan_query(int32_t n, int32_t q, int64_t free_bytes, aq_ytrans_plan *out);
+
 #ifdef __cplusplus
 }
 #endif
