@@ -1,14 +1,14 @@
 // aq_cov_kernels.h -- covariate adjustment of the device-side preparation: the columns of X and
 // of Y are replaced by their least-squares residuals on W = [1, Z] before the existing pipeline standardises / centres them.
 // The host hands over Qt, an orthonormal basis of W's columns stored [D][n] (row l = basis vector l, so that the lanes of a
-// wave read consecutive samples of one vector: coalesced); Qt[0][i] = 1 / sqrt(n).  Included by aq_prepare.hip after its
-// aq_xval and aq_block_sum, which the kernels use.
+// wave read consecutive samples of one vector: coalesced); Qt[0][i] = 1 / sqrt(n).  Included by aq_prep_cov.hip.
 //
 // Both kernels are deterministic and do not depend on the column index: one workgroup of 256 threads per column, thread t
 // sums samples t, t + 256, ... in that order, the 64 partial sums of a wave go through one shuffle tree and the four waves'
 // sums are added in wave order.  Two bit-identical columns of X therefore give bit-identical residuals, which the bitwise
 // duplicate detection that follows relies on.
 #pragma once
+#include "aq_prep_dev.h"     // aq_xval, aq_block_sum
 
 #define AQ_COV_MAX_D 96      // covariates; D = d + 1 basis vectors with the intercept
 #define AQ_COV_CHUNK 32      // dot products a thread accumulates at a time

@@ -1,6 +1,6 @@
 // aq_grm_kernels.h -- the genetic relationship matrix of the device-side preparation:
 // K = Xs Xs' / p1 over all p1 columns of the compact standardised X, n x n, on the f64 matrix pipe.  Included by
-// aq_prepare.hip; the launch plan is aq_grm_plan.h.  Every kernel is a plain grid: no workgroup waits for another one,
+// aq_prep_grm.hip; the launch plan is aq_grm_plan.h.  Every kernel is a plain grid: no workgroup waits for another one,
 // nothing spins, and no floating-point atomic is used, so two calls on one handle give the same bits.
 //
 // Xs is [p1][n], every column contiguous.  K[a, b] = sum_j Xs[a, j] Xs[b, j] / p1.

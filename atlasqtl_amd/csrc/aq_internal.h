@@ -90,6 +90,7 @@ struct aq_vb;
 
 // aq_ops.hip
 int aq_probe_dmode(int *dmode);   // accumulator layout of v_mfma_f64_16x16x4 on the current device (probed once per process)
+int aq_need_acc_layout(const char *who);   // ... and the error of entry `who` unless it is row = (lane >> 4) + 4 reg
 
 // aq_vb_sweep.hip
 int aq_check_chain_error(aq_vb *s);   // a bounded wait inside a sweep kernel expired: the handle has failed

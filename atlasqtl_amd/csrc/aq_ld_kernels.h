@@ -1,6 +1,6 @@
 // aq_ld_kernels.h -- LD pruning of the device-side preparation: the banded correlation matrix of the
 // compact standardised X on the f64 matrix pipe, the first-one-wins scan over its thresholded bits, the r^2 of every removed
-// column with its tag, and the gather of the kept columns.  Included by aq_prepare.hip.  Every kernel is a plain grid: no
+// column with its tag, and the gather of the kept columns.  Included by aq_prep_ld.hip.  Every kernel is a plain grid: no
 // workgroup waits for another one, nothing spins.
 //
 // Xs is [p1][n], every column contiguous, mean 0 and sum of squares n - 1, so r(i, j) = (Xs_i . Xs_j) / (n - 1).  Entry

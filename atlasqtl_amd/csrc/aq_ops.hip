@@ -83,6 +83,17 @@ int aq_probe_dmode(int *dmode) {
   return AQ_OK;
 }
 
+// the f64 MFMA accumulator map that the band, GRM and operator kernels of the prepare side are written for
+// (row = (lane >> 4) + 4 reg), checked on the device
+int aq_need_acc_layout(const char *who) {
+  int dmode = 0;
+  AQ_TRY(aq_probe_dmode(&dmode));
+  if (dmode != 0)
+    return aq_fail(AQ_ERR_DEVICE, std::string(who) + ": the band kernel is written for the accumulator map row = (lane >> 4) + 4 reg "
+                                                     "of v_mfma_f64_16x16x4_f64, which this device does not have");
+  return AQ_OK;
+}
+
 // The planner without a device: the plan fields of aq_vb_status for given sizes, missingness counts, CU count and memory, with
 // the hooks taken from `overrides` ("NAME=value NAME=value") and never from the process environment.
 extern "C" int aq_plan_query(int32_t n, int32_t p, int32_t q, int32_t max_missing, int32_t max_short_list, int32_t ncu, int64_t total_bytes,

@@ -1,6 +1,6 @@
 // aq_pcs_kernels.h -- one application of the relationship operator to a block of vectors:
 // Z = Xs (Xs' Q) / p1, n x L, without the n x n matrix K = Xs Xs' / p1 itself -- what subspace iteration for the leading
-// eigenvectors of K needs.  Two tall-skinny products on the f64 matrix pipe.  Included by aq_prepare.hip after
+// eigenvectors of K needs.  Two tall-skinny products on the f64 matrix pipe.  Included by aq_prep_grm.hip after
 // aq_grm_kernels.h (aq_grm_load / aq_grm_store stage the panels of the second product); the launch plan is aq_pcs_plan.h.
 // Every kernel is a plain grid: no workgroup waits for another one, nothing spins, and no floating-point atomic is used, so
 // two calls on one handle give the same bits.
@@ -41,6 +41,7 @@
 // the columns in index order and divides by p1: the trace of K without K.
 #pragma once
 #include "aq_pcs_plan.h"
+#include "aq_prep_dev.h"      // aq_block_sum
 
 typedef double aq_pcs_d2 __attribute__((ext_vector_type(2)));
 

@@ -1,5 +1,5 @@
 // aq_ytrans_kernels.h -- the rank-based inverse normal transform of the traits (include/atlasqtl_hip.h, aq_rank_int and
-// aq_prepare_data_opt; planned by aq_ytrans_plan.h), for gfx950, with its host sequencing.  Included by aq_prepare.hip.
+// aq_prepare_data_opt; planned by aq_ytrans_plan.h), for gfx950.  Included by aq_prep_ytrans.hip, which sequences the kernels.
 //
 // One workgroup per trait.  The column's values become order-preserving 64-bit keys (aq_key_of_bits, -0.0 first made +0.0;
 // NaN and the padding up to a power of two take ~0, above every value), the keys are sorted by a bitonic network, and every
@@ -15,9 +15,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <cstdlib>
-#include <cstring>
-#include <string>
 
 #include "aq_internal.h"
 #include "aq_special.h"        // aq_ndtri
@@ -143,62 +140,4 @@ __global__ __launch_bounds__(AQ_YT_BLOCK) void aq_k_yt_global(const double *Y, i
     }
   }
   aq_yt_finish(g, n_pad, Y + base, n, c, out + base, cnt, nobs + blockIdx.x, ntied + blockIdx.x, degenerate + blockIdx.x);
-}
-
-// ---- host sequencing ----
-// AQ_YT_PATH of the environment: 0 (absent), AQ_YT_FORCE_LDS, AQ_YT_FORCE_GLOBAL, or -1 for anything else
-static inline int aq_ytrans_env_force() {
-  const char *e = getenv("AQ_YT_PATH");
-  if (!e || !*e) return 0;
-  if (!strcmp(e, "lds")) return AQ_YT_FORCE_LDS;
-  if (!strcmp(e, "global")) return AQ_YT_FORCE_GLOBAL;
-  return -1;
-}
-
-static inline int aq_ytrans_check_offset(double c, const char *who) {
-  if (!(c >= 0.0 && c <= 0.5))                 // NaN fails both
-    return aq_fail(AQ_ERR_ARG, std::string(who) + ": the offset c must lie in [0, 1/2], " + std::to_string(c) + " given");
-  return AQ_OK;
-}
-
-// dY (n x q column-major, device) -> dOut (may be dY); dnobs, dntied, ddeg: q ints each on the device.  Asynchronous after
-// the plan: the caller's next copy from the device waits for the kernels.  The current device is the arrays' one.
-static int aq_ytrans_device(const double *dY, double *dOut, int n, int q, double c, int *dnobs, int *dntied, int *ddeg, const char *who,
-                            aq_ytrans_plan *plan_out) {
-  size_t free_b = 0, tot_b = 0;
-  AQ_HIP(hipMemGetInfo(&free_b, &tot_b));
-  aq_ytrans_plan pl{};
-  std::string err;
-  const int rc = aq_ytrans_make_plan(n, q, (long long)(free_b - free_b / 16), aq_ytrans_env_force(), who, &pl, &err);
-  if (rc != AQ_OK) return aq_fail(rc, err);
-  if (plan_out) *plan_out = pl;
-  if (pl.path == 0) {
-    const int half = pl.n_pad / 2;
-    const int block = half < 64 ? 64 : (half > AQ_YT_BLOCK ? AQ_YT_BLOCK : half);
-    AQ_HIP(hipFuncSetAttribute((const void *)aq_k_yt_lds, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes));
-    hipLaunchKernelGGL(aq_k_yt_lds, dim3((unsigned)q), dim3((unsigned)block), (size_t)pl.lds_bytes, 0, dY, n, pl.n_pad, c, dOut, dnobs, dntied, ddeg);
-    AQ_HIP(hipGetLastError());
-    return AQ_OK;
-  }
-  AqDev<uint64_t> keys;
-  AQ_TRY(keys.alloc((size_t)pl.scratch_bytes / sizeof(uint64_t)));
-  const int chunk = pl.lds_bytes / (int)sizeof(uint64_t);
-  AQ_HIP(hipFuncSetAttribute((const void *)aq_k_yt_global, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes));
-  for (int k0 = 0; k0 < q; k0 += pl.traits_per_batch) {
-    const int nb = q - k0 < pl.traits_per_batch ? q - k0 : pl.traits_per_batch;
-    hipLaunchKernelGGL(aq_k_yt_global, dim3((unsigned)nb), dim3(AQ_YT_BLOCK), (size_t)pl.lds_bytes, 0, dY + (size_t)k0 * n, n, pl.n_pad, chunk, c,
-                       dOut + (size_t)k0 * n, keys.get(), dnobs + k0, dntied + k0, ddeg + k0);
-    AQ_HIP(hipGetLastError());
-  }
-  AQ_HIP(hipDeviceSynchronize());              // the scratch is released on return
-  return AQ_OK;
-}
-
-// the first column that cannot be rank-normalised, if any
-static int aq_ytrans_check_degenerate(const int *deg, int q) {
-  for (int k = 0; k < q; k++)
-    if (deg[k])
-      return aq_fail(AQ_ERR_ARG, "column " + std::to_string(k + 1) + " of Y has fewer than two distinct observed values; it cannot be "
-                                     "rank-normalised");
-  return AQ_OK;
 }

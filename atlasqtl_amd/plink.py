@@ -3,8 +3,8 @@
 The .bed holds 2 bits per genotype, variant-major: after the three header bytes 0x6c 0x1b 0x01 one block of
 stride = (n_file + 3) // 4 bytes per variant, in .bim order; sample s of a variant is (block[s >> 2] >> (2 * (s & 3))) & 3
 with 0 = homozygous A1, 1 = missing, 2 = heterozygous, 3 = homozygous A2.  Nothing is unpacked here: PlinkBed parses the
-two text files, validates the .bed and hands the packed blocks of the selected variants to aq_prepare_data_bed, which
-unpacks them on the GPU (csrc/aq_prepare.hip).  The .bed is memory-mapped, so only the selected blocks are read.
+two text files, validates the .bed and hands the packed blocks of the selected variants to the library (the .bed input of
+aq_prepare_data_opt), which unpacks them on the GPU (csrc/aq_prep_bed.hip).  The .bed is memory-mapped, so only the selected blocks are read.
 """
 from __future__ import annotations
 

@@ -5,7 +5,9 @@ Follows R/prepare_atlasqtl.R:8-124 (``prepare_data_``, ``check_verbose_``,
 ``rm_constant_``, ``rm_collinear_``).  Error messages keep the reference's
 wording so tests read like the reference's own.  The argument checks run on the host;
 the O(n p) work itself -- scale(X), the removal of constant and duplicated columns,
-the centring of Y -- runs on the GPU (aq_prepare_data) and X stays there.  Covariates, which the reference
+the centring of Y -- runs on the GPU (aq_prepare_data) and X stays there: one call of aq_prepare_data_opt, the
+five aq_prepare_data* entries in one, whose pipeline is csrc/aq_prepare.hip; the .bed decode, the covariates, the transform of
+Y, LD pruning and the relationship matrix are the csrc/aq_prep_*.hip units.  Covariates, which the reference
 does not take, are regressed out of X and Y there as well (aq_prepare_data_cov), and the compact matrix can be pruned for
 linkage disequilibrium there before the fit (aq_prep_ld_prune).  The genetic relationship matrix of the prepared matrix is
 formed there too (aq_prep_grm); its leading eigenvectors, the genotype principal components, are taken here on the host --
@@ -415,15 +417,18 @@ def _prepare_unpruned(Y, X, device, cov, yt=None):
         raise AtlasqtlError("X and Y must have the same number of samples.")
     p = Xa.shape[1]
     pin.n, pin.p, pin.q, pin.Y, pin.device = n, p, q, _lib.as_dp(Y), int(device)
+    return _prepare_opt(pin, False, cov, yt, n, p, q, device)
+
+
+def _prepare_opt(pin, bed, cov, yt, n, p, q, device):
+    """aq_prepare_data_opt on the one input given (pin: an AqPrepBedInput if bed, else an AqPrepInput; cov, yt: None where
+    absent) and the return value of prepare_on_device from its handle.  An error names the entry that the arguments name."""
+    import ctypes as C
     h = C.c_void_p()
-    if yt is not None:
-        rc = _lib.lib().aq_prepare_data_opt(C.byref(pin), None, None if cov is None else C.byref(cov), C.byref(yt), C.byref(h))
-        return _prepared_from_handle(rc, h, "aq_prepare_data_opt", n, p, q, device, cov=cov is not None, ytrans=True)
-    if cov is None:
-        rc = _lib.lib().aq_prepare_data(C.byref(pin), C.byref(h))
-        return _prepared_from_handle(rc, h, "aq_prepare_data", n, p, q, device)
-    rc = _lib.lib().aq_prepare_data_cov(C.byref(pin), C.byref(cov), C.byref(h))
-    return _prepared_from_handle(rc, h, "aq_prepare_data_cov", n, p, q, device, cov=True)
+    rc = _lib.lib().aq_prepare_data_opt(None if bed else C.byref(pin), C.byref(pin) if bed else None, None if cov is None else C.byref(cov),
+                                        None if yt is None else C.byref(yt), C.byref(h))
+    what = "aq_prepare_data_opt" if yt is not None else "aq_prepare_data" + ("_bed" if bed else "") + ("" if cov is None else "_cov")
+    return _prepared_from_handle(rc, h, what, n, p, q, device, bed=bed, cov=cov is not None, ytrans=yt is not None)
 
 
 def _prepared_from_handle(rc, h, what, n, p, q, device, bed=False, cov=False, ytrans=False):
@@ -460,7 +465,8 @@ def _prepared_from_handle(rc, h, what, n, p, q, device, bed=False, cov=False, yt
 
 
 def _prepare_bed_on_device(Y, bed, device, cov=None, yt=None):
-    """prepare_on_device for a plink.PlinkBed: the packed blocks go to aq_prepare_data_bed as they are."""
+    """prepare_on_device for a plink.PlinkBed: the packed blocks go to the library as they are (the .bed input of
+    aq_prepare_data_opt)."""
     import ctypes as C
     n, q = Y.shape
     if bed.n != n:
@@ -472,17 +478,7 @@ def _prepare_bed_on_device(Y, bed, device, cov=None, yt=None):
     pin.sample_idx = None if bed.sample_index is None else _lib.as_ip(bed.sample_index)
     pin.Y, pin.device = _lib.as_dp(Y), int(device)
     pin.count_a2, pin.missing = int(bed.count == "A2"), int(bed.missing == "mean")
-    h = C.c_void_p()
-    what = "aq_prepare_data_bed" + ("" if cov is None else "_cov")
-    if yt is not None:
-        what = "aq_prepare_data_opt"
-        rc = _lib.lib().aq_prepare_data_opt(None, C.byref(pin), None if cov is None else C.byref(cov), C.byref(yt), C.byref(h))
-    elif cov is None:
-        rc = _lib.lib().aq_prepare_data_bed(C.byref(pin), C.byref(h))
-    else:
-        rc = _lib.lib().aq_prepare_data_bed_cov(C.byref(pin), C.byref(cov), C.byref(h))
-    del blocks
-    return _prepared_from_handle(rc, h, what, n, bed.p, q, device, bed=True, cov=cov is not None, ytrans=yt is not None)
+    return _prepare_opt(pin, True, cov, yt, n, bed.p, q, device)       # `blocks` lives until the call has returned
 
 
 def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_path,
@@ -529,12 +525,9 @@ def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_p
     if names_y is None:
         names_y = [f"Resp_{k + 1}" for k in range(q)]
 
-    # scale(X), rm_constant_, rm_collinear_, centring of Y: on the device (aq_prepare.hip); X stays there
+    # scale(X), rm_constant_, rm_collinear_, centring of Y: on the device (csrc/aq_prepare.hip and its aq_prep_*.hip units); X stays there
     yt_opts = transform_y_options(transform_y)
-    if yt_opts is None:
-        prep, bool_cst_x, bool_coll_full, dup_of = prepare_on_device(Y, X, device, covariates, ld_prune)
-    else:
-        prep, bool_cst_x, bool_coll_full, dup_of = prepare_on_device(Y, X, device, covariates, ld_prune, transform_y=yt_opts)
+    prep, bool_cst_x, bool_coll_full, dup_of = prepare_on_device(Y, X, device, covariates, ld_prune, transform_y=yt_opts)
     rmvd_cst_x = [names_x[j] for j in np.where(bool_cst_x)[0]] if bool_cst_x.any() else None
     names_after_cst = [nm for nm, b in zip(names_x, bool_cst_x) if not b]
     bool_rmvd_x = bool_cst_x | bool_coll_full

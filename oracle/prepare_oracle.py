@@ -1,5 +1,5 @@
 """CPU restatement (NumPy) of the O(n p) half of the reference's prepare_data_ -- test infrastructure, the checker of the
-device-side aq_prepare_data (atlasqtl_amd/csrc/aq_prepare.hip); the product never imports it.
+device-side aq_prepare_data (atlasqtl_amd/csrc/aq_prepare.hip and the aq_prep_*.hip units around it); the product never imports it.
 
 Follows R/prepare_atlasqtl.R:57-83 (scale(X), the removals, centring of Y) and R/utils.R:276-343 (rm_constant_, rm_collinear_).
 Parity unpinned with respect to reference-produced numbers (R is absent from the image; the reference's tests hold no

@@ -1,7 +1,8 @@
 // cov_kernels_cpu.cpp -- runs the two kernels of atlasqtl_amd/csrc/aq_cov_kernels.h on the CPU, one workgroup at a time: 256
 // host threads per workgroup, a barrier for __syncthreads and a per-wave barrier pair for each shuffle.  It checks the
 // kernels' indexing, barrier placement and arithmetic where no GPU is at hand (tools/cov_kernels_cpu.py builds and drives
-// it); it says nothing about speed.  aq_xval and aq_block_sum restate the two helpers of aq_prepare.hip that the header uses.
+// it); it says nothing about speed.  aq_xval and aq_block_sum come from aq_prep_dev.h, which the header includes: the macros and
+// threadIdx / __syncthreads below are what that header needs on the CPU.
 #include <barrier>
 #include <thread>
 #include <vector>
@@ -33,19 +34,6 @@ using std::min;
 #define __shared__ static
 #define __restrict__
 double lds[16384];
-template <typename T> inline double aq_xval(const T *X, size_t i) { return (double)X[i]; }
-inline double aq_block_sum(double v, double *sh) {
-  const int t = threadIdx.x;
-  sh[t] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) sh[t] += sh[t + s];
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
 #include "aq_cov_kernels_host.h"   // the header with its extern __shared__ line rewritten (cov_kernels_cpu.py)
 
 template <typename F> static void run_block(int b, F f) {

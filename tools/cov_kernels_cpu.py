@@ -24,7 +24,8 @@ def build(tmp):
     with open(os.path.join(tmp, "aq_cov_kernels_host.h"), "w") as f:
         f.write(src)
     out = os.path.join(tmp, "libcovcpu.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-fPIC", "-shared", "-pthread", "-I", tmp, "-o", out,
+    subprocess.check_call(["g++", "-std=c++20", "-O1", "-fPIC", "-shared", "-pthread", "-I", tmp, "-I", os.path.join(ROOT, "atlasqtl_amd", "csrc"),
+                           "-o", out,
                            os.path.join(ROOT, "tools", "cov_kernels_cpu.cpp")])
     return C.CDLL(out)
 
