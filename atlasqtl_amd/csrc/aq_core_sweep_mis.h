@@ -21,7 +21,11 @@
 // redundantly -- so delta is bitwise identical in all of them and no second exchange is needed.  Workgroups of a
 // tile are adjacent in dispatch order, hence a waiting one always has its partners resident or next to be dispatched.
 // Everything per (j,k) uses the same trait-tiled arrays and the same 6 column sums as aq_trait_wave.h (the generic
-// kernel, which stays the fallback for more than AQ_MIS_MMAX missing samples in a trait and for n > 16384).
+// kernel, which stays the fallback for more than AQ_MIS_MMAX missing samples in a trait).  Neither of the two serves
+// n > 10240: since the wide sample split that is the look-ahead kernel's alone (aq_plan_kernel refuses AQ_KERNEL >= 2 there;
+// its own test in.n <= 16384 is never the one that decides).  No hook-free plan picks NT = 16 with C >= 6 -- (16, 5) holds
+// 10240 samples and is found first in aq_plan_mis -- but AQ_MIS_C = 6, 7, 8 reaches them for 1024 C < n <= 10240 (n_pad up to
+// 16384, the last parts holding nothing but padding).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "aq_special.h"
