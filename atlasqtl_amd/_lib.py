@@ -77,6 +77,11 @@ class AqYtransPlan(C.Structure):
                 ("scratch_bytes", C.c_int64)]
 
 
+class AqMscreenPlan(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("sample_chunk", C.c_int32), ("tiles_p", C.c_int32), ("tiles_q", C.c_int32), ("masked", C.c_int32),
+                ("lds_bytes", C.c_int32), ("n_tiles", C.c_int64), ("scratch_bytes", C.c_int64)]
+
+
 class AqVbMultiOut(C.Structure):
     _fields_ = [
         ("beta_vb", dp), ("gam_vb", dp), ("mu_beta_vb", dp), ("theta_vb", dp), ("zeta_vb", dp), ("lam2_inv_vb", dp),
@@ -183,6 +188,10 @@ SYMBOLS = {
     "aq_prep_ytrans_info": (C.c_int, [C.c_void_p, ip, dp, ip, ip]),
     "aq_rank_int": (C.c_int, [dp, C.c_int32, C.c_int32, C.c_double, dp, ip, ip, C.c_int32]),
     "aq_ytrans_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(AqYtransPlan)]),
+    "aq_mscreen_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AqMscreenPlan)]),
+    "aq_prep_marginal": (C.c_int, [C.c_void_p, dp, C.c_int64, ip, ip, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), ip, dp,
+                                   C.POINTER(C.c_int64), dp]),
+    "aq_prep_marginal_time": (C.c_int, [C.c_void_p, C.c_int32, dp, C.POINTER(AqMscreenPlan)]),
 }
 
 _lib = None

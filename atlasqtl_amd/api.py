@@ -14,6 +14,7 @@ import numpy as np
 from .core import atlasqtl_global_local_core_
 from .postproc import hotspot_sizes, six_numbers_host_, sparse_output_options, value_summary
 from .hyper_init import prepare_list_hyper_, prepare_list_init_
+from .marginal import screen_arg, screen_handle
 from .prepare import (check_annealing_, check_positive_, check_vector_, check_verbose_, covariates_with_genotype_pcs,
                       prepare_data_, transform_y_options)
 
@@ -74,7 +75,7 @@ def warn_tied_traits_(n_obs, n_tied, names_y):
 def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, verbose=1, list_hyper=None,
              list_init=None, save_hyper=False, save_init=False, full_output=False, thinned_elbo_eval=True,
              checkpoint_path=None, trace_path=None, add_collinear_back=False, device=0, device_init=False,
-             sparse_output=None, covariates=None, ld_prune=None, genotype_pcs=None, transform_y=None):
+             sparse_output=None, covariates=None, ld_prune=None, genotype_pcs=None, transform_y=None, marginal_screen=None):
     """R/atlasqtl.R:179-322.
 
     X: a float64 matrix, int8 dosages, or a plink.PlinkBed (a PLINK 1 .bed / .bim / .fam fileset, unpacked on the GPU): the
@@ -120,7 +121,13 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
     levels go through before a QTL analysis; with covariates the transformed response is residualised.  The genotype PCs
     never see Y.  The result then carries `transform_y` (the options used), `y_n_obs` and `y_n_tied` (per response, its observed
     values and those among them that share their value with another one).  A response more than half of whose observed
-    values are tied is not made normal by ranks: one warning names such responses (the first ten)."""
+    values are tied is not made normal by ranks: one warning names such responses (the first ten).
+
+    marginal_screen = True or {"p_value": ..., "fdr": ..., "max_pairs": ...} (at most one of the first two; True or neither:
+    Bonferroni, 0.05 / (p q)): before the fit, test every predictor against every response on its own on the GPU
+    (marginal_screen()), on the very handle the fit is about to use, so X is prepared once.  The result then carries
+    `marginal`: the result of marginal_screen() -- its `assoc` table, `rs_thres` (the marginal hotspot sizes, to hold the
+    fit's against), `best_snp` ... -- without the rmvd_* fields, which this result has itself."""
     if ld_prune is not None and add_collinear_back:
         raise ValueError("add_collinear_back=True cannot be combined with ld_prune: a predictor removed for LD is not a copy of "
                          "the predictor that tags it, and the add-back maps assume copies (they would hand it the tag's "
@@ -137,6 +144,7 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
     check_verbose_(verbose)
     check_annealing_(anneal)
     yt_opts = transform_y_options(transform_y)                              # before the first device call
+    screen = screen_arg(marginal_screen)
     pcs = None
     if genotype_pcs is not None:
         covariates, pcs = covariates_with_genotype_pcs(Y, X, covariates, genotype_pcs, device)
@@ -163,6 +171,7 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
         print("**************************************************** \n"
               f"Number of samples: {n}\nNumber of (non-redundant) candidate predictors: {p}\n"
               f"Number of responses: {q}\n**************************************************** \n")
+    marginal = None if screen is None else screen_handle(Xs, dat["names_x"], dat["names_y"], **screen)
     df = 1                                                                  # :272  (hs <- TRUE, debug <- TRUE :267-268)
     res = atlasqtl_global_local_core_(Yc, Xs, shr_fac_inv, None if anneal is None else tuple(anneal), df, tol,
                                       maxit, verbose, list_hyper, list_init, checkpoint_path, trace_path,
@@ -175,6 +184,8 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
     res["rmvd_cst_x"] = dat["rmvd_cst_x"]
     res["rmvd_coll_x"] = dat["rmvd_coll_x"]
     res["names_x"], res["names_y"] = dat["names_x"], dat["names_y"]
+    if marginal is not None:
+        res["marginal"] = marginal
     if dat["genotype_counts"] is not None:                # X = PlinkBed: 4 x p (hom A1, het, hom A2, missing), before removals
         res["genotype_counts"] = dat["genotype_counts"]
     if covariates is not None:

@@ -1,6 +1,6 @@
-// aq_prep.h -- the prepare side's analogue of aq_vb.h: the handle of aq_prepare_data* and the prototype of every host function
-// that one aq_prep*.hip unit calls in another.  Every unit that defines or calls one of them includes this header, so a
-// definition that differs from its declaration is a compile error.
+// aq_prep.h -- the prepare side's analogue of aq_vb.h: the handle of aq_prepare_data*, the prototype of every host function
+// that one aq_prep*.hip unit calls in another, and the timing loop that the *_time entries share.  Every unit that defines
+// or calls one of them includes this header, so a definition that differs from its declaration is a compile error.
 #pragma once
 #include <stdint.h>
 #include <vector>
@@ -52,3 +52,28 @@ int aq_ytrans_device(const double *dY, double *dOut, int n, int q, double c, int
                      aq_ytrans_plan *plan_out);
 // the first column that cannot be rank-normalised, if any
 int aq_ytrans_check_degenerate(const int *deg, int q);
+
+// the *_time entries (aq_prep_grm.hip, aq_prep_marginal.hip): `launch` once as a warm-up, then `reps` times between two events:
+// the milliseconds of one call
+template <typename F>
+int aq_time_launches(int reps, double *ms_per_call, F launch) {
+  AQ_TRY(launch());
+  AQ_HIP(hipDeviceSynchronize());
+  struct Events {                              // both destroyed on every way out
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t ev : e)
+        if (ev) hipEventDestroy(ev);
+    }
+  } ev;
+  AQ_HIP(hipEventCreate(&ev.e[0]));
+  AQ_HIP(hipEventCreate(&ev.e[1]));
+  AQ_HIP(hipEventRecord(ev.e[0], 0));
+  for (int r = 0; r < reps; r++) AQ_TRY(launch());
+  AQ_HIP(hipEventRecord(ev.e[1], 0));
+  AQ_HIP(hipEventSynchronize(ev.e[1]));
+  float ms = 0.f;
+  AQ_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  *ms_per_call = (double)ms / reps;
+  return AQ_OK;
+}

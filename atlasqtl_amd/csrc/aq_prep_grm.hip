@@ -10,7 +10,7 @@
 #include <stdint.h>
 #include <string>
 #include <vector>
-#include "aq_prep.h"          // aq_prep; aq_internal.h: aq_fail, AQ_HIP, aq_need_device, aq_need_acc_layout, AqDev
+#include "aq_prep.h"          // aq_prep, aq_time_launches; aq_internal.h: aq_fail, AQ_HIP, aq_need_device, aq_need_acc_layout, AqDev
 #include "aq_grm_kernels.h"   // aq_k_grm_partial, aq_k_grm_reduce; aq_grm_make_plan
 #include "aq_pcs_kernels.h"   // aq_k_pcs_pack_q, aq_k_pcs_xtq, aq_k_pcs_xt, aq_k_pcs_reduce, aq_k_pcs_colss; aq_pcs_make_plan
 
@@ -28,30 +28,6 @@ static int aq_plan_facts(const aq_prep *h, const char *env, int max_splits, cons
   }
   f->ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   f->free_bytes = (long long)free_b;
-  return AQ_OK;
-}
-
-// `launch` once as a warm-up, then `reps` times between two events: the milliseconds of one call
-template <typename F>
-static int aq_time_launches(int reps, double *ms_per_call, F launch) {
-  AQ_TRY(launch());
-  AQ_HIP(hipDeviceSynchronize());
-  struct Events {                              // both destroyed on every way out
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() {
-      for (hipEvent_t ev : e)
-        if (ev) hipEventDestroy(ev);
-    }
-  } ev;
-  AQ_HIP(hipEventCreate(&ev.e[0]));
-  AQ_HIP(hipEventCreate(&ev.e[1]));
-  AQ_HIP(hipEventRecord(ev.e[0], 0));
-  for (int r = 0; r < reps; r++) AQ_TRY(launch());
-  AQ_HIP(hipEventRecord(ev.e[1], 0));
-  AQ_HIP(hipEventSynchronize(ev.e[1]));
-  float ms = 0.f;
-  AQ_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-  *ms_per_call = (double)ms / reps;
   return AQ_OK;
 }
 

@@ -174,6 +174,30 @@ class PreparedData:
                                                 C.byref(tr) if return_trace else None), "aq_prep_grm_apply")
         return (out, float(tr.value)) if return_trace else out
 
+    def marginal(self, r2_cut, cap, dense=False):
+        """The marginal screen of the matrix as it stands against every trait: aq_prep_marginal.  r2_cut: q cutoffs on r^2
+        (trait t selects r^2 >= r2_cut[t]; +inf: none); cap: rows of the table (0 only counts).  Returns dict(snp, trait, r:
+        the min(n_pairs, cap) rows written, in no particular order; n_pairs: the full count; rs: selected traits per
+        predictor (p); best_snp, best_r: per trait, the predictor of largest r^2 (-1 / NaN: none defined); n_undefined;
+        r_dense: p x q with dense=True, else None)."""
+        import ctypes as C
+        cut = np.ascontiguousarray(r2_cut, dtype=np.float64)
+        if cut.shape != (self.q,):
+            raise AtlasqtlError(f"marginal: r2_cut must hold one cutoff per trait ({self.q}), not {cut.shape}.")
+        cap = int(cap)
+        rows = max(cap, 0)
+        snp = np.empty(rows, dtype=np.int32); trait = np.empty(rows, dtype=np.int32); r = np.empty(rows)
+        rs = np.zeros(self.p, dtype=np.int64); best_snp = np.empty(self.q, dtype=np.int32); best_r = np.empty(self.q)
+        n_pairs, n_undef = C.c_int64(0), C.c_int64(0)
+        r_dense = np.empty((self.p, self.q), order="F") if dense else None
+        _lib.check(_lib.lib().aq_prep_marginal(self.handle, _lib.as_dp(cut), cap, _lib.as_ip(snp), _lib.as_ip(trait), _lib.as_dp(r),
+                                               C.byref(n_pairs), rs.ctypes.data_as(C.POINTER(C.c_int64)), _lib.as_ip(best_snp),
+                                               _lib.as_dp(best_r), C.byref(n_undef), None if r_dense is None else _lib.as_dp(r_dense)),
+                   "aq_prep_marginal")
+        k = min(int(n_pairs.value), rows)
+        return dict(snp=snp[:k], trait=trait[:k], r=r[:k], n_pairs=int(n_pairs.value), rs=rs, best_snp=best_snp, best_r=best_r,
+                    n_undefined=int(n_undef.value), r_dense=r_dense)
+
     def close(self):
         if self.handle is not None:
             _lib.lib().aq_prep_destroy(self.handle)

@@ -648,6 +648,52 @@ int aq_prep_ytrans_info(aq_prep_handle h, int32_t *method, double *offset, int32
 int aq_rank_int(const double *Y, int32_t n, int32_t q, double offset, double *out, int32_t *n_obs, int32_t *n_tied, int32_t device);
 int aq_ytrans_plan_query(int32_t n, int32_t q, int64_t free_bytes, aq_ytrans_plan *out);
 
+/* ------------------------------------------------------------------------------------------
+ * Marginal screen of a finished handle: every predictor of the handle's CURRENT matrix Xs (p1 columns) tested against every
+ * trait of Yc on its own, the classical univariate scan that a joint fit is compared with.  For predictor s and trait t, over
+ * the m_t rows O_t where the trait is observed:
+ *   Sxy = sum x y,  Sx = sum x,  Sxx = sum x^2,  Syy_t = sum y^2 (added in index order; Yc is centred over O_t, so sum y = 0)
+ *   Vx = Sxx - Sx^2 / m_t,   r = Sxy / sqrt(Vx Syy_t),   df_t = m_t - 2 - n_cov,   t = r sqrt(df_t / (1 - r^2)).
+ * A pair is UNDEFINED when Vx <= 1e-10 Sxx (the predictor is constant over O_t), Syy_t = 0 or df_t < 1: its r is NaN, it is
+ * never selected, and it is counted in n_undefined.  With covariates and missing values the predictors were residualised
+ * over all rows, not over O_t: the same approximation as in the fit.
+ * The p1 q work runs on the f64 matrix pipe, one workgroup per tile of predictors x traits contracting over all n samples
+ * (2 n p1 q flop for complete Y; with missing values three products from the same operand reads, 6 n p1 q), and the
+ * selection happens in registers: nothing of size p1 q is allocated unless r_dense is given.  No floating-point atomics: two
+ * calls on one handle give the same set of rows and the same bits in every other output; the order of the rows is unspecified.
+ *   aq_prep_marginal       r2_cut: q doubles, trait t selects the pairs with r^2 >= r2_cut[t] (+inf: none).  cap: rows of the
+ *                          table snp / trait / r (int32, int32, double; cap = 0 only counts); n_pairs: the number of
+ *                          selected pairs, always the full count, of which min(n_pairs, cap) rows are written.  rs: int64[p1],
+ *                          selected traits per predictor.  best_snp: int32[q], the predictor of largest r^2 per trait, the
+ *                          lowest index on a tie, -1 where the trait has no defined pair; best_r: double[q], its r (NaN
+ *                          there).  n_undefined: int64.  r_dense: NULL, or p1 x q column-major on the host.  Any output may
+ *                          be NULL.  The handle is not changed.
+ *   aq_mscreen_plan_query  the launch plan without a device, a pure function of its arguments: tile edge (complete Y: 128 when
+ *                          the 128 x 128 tiles alone give every CU a workgroup, else 64; masked: 64), samples per step, tile
+ *                          counts (the grid is n_tiles = tiles_p tiles_q workgroups), static LDS and scratch.  The environment
+ *                          variable AQ_MSCREEN_TILE (64 | 128; tests) forces the tile edge of the complete instance in
+ *                          aq_prep_marginal; the query does not read it.
+ *   aq_prep_marginal_time  measurement: the kernels of one screen `reps` times between two events after one warm-up, counting
+ *                          only (cap = 0, r2_cut = 40 / (40 + df_t)), without the copies and without the per-trait pass over
+ *                          Yc (Syy_t, m_t: O(n q), it also decides the plan and runs before); ms_per_call and, if not NULL,
+ *                          the plan used.
+ * A NULL r2_cut, cap < 0, a NULL handle or a NaN cutoff are AQ_ERR_ARG, in this order, before any device call.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_mscreen_plan {
+  int32_t tile;               /* edge of a tile: predictors and traits per workgroup, 64 or 128 */
+  int32_t sample_chunk;       /* samples staged per step                                     */
+  int32_t tiles_p;            /* ceil(p1 / tile)                                             */
+  int32_t tiles_q;            /* ceil(q / tile)                                              */
+  int32_t masked;             /* 1: the three-stream instance for Yc with missing values     */
+  int32_t lds_bytes;          /* static LDS of a workgroup, <= 64 KiB                        */
+  int64_t n_tiles;            /* tiles_p tiles_q: the grid                                   */
+  int64_t scratch_bytes;      /* each trait's best predictor per row of tiles: 12 tiles_p q  */
+} aq_mscreen_plan;
+int aq_mscreen_plan_query(int32_t n, int32_t p1, int32_t q, int32_t masked, int32_t ncu, aq_mscreen_plan *out);
+int aq_prep_marginal(aq_prep_handle h, const double *r2_cut, int64_t cap, int32_t *snp, int32_t *trait, double *r, int64_t *n_pairs,
+                     int64_t *rs, int32_t *best_snp, double *best_r, int64_t *n_undefined, double *r_dense);
+int aq_prep_marginal_time(aq_prep_handle h, int32_t reps, double *ms_per_call, aq_mscreen_plan *plan_out);
+
 #ifdef __cplusplus
 }
 #endif
