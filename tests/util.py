@@ -20,9 +20,9 @@ def shard_lists(list_hyper, list_init, k0, k1):
     return lh, li
 
 
-def gloo_rank(rank, world, port):
-    """The prologue of a spawned worker: the repository on sys.path and this process in a gloo group of `world` ranks.
-    Returns torch.distributed (the worker ends with its destroy_process_group())."""
+def gloo_rank(rank, world, port, backend="gloo"):
+    """The prologue of a spawned worker: the repository on sys.path and this process in a group of `world` ranks (gloo unless
+    another backend is named).  Returns torch.distributed (the worker ends with its destroy_process_group())."""
     import os
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,7 +31,7 @@ def gloo_rank(rank, world, port):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group(backend, rank=rank, world_size=world)
     return dist
 
 
@@ -61,6 +61,38 @@ def make_problem(n, p, q, p_act=10, seed=123, init_seed=456, maf=0.2, p0=(5, 25)
     lh = H.prepare_list_hyper_(None, Y, pp, p0, bool_rmvd_x)
     li = H.prepare_list_init_(None, Y, pp, p0, bool_rmvd_x, q, init_seed)
     return dict(X=X, Y=Y, list_hyper=lh, list_init=li, truth=d, n=n, p=pp, q=q)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# Inputs of the trait-sharded runs (tests/test_shard_coverage_host.py asserts what they hold, tests/test_gpu_shard_schemes.py
+# runs them).
+SHARD_HETERO_SHAPE = (1300, 70, 48)
+SHARD_HETERO_NA = (16, 32, 0.05)            # traits [16, 32) lose 5 % of their samples
+SHARD_HETERO_TRAIT = (37, 1030)             # trait 37 loses 1030 of its 1300: more than AQ_MIS_MMAX = 1024
+SHARD_SMALL_Q = (17, 33, 40)
+
+
+def make_shard_problem(kind, q=None, na=0.0):
+    """kind = "hetero": make_problem(1300, 70, 48) whose three 16-trait shards fall to three kernel families -- traits [0, 16)
+    complete (look-ahead kernel), [16, 32) with 5 % NaN (its MASK instance), and trait 37 with 1030 missing samples, which hands
+    the whole shard [32, 48) to the generic kernel; every column re-centred over its observed rows.  The lists are those of the
+    complete problem.  kind = "small": make_problem(300, 70, q) with q in SHARD_SMALL_Q and na = 0 or 0.04 sprinkled uniformly."""
+    if kind == "small":
+        if q not in SHARD_SMALL_Q or na not in (0.0, 0.04):
+            raise ValueError("make_shard_problem: 'small' takes q in (17, 33, 40) and na in (0, 0.04)")
+        return make_problem(300, 70, q, p_act=8, prob_assoc=0.3, seed=123, na_frac=na)
+    if kind != "hetero" or q is not None or na:
+        raise ValueError("make_shard_problem: kind is 'hetero' (no further argument) or 'small'")
+    n, p, q = SHARD_HETERO_SHAPE
+    prob = make_problem(n, p, q, p_act=8, prob_assoc=0.3, seed=123)
+    rng = np.random.default_rng(9)
+    Y = np.array(prob["Y"], dtype=np.float64, order="F")
+    k0, k1, frac = SHARD_HETERO_NA
+    Y[:, k0:k1][rng.random((n, k1 - k0)) < frac] = np.nan
+    k, m = SHARD_HETERO_TRAIT
+    Y[rng.choice(n, size=m, replace=False), k] = np.nan
+    prob["Y"] = np.asfortranarray(Y - np.nanmean(Y, axis=0)[None, :])
+    return prob
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
