@@ -553,14 +553,16 @@ def atlasqtl_global_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, list_hyper,
 
 def atlasqtl_global_local_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, list_hyper, list_init,
                                 thinned_elbo_eval=True, debug=True, inner="c", trace=None,
-                                full_output=False, scheme="global_local", threads=1):
+                                full_output=False, scheme="global_local", threads=1, snapshots=None):
     """Restatement of atlasqtl_global_local_core_ (batch == "y").  scheme = "global": the p-vector part and the ELBO of
     atlasqtl_global_core_ (R/atlasqtl_global_core.R:236-256,372-421) instead; df in {1, 3} (df = 3 without annealing:
     the annealed update of lam2_inv_vb needs Kummer's 1F1, R/update_vb.R:76-81).  Y may contain
     NaN (missing); X must be complete and standardised.  ``inner``: "c" = C
     restatement of src/coreLoop.cpp, "pure" = Python restatement of the
     reference's pure-R inner update in the same natural order (tiny cases).
-    ``trace``: optional list receiving one dict per sweep (it, c, lb, ...)."""
+    ``trace``: optional list receiving one dict per sweep (it, c, lb, ...).
+    ``snapshots``: optional dict whose keys are sweep numbers; each is given a copy of the state after that sweep (the
+    result fields a test compares, and L_vb as that sweep computed it), so that one run serves several sweep counts."""
     Y = np.array(Y, dtype=np.float64, order="F")
     X = _F(X)
     n, p = X.shape
@@ -716,6 +718,13 @@ def atlasqtl_global_local_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, list_
 
         rec = dict(it=it, c=c_used, annealing=bool(annealing), lb=None, lentz_iters=lentz_iters,
                    sig02_inv_vb=sig02_inv_vb, sig2_inv_vb=float(sig2_inv_vb))
+        if snapshots is not None and it in snapshots:
+            glob = scheme == "global"
+            snapshots[it] = dict(it=it, gam_vb=np.array(gam_vb), mu_beta_vb=np.array(mu_beta_vb), theta_vb=np.array(theta_vb),
+                                 zeta_vb=np.array(zeta_vb), tau_vb=np.array(tau_vb), sig02_inv_vb=sig02_inv_vb,
+                                 lam2_inv_vb=np.ones(p) if glob else np.array(lam2_inv_vb),
+                                 sig2_theta_vb=np.full(p, float(sig2_theta_vb)) if glob else np.array(sig2_theta_vb),
+                                 L_vb=None if glob else np.array(L_vb), lentz_iters=lentz_iters)
         if annealing:                                                                 # :318-337
             sig2_zeta_vb = c * sig2_zeta_vb
             c = float(ladder[it]) if it < len(ladder) else 1.0    # ladder[it + 1], 1-based

@@ -356,6 +356,66 @@ def make_regime_problem(n, p, q, regime, na_frac=0.0, hyper="auto", seed=31, ini
                 carriers=carriers, dropped=dropped, active=active, scales=scales, regime=regime, hyper=hyper)
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# Inputs for the p- and q-vector kernels at the edges of their launch grids (tests/test_vector_coverage_host.py asserts what they
+# hold, tests/test_gpu_vector_edges.py runs them).
+VECTOR_SCALE = 4.0                          # Y[:, k] *= 10^s_k with s_k in [-4, 4], as regime_scales
+VECTOR_BORDER_TRAITS = (255, 256, 1023, 1024, 2047, 2048)      # blocks of 256 q-threads, strides of 1024
+
+
+def theta_for_L(list_init, q, positions, L, df=1):
+    """theta_vb values at `positions` that make the first sweep without annealing compute L_j = sig02_inv_vb shr (theta_j^2 +
+    sig2_theta_j) / (2 df) (R/atlasqtl_global_local_core.R:241 with m0 = 0, shr = q) equal to L; the signs alternate."""
+    positions = np.asarray(positions, dtype=np.int64)
+    L = np.broadcast_to(np.asarray(L, dtype=np.float64), positions.shape)
+    t2 = 2.0 * df * L / (float(list_init["sig02_inv_vb"]) * q) - np.asarray(list_init["sig2_theta_vb"])[positions]
+    if np.any(t2 < 0):
+        raise ValueError("theta_for_L: an L below the one theta_j = 0 gives")
+    return np.sqrt(t2) * np.where(positions % 2 == 0, 1.0, -1.0)
+
+
+def make_vector_problem(n, p, q, na_frac=0.0, theta=None, df=1, seed=123, hyper_seed=1031, init_seed=456, p0=(5, 25)):
+    """A problem in the form of make_problem in which every trait differs from its neighbours in every q-vector a kernel reads,
+    so that a trait index that slips by one across a thread-block or stride border changes a number a test reads: the data of
+    make_problem(n, p, q, p_act=8, prob_assoc=0.3, na_frac=na_frac, seed=seed) with Y[:, k] *= 10^s_k, s_k ~ U(-4, 4), and the
+    per-trait hyper-parameters and initial tau_vb of make_regime_problem(..., {"scale"}, hyper="per_trait"): eta_k ~ U(0.5, 20),
+    kappa_k = v_k U(0.2, 5), n0_k = the automatic n0 + U(-1.5, 1.5), nu = 0.5, rho = 3, t02 = 2.5 x the automatic one, tau_vb =
+    U(0.5, 2) / v_k.  (One builder for every p and q: regime_scales refuses q = 16 m + 1, make_regime_problem p <= 80.)  The
+    traits VECTOR_BORDER_TRAITS and the last two are associated with all eight active SNPs and have n0_k at the upper end.
+    theta: None, or (positions, L): list_init["theta_vb"] -- and nothing else -- is replaced at those predictors by
+    theta_for_L(..., df).  Extra keys: scales, theta_positions."""
+    d = synth.simulate(n, p, q, p_act=8, seed=seed, maf=0.2, prob_assoc=0.3, na_frac=na_frac)
+    hr = np.random.default_rng(hyper_seed)
+    scales = hr.uniform(-VECTOR_SCALE, VECTOR_SCALE, size=q)
+    border = [k for k in VECTOR_BORDER_TRAITS + (q - 2, q - 1) if 0 <= k < q]
+    # the traits on either side of a block or stride border of the q-threads, and the last two, are associated with every active
+    # SNP, and (below) get the upper end of n0, each its own value: their columns of gam_vb carry an above-average share of the
+    # sums over traits, so a sum that stops one trait short is short by a share that shows
+    signs = np.where(np.arange(d["act_x"].size) % 2 == 0, 1.0, -1.0)
+    d["Y"][:, border] += (d["X"][:, d["act_x"]] @ signs)[:, None]
+    X, Y, bool_cst, bool_coll = prepare_oracle.prepare_xy(d["Y"] * 10.0 ** scales[None, :], d["X"])
+    bool_rmvd_x = bool_cst.copy()
+    bool_rmvd_x[~bool_cst] = bool_coll
+    pp = X.shape[1]
+    auto = H.auto_set_hyper_(Y, pp, p0)
+    v = np.nanvar(Y, axis=0, ddof=1)
+    eta, kappa, shift = hr.uniform(0.5, 20.0, size=q), v * hr.uniform(0.2, 5.0, size=q), hr.uniform(-1.5, 1.5, size=q)
+    for i, k in enumerate(border):
+        shift[k] = 1.5 - 0.01 * i
+    lh = H.set_hyper(q, p, eta=eta, kappa=kappa, n0=auto["n0"] + shift, nu=0.5, rho=3.0, t02=2.5 * auto["t02"])
+    lh = H.prepare_list_hyper_(lh, Y, pp, p0, bool_rmvd_x)
+    li = H.ListInit(H.prepare_list_init_(None, Y, pp, p0, bool_rmvd_x, q, init_seed))
+    li.cls = "out_init"
+    li["tau_vb"] = hr.uniform(0.5, 2.0, size=q) / v
+    positions = np.zeros(0, dtype=np.int64)
+    if theta is not None:
+        positions = np.asarray(theta[0], dtype=np.int64)
+        th = np.array(li["theta_vb"], dtype=np.float64)
+        th[positions] = theta_for_L(li, q, positions, theta[1], df)
+        li["theta_vb"] = th
+    return dict(X=X, Y=Y, list_hyper=lh, list_init=li, truth=d, n=n, p=pp, q=q, scales=scales, theta_positions=positions)
+
+
 def operator_inputs(p, q, n=60, seed=0, mis=False, c=1.0):
     """Random but well-formed inputs of coreDualLoop / coreDualMisLoop (R layout)."""
     rng = np.random.default_rng(seed)
