@@ -82,6 +82,15 @@ class AqMscreenPlan(C.Structure):
                 ("lds_bytes", C.c_int32), ("n_tiles", C.c_int64), ("scratch_bytes", C.c_int64)]
 
 
+class AqPredictPlan(C.Structure):
+    _fields_ = [("sample_tiles", C.c_int32), ("trait_tiles", C.c_int32), ("sample_blocks", C.c_int32), ("trait_groups", C.c_int32),
+                ("splits", C.c_int32), ("chunk", C.c_int32), ("chunks_per_split", C.c_int32), ("n_pad", C.c_int32),
+                ("panel_bytes", C.c_int64), ("scratch_bytes", C.c_int64)]
+
+
+AQ_N_MAX = 82944          # most samples of one handle, and most rows of one aq_vb_predict call (csrc/aq_plan_const.h)
+
+
 class AqVbMultiOut(C.Structure):
     _fields_ = [
         ("beta_vb", dp), ("gam_vb", dp), ("mu_beta_vb", dp), ("theta_vb", dp), ("zeta_vb", dp), ("lam2_inv_vb", dp),
@@ -192,6 +201,11 @@ SYMBOLS = {
     "aq_prep_marginal": (C.c_int, [C.c_void_p, dp, C.c_int64, ip, ip, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), ip, dp,
                                    C.POINTER(C.c_int64), dp]),
     "aq_prep_marginal_time": (C.c_int, [C.c_void_p, C.c_int32, dp, C.POINTER(AqMscreenPlan)]),
+    "aq_predict_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AqPredictPlan)]),
+    "aq_vb_predict": (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int8), C.c_int32, dp, dp, dp]),
+    "aq_vb_fitted": (C.c_int, [C.c_void_p, C.c_void_p, dp]),
+    "aq_predict": (C.c_int, [dp, C.c_int32, C.c_int32, dp, C.POINTER(C.c_int8), C.c_int32, dp, dp, dp, C.c_int32]),
+    "aq_vb_predict_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, dp, C.POINTER(AqPredictPlan)]),
 }
 
 _lib = None

@@ -11,6 +11,7 @@ import warnings
 
 import numpy as np
 
+from . import prediction
 from .core import atlasqtl_global_local_core_
 from .postproc import hotspot_sizes, six_numbers_host_, sparse_output_options, value_summary
 from .hyper_init import prepare_list_hyper_, prepare_list_init_
@@ -75,7 +76,8 @@ def warn_tied_traits_(n_obs, n_tied, names_y):
 def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, verbose=1, list_hyper=None,
              list_init=None, save_hyper=False, save_init=False, full_output=False, thinned_elbo_eval=True,
              checkpoint_path=None, trace_path=None, add_collinear_back=False, device=0, device_init=False,
-             sparse_output=None, covariates=None, ld_prune=None, genotype_pcs=None, transform_y=None, marginal_screen=None):
+             sparse_output=None, covariates=None, ld_prune=None, genotype_pcs=None, transform_y=None, marginal_screen=None,
+             predict=None, fitted=False, keep_predictor=False):
     """R/atlasqtl.R:179-322.
 
     X: a float64 matrix, int8 dosages, or a plink.PlinkBed (a PLINK 1 .bed / .bim / .fam fileset, unpacked on the GPU): the
@@ -127,7 +129,23 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
     Bonferroni, 0.05 / (p q)): before the fit, test every predictor against every response on its own on the GPU
     (marginal_screen()), on the very handle the fit is about to use, so X is prepared once.  The result then carries
     `marginal`: the result of marginal_screen() -- its `assoc` table, `rs_thres` (the marginal hotspot sizes, to hold the
-    fit's against), `best_snp` ... -- without the rmvd_* fields, which this result has itself."""
+    fit's against), `best_snp` ... -- without the rmvd_* fields, which this result has itself.
+
+    predict = X_new (float64 or int8 dosages, n_new rows, the columns of X in its original numbering, finite): apply the fitted
+    model to new genotypes on the GPU before the run's state is released, so also with sparse_output.  The removed columns
+    (constant, duplicate, LD-pruned) are dropped and the others standardised by the fit's own means and standard deviations.  The
+    result then carries `predicted` (n_new x q): the genetic component of the responses on the scale of the prepared Y
+    (centred, and transformed if transform_y= was used).  Not with covariates= or genotype_pcs=; not a PlinkBed.
+    fitted=True: the result carries `X_beta_vb` (n x q), the same product for the samples of the fit, on the prepared X.
+    keep_predictor=True: the result carries `predictor` = {"kept_x", "x_center", "x_scale", "p_given"} -- the kept columns
+    in the original numbering and their standardisation -- with which predict(res, X_new) applies a dense result later.
+    Without these three arguments the result has none of these keys."""
+    X_new = None
+    if predict is not None:
+        prediction.refuse_with_covariates("predict=", covariates, genotype_pcs)
+        X_new = prediction.check_x_new(predict, (X.shape if hasattr(X, "shape") else np.shape(X))[1], "predict")
+    if keep_predictor:
+        prediction.refuse_with_covariates("keep_predictor=True", covariates, genotype_pcs)
     if ld_prune is not None and add_collinear_back:
         raise ValueError("add_collinear_back=True cannot be combined with ld_prune: a predictor removed for LD is not a copy of "
                          "the predictor that tags it, and the add-back maps assume copies (they would hand it the tag's "
@@ -173,13 +191,24 @@ def atlasqtl(Y, X, p0, anneal=(1, 2, 10), tol=0.1, maxit=1000, user_seed=None, v
               f"Number of responses: {q}\n**************************************************** \n")
     marginal = None if screen is None else screen_handle(Xs, dat["names_x"], dat["names_y"], **screen)
     df = 1                                                                  # :272  (hs <- TRUE, debug <- TRUE :267-268)
+    new_args = {}                                                           # only what was asked for reaches the core
+    predictor = None
+    if X_new is not None or keep_predictor:
+        predictor = prediction.predictor_of(bool_rmvd_x, *Xs.x_moments(len(bool_rmvd_x)))
+    if X_new is not None:
+        new_args["predict"] = {"X": X_new[:, predictor["kept_x"]], "center": predictor["x_center"], "scale": predictor["x_scale"],
+                               "checked": True}
+    if fitted:
+        new_args["fitted"] = True
     res = atlasqtl_global_local_core_(Yc, Xs, shr_fac_inv, None if anneal is None else tuple(anneal), df, tol,
                                       maxit, verbose, list_hyper, list_init, checkpoint_path, trace_path,
                                       full_output, thinned_elbo_eval, debug=True, device=device,
                                       # the collinear copies are added to the complete table; max_pairs cuts afterwards
                                       sparse_output=None if sparse is None else
-                                      {**sparse, "max_pairs": None if add_collinear_back else sparse["max_pairs"]})
+                                      {**sparse, "max_pairs": None if add_collinear_back else sparse["max_pairs"]}, **new_args)
     res = AtlasqtlResult(res)
+    if keep_predictor:
+        res["predictor"] = predictor
     res["p0"] = p0
     res["rmvd_cst_x"] = dat["rmvd_cst_x"]
     res["rmvd_coll_x"] = dat["rmvd_coll_x"]

@@ -21,7 +21,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, prediction
 from ._lib import AqVbProblem, AqVbStatus, as_dp, as_ip, check, lib
 from .operators import coreDualLoop, coreDualMisLoop  # noqa: F401
 from .postproc import (SPARSE_OUTPUT_DEFAULTS, _fetch_pairs, _key_to_double, assign_bFDR, associations,  # noqa: F401
@@ -126,7 +126,7 @@ class VbRun:
         q = Y.shape[1]
         if prep is not None and prep.device != int(device):
             raise ValueError("PreparedData lives on another device")
-        self.n, self.p, self.q = n, p, q
+        self.n, self.p, self.q, self.device = n, p, q, int(device)
         self.q_total = int(q if q_total is None else q_total)
         self.pg = process_group
         self.trait_offset = int(trait_offset)
@@ -347,6 +347,33 @@ class VbRun:
         check(lib().aq_vb_get_residual(self.h, as_dp(R)), "aq_vb_get_residual")
         return R
 
+    def predict(self, X_new, center=None, scale=None, checked=False):
+        """Yhat = Xt beta_vb (n_new x q) from the gam_vb / mu_beta_vb resident on the device, read in place on the f64 matrix
+        pipe (aq_vb_predict): nothing of size p q is formed, so it works where the p x q matrices never leave the GPU.
+        X_new: float64 or int8, n_new rows and the p columns of the fitted (compact) matrix; Xt = (X_new - center) / scale
+        per column, or X_new itself when both are None (already standardised).  Rows go to the library in batches of at
+        most prediction.PREDICT_MAX_ROWS.  With a process group each rank returns the columns of its own traits.
+        checked: X_new is what prediction.check_x_new returned for these p columns (the scan for non-finite values is not
+        repeated)."""
+        X = X_new if checked else prediction.check_x_new(X_new, self.p)
+        L = lib()
+
+        def call(xd, x8, n_rows, c, s, out):
+            check(L.aq_vb_predict(self.h, xd, x8, n_rows, c, s, out), "aq_vb_predict")
+
+        return prediction.apply_in_batches(call, X, self.q, center, scale)
+
+    def fitted(self, prep):
+        """X beta_vb (n x q), the reference's X_beta_vb, on the standardised X of the fit: a prepare.PreparedData (its matrix
+        is used where it lies on the device, aq_vb_fitted) or the host matrix the run was given."""
+        if not hasattr(prep, "x_ptr"):
+            return self.predict(prep)
+        if tuple(prep.shape) != (self.n, self.p) or prep.device != self.device:
+            raise ValueError("fitted: the PreparedData is not the n x p matrix of this run on its device")
+        out = np.empty((self.n, self.q), order="F")
+        check(lib().aq_vb_fitted(self.h, prep.x_ptr, as_dp(out)), "aq_vb_fitted")
+        return out
+
     def result(self, full_output=False, dense=True):
         """dense=False skips the p x q matrices (beta_vb, gam_vb, mu_beta_vb): aq_vb_get_result gets NULL for them."""
         out = _result_buffers(self.p, self.q, full_output, dense)
@@ -480,7 +507,8 @@ def _run_with_checkpoints(run, checkpoint_path, rate, maxit):
 def atlasqtl_global_local_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, verbose, list_hyper, list_init,
                                 checkpoint_path=None, trace_path=None, full_output=False, thinned_elbo_eval=True,
                                 debug=False, batch="y", device=0, process_group=None, resume_from=None,
-                                checkpoint_rate=100, trait_offset=None, scheme="global_local", sparse_output=None):
+                                checkpoint_rate=100, trait_offset=None, scheme="global_local", sparse_output=None,
+                                predict=None, fitted=False):
     """R/atlasqtl_global_local_core.R:8-433 on the GPU.  Returns the reference's list
     (:426-428): beta_vb, gam_vb, theta_vb, zeta_vb, n, p, q, anneal, converged, it, maxit,
     tol, lb_opt, diff_lb (+ the variational parameters with full_output).
@@ -495,8 +523,18 @@ def atlasqtl_global_local_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, verbo
     (VbRun.hotspot_sizes), theta_vb, zeta_vb and the scalars -- no gam_vb / beta_vb / mu_beta_vb, which stay on the device.
     With "summary": True (default False) the result also holds `value_summary` = {"gam_vb": ..., "beta_vb": ...}, the six
     numbers of VbRun.value_summary that summary() prints for the p q PPIs and effect sizes, and `sparse_output`, the
-    options used."""
+    options used.
+
+    predict = X_new, or {"X": X_new, "center": ..., "scale": ..., "checked": False}: rows of the p fitted columns (float64 or int8), already
+    standardised or to be standardised by center / scale; the result then holds `predicted` = Xt beta_vb (n_new x q,
+    VbRun.predict).  fitted=True: the result holds `X_beta_vb` = X beta_vb (n x q, VbRun.fitted) on the X of the run.  Both are
+    taken from the state on the device before it is released, so they work with sparse_output as well; with a process group
+    each rank gets the columns of its own traits."""
     sparse = None if sparse_output is None else sparse_output_options(sparse_output)
+    if predict is not None:
+        predict = dict(predict) if isinstance(predict, dict) else {"X": predict}
+        if not predict.get("checked"):                  # atlasqtl() has checked its X_new already, in the original numbering
+            predict["X"] = prediction.check_x_new(predict["X"], (X.shape if hasattr(X, "shape") else np.shape(X))[1], "predict")
     if df not in (1, 3, 5, 7):
         raise NotImplementedError("df must be 1, 3, 5 or 7 (compute_integral_hs_, R/utils.R:425-568, is unstable from df = 9 on)")
     if batch != "y":
@@ -532,6 +570,10 @@ def atlasqtl_global_local_core_(Y, X, shr_fac_inv, anneal, df, tol, maxit, verbo
             if sparse["summary"]:
                 res["value_summary"] = {"gam_vb": run.value_summary("gam_vb"), "beta_vb": run.value_summary("beta_vb")}
                 res["sparse_output"] = dict(sparse)
+        if predict is not None:
+            res["predicted"] = run.predict(predict["X"], predict.get("center"), predict.get("scale"), checked=True)
+        if fitted:
+            res["X_beta_vb"] = run.fitted(X)
         its, lbs = run.elbo_trace()
         res.update(n=run.n, p=run.p, q=run.q, anneal=anneal, converged=bool(st["converged"]), it=int(st["it"]),
                    maxit=maxit, tol=tol, lb_opt=st["lb_opt"], diff_lb=st["diff_lb"])

@@ -146,6 +146,12 @@ class PreparedData:
         _lib.check(_lib.lib().aq_prep_get(self.handle, _lib.as_dp(out), None), "aq_prep_get")
         return out
 
+    def x_moments(self, p_given):
+        """The column means and n - 1 standard deviations that scale(X) used, per column given (aq_prep_info)."""
+        mean = np.empty(int(p_given)); sd = np.empty(int(p_given))
+        _lib.check(_lib.lib().aq_prep_info(self.handle, None, None, None, None, _lib.as_dp(mean), _lib.as_dp(sd)), "aq_prep_info")
+        return mean, sd
+
     def ld_band(self, window):
         """r(j - 1 - b, j) of the matrix as it stands, p x window (NaN where j - 1 - b < 0): aq_prep_ld_band."""
         out = np.empty((self.p, int(window)), order="F")

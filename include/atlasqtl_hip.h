@@ -694,6 +694,65 @@ int aq_prep_marginal(aq_prep_handle h, const double *r2_cut, int64_t cap, int32_
                      int64_t *rs, int32_t *best_snp, double *best_r, int64_t *n_undefined, double *r_dense);
 int aq_prep_marginal_time(aq_prep_handle h, int32_t reps, double *ms_per_call, aq_mscreen_plan *plan_out);
 
+/* ------------------------------------------------------------------------------------------
+ * Prediction: the fitted model applied to genotypes,
+ *   Yhat = Xt B,   B = beta_vb = gam_vb * mu_beta_vb (p x q, R/update_vb.R:17),   Xt = (X_new - center) / scale per column,
+ * n_new x q: the genetic component of the traits on the scale of the prepared Y, in-sample (the X_beta_vb that the reference's
+ * man page lists and its code never returns: the update is commented out at src/coreLoop.cpp:100, R/update_vb.R:52) or for
+ * new samples.  B is read where it lies: the trait-tiled gam_vb and mu_beta_vb of the handle are multiplied in registers into
+ * the B operand of the f64 matrix instruction, a row at or beyond p or a trait at or beyond q is replaced by 0.0 there
+ * (whatever the padding of the storage holds), and nothing of size p q is allocated -- so a run whose p x q matrices never
+ * leave the device (sparse output) can be predicted from.  A pre-pass writes Xt from the uploaded fp64 or int8 columns as
+ * (x - center) (1 / scale), two roundings and the one of 1 / scale, into panels of 16 samples, [n_pad / 16][p_pad][16], with
+ * exact zeros in the rows >= n_new and the predictors >= p.  Workgroup (b, g, s) of the grid (sample_blocks, trait_groups,
+ * splits) owns sample_tiles tiles of 16 samples (a quarter per wave, every wave holding sample_tiles / 4 x trait_tiles
+ * accumulators so that a loaded block of B serves all its sample tiles), trait_tiles tiles of 16 traits and the predictors of
+ * split s, chunks_per_split chunks of `chunk` each, and writes its partial tiles to scratch, [splits][ceil(q / 16)][n_pad][16];
+ * a second kernel adds the partials of an entry in the order s = 0, 1, ... and writes the column-major result.  No
+ * floating-point atomics: two calls return the same bits, and so do two row batches of one matrix whose plans have the same
+ * splits.  Every offset is 64-bit.  Every entry is within (p + 8) 2^-53 sum_s |Xt_is B_st| of the exact value.
+ *   aq_vb_predict          X_new (n_new x p column-major fp64, host) or, when it is NULL, X_new_i8 (int8 dosages), with the
+ *                          handle's p columns; center, scale: p each, or both NULL: the input is standardised already.
+ *                          1 <= n_new <= 82 944 (AQ_N_MAX) per call.  Yhat_out: n_new x q column-major, host, q the handle's
+ *                          traits.  NaN in X_new is not looked for: it spreads to its row of Yhat.  Synchronises and reports
+ *                          an expired in-kernel wait as aq_vb_get_result does.
+ *   aq_vb_fitted           the same kernels on a standardised matrix that lies on the handle's device, n x p column-major
+ *                          with the handle's n rows: aq_prep_x_device of the prepare handle the fit was made from.
+ *   aq_predict             the matrix-level twin for a dense result, as aq_select_pairs is to aq_vb_select_pairs: beta_vb
+ *                          (p x q column-major, host) is uploaded into the tiled layout and the same kernels run.
+ *   aq_predict_plan_query  the launch plan without a device: a function of its arguments and of the environment variable
+ *                          AQ_PREDICT_SPLITS (1 ... 64; tests), which forces the splits of the entries above whatever p and
+ *                          the CU count say and which the query reads as they do (as aq_ytrans_plan_query reads AQ_YT_PATH);
+ *                          a value outside [1, 64] is AQ_ERR_ARG in all of them.  The entries plan for the device's CU count,
+ *                          or for AQ_NCU when it is set (the hook of aq_vb_create's planner; tests reach two trait tiles per
+ *                          workgroup at small shapes with it); the query takes the count as its argument.  More than
+ *                          1 048 560 traits per call (65 535 trait tiles, the y dimension of the grids) is AQ_ERR_UNSUPPORTED.
+ *   aq_vb_predict_time     measurement: the pre-pass (from int8 zeros, center 0, scale 1) and the two kernels `reps` times
+ *                          between two events after one warm-up, without the copies from and to the host; ms_per_call and,
+ *                          if not NULL, the plan used.
+ * A NULL handle, matrix or output, center without scale or the reverse, n_new outside [1, 82 944], p or q < 1 and a scale that
+ * is not finite and positive are AQ_ERR_ARG, with the entry's name in aq_last_error(), before any device call.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_predict_plan {
+  int32_t sample_tiles;       /* 16-sample tiles per workgroup: 4, 8 or 16 (1, 2 or 4 per wave)  */
+  int32_t trait_tiles;        /* 16-trait tiles per workgroup: 1 or 2                        */
+  int32_t sample_blocks;      /* ceil(ceil(n_new / 16) / sample_tiles)                       */
+  int32_t trait_groups;       /* ceil(ceil(q / 16) / trait_tiles)                            */
+  int32_t splits;             /* workgroups per (block, group), each with its own predictors */
+  int32_t chunk;              /* predictors per step: 16                                     */
+  int32_t chunks_per_split;   /* split s owns chunks [s chunks_per_split, (s + 1) chunks_per_split) */
+  int32_t n_pad;              /* 16 sample_tiles sample_blocks                               */
+  int64_t panel_bytes;        /* Xt in panel order: n_pad p_pad doubles, p_pad = p padded to 16 */
+  int64_t scratch_bytes;      /* the partial tiles: splits ceil(q / 16) n_pad 16 doubles     */
+} aq_predict_plan;
+int aq_predict_plan_query(int32_t n_new, int32_t p, int32_t q, int32_t ncu, aq_predict_plan *out);
+int aq_vb_predict(aq_vb_handle h, const double *X_new, const int8_t *X_new_i8, int32_t n_new, const double *center,
+                  const double *scale, double *Yhat_out);
+int aq_vb_fitted(aq_vb_handle h, const double *Xs_device, double *Yhat_out);
+int aq_predict(const double *beta_vb, int32_t p, int32_t q, const double *X_new, const int8_t *X_new_i8, int32_t n_new,
+               const double *center, const double *scale, double *Yhat_out, int32_t device);
+int aq_vb_predict_time(aq_vb_handle h, int32_t n_new, int32_t reps, double *ms_per_call, aq_predict_plan *plan_out);
+
 #ifdef __cplusplus
 }
 #endif
