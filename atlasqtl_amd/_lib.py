@@ -82,6 +82,12 @@ class AqMscreenPlan(C.Structure):
                 ("lds_bytes", C.c_int32), ("n_tiles", C.c_int64), ("scratch_bytes", C.c_int64)]
 
 
+class AqMspermPlan(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("pb", C.c_int32), ("batch", C.c_int32), ("launches", C.c_int32), ("tiles_p", C.c_int32),
+                ("tiles_q", C.c_int32), ("masked", C.c_int32), ("lds_bytes", C.c_int32), ("yp_bytes", C.c_int64),
+                ("scratch_bytes", C.c_int64)]
+
+
 class AqPredictPlan(C.Structure):
     _fields_ = [("sample_tiles", C.c_int32), ("trait_tiles", C.c_int32), ("sample_blocks", C.c_int32), ("trait_groups", C.c_int32),
                 ("splits", C.c_int32), ("chunk", C.c_int32), ("chunks_per_split", C.c_int32), ("n_pad", C.c_int32),
@@ -201,6 +207,10 @@ SYMBOLS = {
     "aq_prep_marginal": (C.c_int, [C.c_void_p, dp, C.c_int64, ip, ip, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), ip, dp,
                                    C.POINTER(C.c_int64), dp]),
     "aq_prep_marginal_time": (C.c_int, [C.c_void_p, C.c_int32, dp, C.POINTER(AqMscreenPlan)]),
+    "aq_msperm_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AqMspermPlan)]),
+    "aq_prep_marginal_perm": (C.c_int, [C.c_void_p, dp, C.c_int32, ip, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64)]),
+    "aq_prep_marginal_perm_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, dp, C.POINTER(AqMspermPlan)]),
     "aq_predict_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AqPredictPlan)]),
     "aq_vb_predict": (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int8), C.c_int32, dp, dp, dp]),
     "aq_vb_fitted": (C.c_int, [C.c_void_p, C.c_void_p, dp]),

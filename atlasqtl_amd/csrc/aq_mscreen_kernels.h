@@ -82,8 +82,9 @@ struct AqMsShape {
   static constexpr int NV = T * (AQ_MSCREEN_NC / 2) / 256;   // 16-byte vectors per thread and panel
 };
 
-__global__ __launch_bounds__(256) void aq_k_ms_traitstats(const double *__restrict__ Yc, int n, int q, double *__restrict__ syy,
-                                                         int *__restrict__ mt) {
+// the kernels that are no templates are static: two units include this header (aq_prep_marginal.hip, aq_prep_marginal_perm.hip)
+static __global__ __launch_bounds__(256) void aq_k_ms_traitstats(const double *__restrict__ Yc, int n, int q, double *__restrict__ syy,
+                                                                int *__restrict__ mt) {
   const int t = (int)blockIdx.x * 256 + threadIdx.x;
   if (t >= q) return;
   const double *col = Yc + (size_t)t * (size_t)n;
@@ -100,8 +101,8 @@ __global__ __launch_bounds__(256) void aq_k_ms_traitstats(const double *__restri
   mt[t] = m;
 }
 
-__global__ __launch_bounds__(256) void aq_k_ms_colstats(const double *__restrict__ Xs, int n, double *__restrict__ sx,
-                                                       double *__restrict__ sxx) {
+static __global__ __launch_bounds__(256) void aq_k_ms_colstats(const double *__restrict__ Xs, int n, double *__restrict__ sx,
+                                                              double *__restrict__ sxx) {
   __shared__ double sh[256];
   const double *col = Xs + (size_t)blockIdx.x * (size_t)n;
   double a = 0.0, b = 0.0;
@@ -346,8 +347,8 @@ __global__ __launch_bounds__(256, 2) void aq_k_ms_tile(const aq_ms_args a) {
 }
 
 // each trait's best predictor over the rows of tiles, in the order tp = 0, 1, ...: a later one only if strictly better
-__global__ __launch_bounds__(256) void aq_k_ms_best(const double *__restrict__ part_r, const int32_t *__restrict__ part_s, int tiles_p,
-                                                   int q, int32_t *__restrict__ best_snp, double *__restrict__ best_r) {
+static __global__ __launch_bounds__(256) void aq_k_ms_best(const double *__restrict__ part_r, const int32_t *__restrict__ part_s, int tiles_p,
+                                                          int q, int32_t *__restrict__ best_snp, double *__restrict__ best_r) {
   const int t = (int)blockIdx.x * 256 + threadIdx.x;
   if (t >= q) return;
   double br = __builtin_nan(""), b2 = -1.0;

@@ -10,6 +10,13 @@ Definition (include/atlasqtl_hip.h).  Over the m_t observed rows of trait t: r =
 Vx = Sxx - Sx^2 / m_t; df_t = m_t - 2 - n_cov; t = r sqrt(df_t / (1 - r^2)); the p-value is two-sided Student's t with df_t
 degrees of freedom.  A pair is undefined (r NaN, never selected) when the predictor is constant over the trait's observed rows
 (Vx <= 1e-10 Sxx), when Syy_t = 0 or when df_t < 1.
+
+Permutation nulls (permutations=; aq_prep_marginal_perm, csrc/aq_prep_marginal_perm.hip).  The p-values above are per pair:
+they do not correct a trait's best predictor for the p correlated predictors it was chosen from, and they do not say how large
+a marginal hotspot correlated traits produce by chance.  Permuting the sample rows of Y, all traits together, keeps the LD among
+predictors and the correlation among traits and breaks only the link between the two; every permutation is a whole screen on
+the GPU, of which each trait's largest r^2, the largest hotspot size and the number of selected pairs come back.  The host
+parses the argument (permutation_options) and turns the null statistics into p-values (permutation_summary).
 """
 from __future__ import annotations
 
@@ -115,12 +122,81 @@ def table_order(pvalue, t, snp, trait, p):
     return np.lexsort((pos, -np.abs(np.asarray(t, dtype=np.float64)), np.asarray(pvalue, dtype=np.float64)))
 
 
-def screen_handle(prep, names_x, names_y, p_value=None, fdr=None, max_pairs=None, dense=False):
+def _check_perm_rows(perms, n):
+    """perms as a B x n int32 array whose rows are permutations of 0 ... n - 1 (n None: of 0 ... width - 1), or the error."""
+    a = np.asarray(perms)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1 or not np.issubdtype(a.dtype, np.integer):
+        raise AtlasqtlError(f"marginal_screen: permutations given as an array must be B x n integers, not {a.dtype} {a.shape}.")
+    if n is not None and a.shape[1] != int(n):
+        raise AtlasqtlError(f"marginal_screen: the rows of permutations must have one entry per sample ({int(n)}), not {a.shape[1]}.")
+    width = a.shape[1]
+    bad = np.nonzero(np.any(np.sort(a, axis=1) != np.arange(width)[None, :], axis=1))[0]
+    if bad.size:
+        raise AtlasqtlError(f"marginal_screen: row {int(bad[0])} of permutations is not a permutation of 0 ... {width - 1}.")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def permutation_options(permutations, n=None):
+    """The `permutations` argument of marginal_screen() checked on the host.  None: no permutations.  A whole number B >= 1:
+    B random permutations from seed 0.  A dict {"n": B, "seed": s} (seed optional, a whole number >= 0, default 0).  An integer
+    array B x n of explicit permutations, every row a permutation of 0 ... n - 1: permutations restricted within sex or batch,
+    or the identity.  Returns None or dict(n B, seed (None for explicit rows), perms (B x n int32; None until n is known)).
+    Generated permutations are exactly
+        rng = np.random.default_rng(seed); np.stack([rng.permutation(n) for _ in range(B)]).astype(np.int32)"""
+    if permutations is None:
+        return None
+    if isinstance(permutations, (bool, np.bool_, float, np.floating, str)):
+        raise AtlasqtlError(f"marginal_screen: permutations must be None, a whole number >= 1, a dict with keys 'n' and 'seed' "
+                            f"or an integer array B x n, not {permutations!r}.")
+    if _is_whole(permutations) or isinstance(permutations, dict):
+        spec = {"n": permutations} if _is_whole(permutations) else dict(permutations)
+        if set(spec) - {"n", "seed"} or "n" not in spec:
+            raise AtlasqtlError("marginal_screen: permutations given as a dict must have the key 'n' and may have 'seed'.")
+        B, seed = spec["n"], spec.get("seed", 0)
+        if not _is_whole(B) or int(B) < 1:
+            raise AtlasqtlError(f"marginal_screen: the number of permutations must be a whole number >= 1, not {B!r}.")
+        if not _is_whole(seed) or int(seed) < 0:
+            raise AtlasqtlError(f"marginal_screen: the seed of permutations must be a whole number >= 0, not {seed!r}.")
+        B, seed = int(B), int(seed)
+        perms = None
+        if n is not None:
+            rng = np.random.default_rng(seed)
+            perms = np.stack([rng.permutation(int(n)) for _ in range(B)]).astype(np.int32)
+        return dict(n=B, seed=seed, perms=perms)
+    perms = _check_perm_rows(permutations, n)
+    return dict(n=int(perms.shape[0]), seed=None, perms=perms)
+
+
+def permutation_summary(max_r2, hs_max, n_sel, best_snp, best_r, rs_thres, nb_pairwise):
+    """What the permutation nulls say about a screen, in numpy.  max_r2 (B x q), hs_max (B), n_sel (B): the outputs of
+    PreparedData.marginal_permute; best_snp, best_r (q), rs_thres (p), nb_pairwise: of the screen.  Returns dict of
+      trait_pvalue[t] = (1 + #{b: max_r2[b][t] >= best_r[t]^2}) / (B + 1): the p-value of the trait's best predictor, corrected
+        for the predictors it was chosen from; NaN where the trait has no defined pair (best_snp[t] < 0);
+      hotspot_pvalue[s] = (1 + #{b: hs_max[b] >= rs_thres[s]}) / (B + 1): of a hotspot of that size anywhere among the
+        predictors (1 for a predictor without a selected trait);
+      expected_null_pairs = mean(n_sel); empirical_fdr = min(1, expected_null_pairs / max(1, nb_pairwise))."""
+    max_r2 = np.asarray(max_r2, dtype=np.float64)
+    hs_max = np.asarray(hs_max, dtype=np.int64)
+    B = max_r2.shape[0]
+    best_r = np.asarray(best_r, dtype=np.float64)
+    has = np.asarray(best_snp) >= 0
+    obs = np.where(has, best_r * best_r, np.inf)
+    trait_p = (1.0 + np.sum(max_r2 >= obs[None, :], axis=0)) / (B + 1.0)
+    trait_p[~has] = np.nan
+    rs = np.asarray(rs_thres, dtype=np.int64)
+    hot_p = (1.0 + (B - np.searchsorted(np.sort(hs_max), rs, side="left"))) / (B + 1.0)      # #{b: hs_max[b] >= rs[s]}
+    expected = float(np.mean(np.asarray(n_sel, dtype=np.float64)))
+    return dict(trait_pvalue=trait_p, hotspot_pvalue=hot_p, expected_null_pairs=expected,
+                empirical_fdr=min(1.0, expected / max(1, int(nb_pairwise))))
+
+
+def screen_handle(prep, names_x, names_y, p_value=None, fdr=None, max_pairs=None, dense=False, permutations=None):
     """The screen on a PreparedData as it stands: marginal_screen() without the preparation.  Returns the result dict without
     the rmvd_* fields."""
     from .api import AtlasqtlResult
     p, q = int(prep.p), int(prep.q)
     o = screen_options(p_value, fdr, max_pairs, dense, p, q)
+    po = permutation_options(permutations, int(prep.n))
     n_obs = np.sum(~np.isnan(prep.Y), axis=0).astype(np.int64)
     df = n_obs - 2 - int(prep.n_cov)
     cut = r2_cutoff(o["level"], df)
@@ -155,11 +231,24 @@ def screen_handle(prep, names_x, names_y, p_value=None, fdr=None, max_pairs=None
                          names_x=list(names_x), names_y=list(names_y))
     if o["dense"]:
         res["r"] = out["r_dense"]
+    if po is not None:
+        # the null counts use the cutoff that defined rs_thres: the device's own, or in the fdr mode the one of the largest
+        # p-value that the Benjamini-Hochberg cut kept (+inf everywhere: nothing was kept)
+        if o["mode"] != "fdr":
+            null_cut = cut
+        elif n_pairs > 0:
+            null_cut = r2_cutoff(float(pv[-1]), df)
+        else:
+            null_cut = np.full(q, np.inf)
+        nul = prep.marginal_permute(null_cut, po["perms"])
+        res["permutation"] = dict(n=po["n"], seed=po["seed"], max_r2=nul["max_r2"], hotspot_max=nul["hs_max"], n_selected=nul["n_sel"],
+                                  n_undefined=nul["n_undef"], r2_cut=null_cut,
+                                  **permutation_summary(nul["max_r2"], nul["hs_max"], nul["n_sel"], best_snp, best_r, rs, n_pairs))
     return res
 
 
 def marginal_screen(Y, X, p_value=None, fdr=None, max_pairs=None, covariates=None, ld_prune=None, transform_y=None, dense=False,
-                    device=0):
+                    device=0, permutations=None):
     """Every predictor of X tested against every trait of Y on its own, on the GPU.
 
     X and Y are prepared exactly as atlasqtl() prepares them (prepare_on_device: X float64, int8 dosages or a plink.PlinkBed;
@@ -184,13 +273,30 @@ def marginal_screen(Y, X, p_value=None, fdr=None, max_pairs=None, covariates=Non
         of the trait is defined);
       n_obs, df: per trait; n_undefined: pairs without a defined r; threshold: dict(mode, level, r2_cut [per trait], n_tests);
       names_x, names_y, n, p, q, and rmvd_cst_x, rmvd_coll_x, rmvd_cov_x, rmvd_ld_x as prepare_data_ gives them;
-      r: with dense=True, the p x q matrix of correlations (NaN where undefined); refused above 2^27 entries."""
+      r: with dense=True, the p x q matrix of correlations (NaN where undefined); refused above 2^27 entries.
+
+    permutations (None; a whole number B; {"n": B, "seed": s}; or a B x n integer array of explicit permutations, see
+    permutation_options) adds permutation nulls, computed on the GPU from the same handle (aq_prep_marginal_perm): the sample
+    rows of the prepared Y are permuted, all traits together and the missing values with them, which keeps the LD among the
+    predictors and the correlation among the traits and breaks only the link between the two; every permutation is a whole
+    screen, of which only each trait's largest r^2, the largest hotspot size and the number of selected pairs are kept.  The
+    result then carries
+      permutation: dict(n, seed [None for explicit rows], max_r2 [B x q, -1 where a trait has no defined pair], hotspot_max
+        [B], n_selected [B], n_undefined [B], trait_pvalue [q: (1 + #{b: max_r2[b][t] >= best_r[t]^2}) / (B + 1), the p-value
+        of the trait's best predictor corrected for the p predictors it was chosen from; NaN where best_snp < 0],
+        hotspot_pvalue [p: (1 + #{b: hotspot_max[b] >= rs_thres[s]}) / (B + 1)], expected_null_pairs [mean of n_selected],
+        empirical_fdr [min(1, expected_null_pairs / max(1, nb_pairwise))], r2_cut [q: the cutoff of the null counts -- the one
+        that defined rs_thres: threshold["r2_cut"], or with fdr= the cutoff of the largest p-value kept, +inf if none was]).
+    Without the argument the result has no such key.  With covariates= it is the residualised Y whose rows are permuted (the
+    scheme of Freedman and Lane): an approximation, since the residuals are not exchangeable exactly and the predictors were
+    residualised on the unpermuted rows; df keeps its covariate count."""
     screen_options(p_value, fdr, max_pairs, dense)             # before the first device call
+    permutation_options(permutations)
     dat = prepare_data_(Y, X, 0.1, 1, None, 0, None, None, device=device, covariates=covariates, ld_prune=ld_prune,
                         transform_y=transform_y)
     prep = dat["X"]
     try:
-        res = screen_handle(prep, dat["names_x"], dat["names_y"], p_value, fdr, max_pairs, dense)
+        res = screen_handle(prep, dat["names_x"], dat["names_y"], p_value, fdr, max_pairs, dense, permutations)
     finally:
         prep.close()
     for key in ("rmvd_cst_x", "rmvd_coll_x", "rmvd_cov_x", "rmvd_ld_x"):

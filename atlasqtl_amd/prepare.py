@@ -204,6 +204,31 @@ class PreparedData:
         return dict(snp=snp[:k], trait=trait[:k], r=r[:k], n_pairs=int(n_pairs.value), rs=rs, best_snp=best_snp, best_r=best_r,
                     n_undefined=int(n_undef.value), r_dense=r_dense)
 
+    def marginal_permute(self, r2_cut, perms):
+        """Permutation nulls of the marginal screen: aq_prep_marginal_perm.  r2_cut: q cutoffs on r^2, as for marginal();
+        perms: B x n integers, every row a permutation of 0 ... n - 1 (row b permutes the sample rows of Y: Y'[i] = Y[perms[b][i]]).
+        Returns dict(max_r2: B x q, the largest defined r^2 of every trait under every permutation (-1.0: none defined);
+        hs_max: B, the largest number of selected traits of one predictor; n_sel: B, selected pairs; n_undef: B)."""
+        import ctypes as C
+        cut = np.ascontiguousarray(r2_cut, dtype=np.float64)
+        if cut.shape != (self.q,):
+            raise AtlasqtlError(f"marginal_permute: r2_cut must hold one cutoff per trait ({self.q}), not {cut.shape}.")
+        perms = np.asarray(perms)
+        if perms.ndim != 2 or perms.shape[0] < 1 or perms.shape[1] != self.n or not np.issubdtype(perms.dtype, np.integer):
+            raise AtlasqtlError(f"marginal_permute: perms must be a B x n integer array with n = {self.n}, not "
+                                f"{perms.dtype} {perms.shape}.")
+        if perms.size and (perms.min() < 0 or perms.max() >= self.n):       # before the cast to int32 can wrap a value
+            raise AtlasqtlError(f"marginal_permute: every row of perms must be a permutation of 0 ... {self.n - 1}.")
+        perms = np.ascontiguousarray(perms, dtype=np.int32)
+        B = perms.shape[0]
+        max_r2 = np.empty((B, self.q))
+        hs, nsel, nundef = (np.zeros(B, dtype=np.int64) for _ in range(3))
+        i64 = C.POINTER(C.c_int64)
+        _lib.check(_lib.lib().aq_prep_marginal_perm(self.handle, _lib.as_dp(cut), B, _lib.as_ip(perms), _lib.as_dp(max_r2),
+                                                    hs.ctypes.data_as(i64), nsel.ctypes.data_as(i64), nundef.ctypes.data_as(i64)),
+                   "aq_prep_marginal_perm")
+        return dict(max_r2=max_r2, hs_max=hs, n_sel=nsel, n_undef=nundef)
+
     def close(self):
         if self.handle is not None:
             _lib.lib().aq_prep_destroy(self.handle)

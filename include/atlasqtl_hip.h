@@ -695,6 +695,57 @@ int aq_prep_marginal(aq_prep_handle h, const double *r2_cut, int64_t cap, int32_
 int aq_prep_marginal_time(aq_prep_handle h, int32_t reps, double *ms_per_call, aq_mscreen_plan *plan_out);
 
 /* ------------------------------------------------------------------------------------------
+ * Permutation nulls of the marginal screen.  Permutation b is an int32 vector perm[b] of length n, a permutation of
+ * 0 ... n - 1; the permuted response is Y'[i, t] = Yc[perm[b][i], t]: the rows of Yc move, all traits together and the NaN
+ * pattern with the values, and Xs is untouched, so the LD among predictors and the correlation among traits stay and only the
+ * link between the two is broken.  For every b the statistic of aq_prep_marginal is evaluated on (Xs, Y') by the same
+ * definition: the same undefined rule and the same m_t, Syy_t and df_t, which do not change with the permutation.  Kept per
+ * permutation, and nothing else (no object of size p1 q exists and no pair table is written):
+ *   max_r2[b][t]  the largest defined r^2 of trait t over all predictors; -1.0 where the trait has no defined pair
+ *   hs_max[b]     the largest number of traits with r^2 >= r2_cut[t] that one predictor has (the largest null hotspot)
+ *   n_sel[b]      the number of selected pairs;   n_undef[b]  the number of undefined pairs
+ * The permutations run in batches: a gather kernel writes the permuted panels Yp[batch][q][n] of a batch (at most 1 GiB), a
+ * tile kernel on the f64 matrix pipe stages each panel of Xs once for PB permutations, and a reduce kernel turns the
+ * per-predictor counts into hs_max and n_sel.  No floating-point atomics (max_r2 is an integer maximum over bit patterns of
+ * non-negative values): two calls with the same arguments return the same bits in every output.  Every output element is
+ * accumulated over the samples in the order of aq_prep_marginal, so the identity permutation returns max_r2 = best_r^2 of
+ * aq_prep_marginal to the bit, whatever the tile edge and PB.
+ *   aq_prep_marginal_perm       r2_cut: q doubles, as in aq_prep_marginal.  perm: [n_perm][n] int32, row-major.  max_r2:
+ *                               [n_perm][q] doubles, row-major; hs_max, n_sel, n_undef: int64[n_perm].  Any output may be
+ *                               NULL.  The handle is not changed.
+ *   aq_msperm_plan_query        the launch plan without a device, a pure function of its arguments: the tile edge of
+ *                               aq_mscreen_plan_query; PB (complete Y: 2 at tile 64, 1 at tile 128; masked: 1); batch, the
+ *                               largest multiple of PB with batch q n 8 <= 2^30 and batch scratch_per_perm <= 2^30, cut to
+ *                               n_perm rounded up to PB and to a grid below 2^31 workgroups; PB = 1 where PB panels exceed
+ *                               1 GiB; AQ_ERR_UNSUPPORTED where one panel does.  The environment variables AQ_MSCREEN_TILE,
+ *                               AQ_MSPERM_PB (complete Y: 1 | 2 | 4 at tile 64, 1 at tile 128; masked: 1 | 2) and
+ *                               AQ_MSPERM_BATCH (a multiple of PB within the bounds above) force the three in
+ *                               aq_prep_marginal_perm (tests, small shapes); the query does not read them.
+ *   aq_prep_marginal_perm_time  measurement: the gather, tile and reduce kernels of n_perm permutations (generated rows)
+ *                               `reps` times between two events after one warm-up, without the copies; the milliseconds of
+ *                               ONE permutation and, if not NULL, the plan used.
+ * n_perm < 1, a NULL r2_cut or perm, a NULL handle, a NaN cutoff and a row of perm that is not a permutation of 0 ... n - 1
+ * (the message names the row) are AQ_ERR_ARG, in this order, before any device call: an index out of range never reaches a
+ * kernel.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_msperm_plan {
+  int32_t tile;               /* edge of a tile: predictors and traits per workgroup, 64 or 128 */
+  int32_t pb;                 /* permutations per workgroup: they share the staged panel of Xs  */
+  int32_t batch;              /* permutations per launch, a multiple of pb                      */
+  int32_t launches;           /* ceil(n_perm / batch); the last one may be ragged               */
+  int32_t tiles_p;            /* ceil(p1 / tile)                                                */
+  int32_t tiles_q;            /* ceil(q / tile): the grid is tiles_p tiles_q ceil(nb / pb)      */
+  int32_t masked;             /* 1: the three-stream instance for Yc with missing values        */
+  int32_t lds_bytes;          /* static LDS of a workgroup, <= 64 KiB                           */
+  int64_t yp_bytes;           /* the gathered panels: 8 batch q n <= 2^30                       */
+  int64_t scratch_bytes;      /* batch (4 p1 + 16 q + 4 n + 24): counts, maxima, perm rows      */
+} aq_msperm_plan;
+int aq_msperm_plan_query(int32_t n, int32_t p1, int32_t q, int32_t masked, int32_t ncu, int32_t n_perm, aq_msperm_plan *out);
+int aq_prep_marginal_perm(aq_prep_handle h, const double *r2_cut, int32_t n_perm, const int32_t *perm, double *max_r2, int64_t *hs_max,
+                          int64_t *n_sel, int64_t *n_undef);
+int aq_prep_marginal_perm_time(aq_prep_handle h, int32_t n_perm, int32_t reps, double *ms_per_perm, aq_msperm_plan *plan_out);
+
+/* ------------------------------------------------------------------------------------------
  * Prediction: the fitted model applied to genotypes,
  *   Yhat = Xt B,   B = beta_vb = gam_vb * mu_beta_vb (p x q, R/update_vb.R:17),   Xt = (X_new - center) / scale per column,
  * n_new x q: the genetic component of the traits on the scale of the prepared Y, in-sample (the X_beta_vb that the reference's
