@@ -88,6 +88,13 @@ class AqMspermPlan(C.Structure):
                 ("scratch_bytes", C.c_int64)]
 
 
+class AqCisPlan(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("sample_chunk", C.c_int32), ("trait_tiles", C.c_int32), ("q_active", C.c_int32),
+                ("masked", C.c_int32), ("lds_bytes", C.c_int32), ("perm_lds_bytes", C.c_int32), ("pb", C.c_int32), ("batch", C.c_int32),
+                ("launches", C.c_int32), ("n_items", C.c_int64), ("window_pairs", C.c_int64), ("staged_pairs", C.c_int64),
+                ("yp_bytes", C.c_int64), ("scratch_bytes", C.c_int64)]
+
+
 class AqPredictPlan(C.Structure):
     _fields_ = [("sample_tiles", C.c_int32), ("trait_tiles", C.c_int32), ("sample_blocks", C.c_int32), ("trait_groups", C.c_int32),
                 ("splits", C.c_int32), ("chunk", C.c_int32), ("chunks_per_split", C.c_int32), ("n_pad", C.c_int32),
@@ -211,6 +218,11 @@ SYMBOLS = {
     "aq_prep_marginal_perm": (C.c_int, [C.c_void_p, dp, C.c_int32, ip, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                         C.POINTER(C.c_int64)]),
     "aq_prep_marginal_perm_time": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, dp, C.POINTER(AqMspermPlan)]),
+    "aq_cis_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, ip, C.c_int32, C.POINTER(AqCisPlan)]),
+    "aq_prep_cis": (C.c_int, [C.c_void_p, ip, ip, dp, C.c_int64, ip, ip, dp, C.POINTER(C.c_int64), ip, dp, C.POINTER(C.c_int64),
+                              C.POINTER(AqCisPlan)]),
+    "aq_prep_cis_perm": (C.c_int, [C.c_void_p, ip, ip, C.c_int32, ip, dp]),
+    "aq_prep_cis_time": (C.c_int, [C.c_void_p, ip, ip, C.c_int32, C.c_int32, dp, dp, C.POINTER(AqCisPlan)]),
     "aq_predict_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AqPredictPlan)]),
     "aq_vb_predict": (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int8), C.c_int32, dp, dp, dp]),
     "aq_vb_fitted": (C.c_int, [C.c_void_p, C.c_void_p, dp]),

@@ -1,0 +1,257 @@
+"""The cis scan: every trait (gene) tested only against the predictors within a window around its own position, the mapping
+that FastQTL and tensorQTL compute first, on the GPU from a prepare handle (aq_prep_cis, aq_prep_cis_perm,
+csrc/aq_prep_cis.hip).
+
+The GPU does the work of the band -- the correlations of the in-window pairs on the f64 matrix pipe, the selection and each
+trait's best cis predictor in registers, and with permutations= each trait's largest in-window r^2 under every permutation of
+the sample rows of Y.  The host does O(p + q), O(selected pairs) and O(B q) work, all of it here: the windows from positions
+(cis_windows), the user's threshold as a per-trait cutoff on r^2, t, p-value and Benjamini-Hochberg q-value of the rows that
+came back, and the permutation p-value of every trait's best predictor with its beta approximation (beta_approximation).
+
+The statistic is the marginal screen's (marginal.py): r over the m_t observed rows of the trait, df_t = m_t - 2 - n_cov, a pair
+undefined when the predictor is constant over those rows, Syy_t = 0 or df_t < 1.  A pair outside its trait's window does not
+exist: it is neither selected, nor counted as undefined, nor a candidate for the best predictor.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .marginal import INITIAL_CAP, bh_qvalues, permutation_options, r2_cutoff, screen_options, t_and_pvalue, table_order
+from .prepare import AtlasqtlError, _is_whole, prepare_data_
+
+
+def cis_windows(snp_chrom, snp_pos, trait_chrom, trait_start, trait_end=None, window=1_000_000):
+    """(s_lo, s_hi), int32 each, one entry per trait: the window of trait t is the half-open range s_lo[t] <= s < s_hi[t] of
+    predictor indices on the trait's chromosome with trait_start[t] - window <= pos <= trait_end[t] + window (trait_end
+    defaults to trait_start).  snp_chrom, snp_pos: one value per predictor, in the predictors' order (the kept columns of a
+    prepared matrix).  The predictors of a chromosome must be contiguous and their positions non-decreasing, so that the
+    window is one index range; otherwise AtlasqtlError names the first offending column.  A trait on a chromosome without
+    predictors gets an empty window (0, 0).  Chromosomes are compared as strings."""
+    chrom = np.asarray([str(c) for c in snp_chrom], dtype=object)
+    try:
+        pos = np.asarray(snp_pos, dtype=np.int64)
+        start = np.atleast_1d(np.asarray(trait_start, dtype=np.int64))
+        end = start if trait_end is None else np.atleast_1d(np.asarray(trait_end, dtype=np.int64))
+    except (TypeError, ValueError) as e:
+        raise AtlasqtlError(f"cis_windows: positions must be whole numbers ({e}).") from e
+    tchrom = [str(c) for c in np.atleast_1d(np.asarray(trait_chrom, dtype=object))]
+    if pos.ndim != 1 or pos.shape != chrom.shape:
+        raise AtlasqtlError(f"cis_windows: snp_chrom and snp_pos must hold one value per predictor ({chrom.shape} and {pos.shape}).")
+    if start.ndim != 1 or start.shape != end.shape or len(tchrom) != start.size:
+        raise AtlasqtlError("cis_windows: trait_chrom, trait_start and trait_end must hold one value per trait.")
+    if not _is_whole(window) or int(window) < 0:
+        raise AtlasqtlError(f"cis_windows: window must be a whole number >= 0, not {window!r}.")
+    if np.any(end < start):
+        raise AtlasqtlError(f"cis_windows: trait_end < trait_start for trait {int(np.nonzero(end < start)[0][0])}.")
+    window = int(window)
+    blocks = {}                                        # chromosome -> (first column, one past its last column)
+    p = chrom.size
+    j = 0
+    while j < p:
+        c = chrom[j]
+        if c in blocks:
+            raise AtlasqtlError(f"cis_windows: the predictors of chromosome {c} are not contiguous: column {j} follows other "
+                                "chromosomes. Order the predictors by chromosome and position.")
+        k = j + 1
+        while k < p and chrom[k] == c:
+            if pos[k] < pos[k - 1]:
+                raise AtlasqtlError(f"cis_windows: the positions on chromosome {c} decrease at column {k} ({int(pos[k])} after "
+                                    f"{int(pos[k - 1])}). Order the predictors by chromosome and position.")
+            k += 1
+        blocks[c] = (j, k)
+        j = k
+    q = start.size
+    s_lo, s_hi = np.zeros(q, dtype=np.int32), np.zeros(q, dtype=np.int32)
+    for t in range(q):
+        blk = blocks.get(tchrom[t])
+        if blk is None:
+            continue
+        a, b = blk
+        s_lo[t] = a + np.searchsorted(pos[a:b], start[t] - window, side="left")
+        s_hi[t] = a + np.searchsorted(pos[a:b], end[t] + window, side="right")
+    return s_lo, s_hi
+
+
+def beta_approximation(max_r2, df, best_pvalue):
+    """The beta approximation of the permutation p-value of each trait's best predictor, in the moment-matched form of
+    FastQTL's (without its likelihood refinement of the shapes and without its estimate of the degrees of freedom).
+    max_r2: B x q, the largest in-window r^2 per permutation (-1: none); df: q; best_pvalue: q, the two-sided Student p-value
+    of the observed best predictor.  Per trait: p_b = the two-sided Student p-value of max_r2[b][t] with df_t; m and v their
+    mean and (B - 1)-denominator variance; shape1 = m (m (1 - m) / v - 1), shape2 = shape1 (1 / m - 1);
+    pvalue = Beta(shape1, shape2).cdf(best_pvalue).  All three NaN where B < 2, v = 0, a shape <= 0, or the trait or a
+    permutation of it has no defined pair.  Returns (shape1, shape2, pvalue)."""
+    from scipy.stats import beta
+    max_r2 = np.asarray(max_r2, dtype=np.float64)
+    B, q = max_r2.shape
+    df = np.asarray(df, dtype=np.float64)
+    best_pvalue = np.asarray(best_pvalue, dtype=np.float64)
+    s1, s2, pv = np.full(q, np.nan), np.full(q, np.nan), np.full(q, np.nan)
+    if B < 2:
+        return s1, s2, pv
+    usable = np.all(max_r2 >= 0, axis=0) & (df >= 1) & ~np.isnan(best_pvalue)
+    if not usable.any():
+        return s1, s2, pv
+    pb = t_and_pvalue(np.sqrt(max_r2[:, usable]), np.broadcast_to(df[usable], (B, int(usable.sum()))))[1]
+    m, v = pb.mean(axis=0), pb.var(axis=0, ddof=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a = m * (m * (1.0 - m) / v - 1.0)
+        b = a * (1.0 / m - 1.0)
+    ok = (v > 0) & (a > 0) & (b > 0) & np.isfinite(a) & np.isfinite(b)
+    idx = np.nonzero(usable)[0][ok]
+    s1[idx], s2[idx] = a[ok], b[ok]
+    pv[idx] = beta.cdf(best_pvalue[idx], a[ok], b[ok])
+    return s1, s2, pv
+
+
+def cis_permutation_summary(max_r2, best_snp, best_r, best_pvalue, df):
+    """What the permutation nulls say about a cis scan, in numpy: dict of
+      trait_pvalue[t] = (1 + #{b: max_r2[b][t] >= best_r[t]^2}) / (B + 1), NaN where best_snp[t] < 0;
+      beta_shape1, beta_shape2, trait_pvalue_beta: beta_approximation;
+      trait_qvalue: Benjamini-Hochberg of trait_pvalue_beta over the traits with a defined pair (NaN elsewhere, and where the
+        beta approximation is NaN: those traits are not among the tests)."""
+    max_r2 = np.asarray(max_r2, dtype=np.float64)
+    B = max_r2.shape[0]
+    best_r = np.asarray(best_r, dtype=np.float64)
+    has = np.asarray(best_snp) >= 0
+    obs = np.where(has, best_r * best_r, np.inf)
+    trait_p = (1.0 + np.sum(max_r2 >= obs[None, :], axis=0)) / (B + 1.0)
+    trait_p[~has] = np.nan
+    s1, s2, pbeta = beta_approximation(max_r2, df, np.where(has, best_pvalue, np.nan))
+    qv = np.full(trait_p.shape, np.nan)
+    tested = np.nonzero(has & ~np.isnan(pbeta))[0]
+    if tested.size:
+        order = tested[np.argsort(pbeta[tested], kind="stable")]
+        qv[order] = bh_qvalues(pbeta[order], tested.size)
+    return dict(trait_pvalue=trait_p, beta_shape1=s1, beta_shape2=s2, trait_pvalue_beta=pbeta, trait_qvalue=qv)
+
+
+def cis_options(p_value=None, fdr=None, max_pairs=None):
+    """The threshold arguments of cis_screen() checked on the host: those of marginal.screen_options, under this function's
+    name.  Returns dict(mode, level (None for Bonferroni until the windows are known), max_pairs)."""
+    try:
+        o = screen_options(p_value, fdr, max_pairs)
+    except AtlasqtlError as e:
+        raise AtlasqtlError(str(e).replace("marginal_screen:", "cis_screen:")) from None
+    return dict(mode=o["mode"], level=o["level"], max_pairs=o["max_pairs"])
+
+
+def cis_handle(prep, names_x, names_y, s_lo, s_hi, p_value=None, fdr=None, max_pairs=None, permutations=None):
+    """The cis scan on a PreparedData as it stands, with the windows given as index ranges over its columns: cis_screen()
+    without the preparation and without cis_windows.  Returns the result without the rmvd_* fields."""
+    from .api import AtlasqtlResult
+    p, q = int(prep.p), int(prep.q)
+    o = cis_options(p_value, fdr, max_pairs)
+    po = permutation_options(permutations, int(prep.n))
+    s_lo, s_hi = prep._cis_windows_arg(s_lo, s_hi, "cis_screen")
+    n_cis = (s_hi.astype(np.int64) - s_lo.astype(np.int64))
+    M = int(n_cis.sum())
+    level = o["level"] if o["mode"] != "bonferroni" else 0.05 / max(M, 1)
+    n_obs = np.sum(~np.isnan(prep.Y), axis=0).astype(np.int64)
+    df = n_obs - 2 - int(prep.n_cov)
+    cut = r2_cutoff(level, df)
+    cap = int(min(M, INITIAL_CAP))
+    out = prep.cis(s_lo, s_hi, cut, cap)
+    if out["n_pairs"] > cap:                                  # the complete set, whatever order the first call filled its rows in
+        out = prep.cis(s_lo, s_hi, cut, out["n_pairs"])
+    snp, trait, r = out["snp"], out["trait"], out["r"]
+    dfr = df[trait].astype(np.float64)
+    t, pv = t_and_pvalue(r, dfr)
+    order = table_order(pv, t, snp, trait, p)
+    snp, trait, r, t, pv, dfr = snp[order], trait[order], r[order], t[order], pv[order], dfr[order]
+    n_tests_t = n_cis - out["n_undef"]
+    n_tests = int(n_tests_t.sum())
+    qv = bh_qvalues(pv, n_tests)
+    if o["mode"] == "fdr":                                    # the device selected p <= alpha, a superset of the BH set
+        keep = int(np.sum(qv <= level))                       # q is non-decreasing along the table
+        snp, trait, r, t, pv, dfr, qv = (a[:keep] for a in (snp, trait, r, t, pv, dfr, qv))
+    n_pairs = int(snp.size)
+    m = n_pairs if o["max_pairs"] is None else min(n_pairs, o["max_pairs"])
+    assoc = dict(snp=snp[:m], trait=trait[:m], r=r[:m], t=t[:m], df=dfr[:m].astype(np.int64), pvalue=pv[:m], qvalue=qv[:m],
+                 snp_name=np.asarray(names_x, dtype=object)[snp[:m]], trait_name=np.asarray(names_y, dtype=object)[trait[:m]],
+                 n_pairs=n_pairs)
+    best_snp, best_r = out["best_snp"], out["best_r"]
+    best_p = np.full(q, np.nan)
+    has = best_snp >= 0
+    best_p[has] = t_and_pvalue(best_r[has], df[has])[1]
+    res = AtlasqtlResult(assoc=assoc, window=(s_lo, s_hi), n_cis=n_cis, n_tests=n_tests_t, best_snp=best_snp, best_r=best_r,
+                         best_pvalue=best_p, n_obs=n_obs, df=df, n_undefined=out["n_undef"], n=int(prep.n), p=p, q=q,
+                         threshold=dict(mode=o["mode"], level=level, r2_cut=cut, n_tests=n_tests), plan=out["plan"],
+                         names_x=list(names_x), names_y=list(names_y))
+    if po is not None:
+        max_r2 = prep.cis_permute(s_lo, s_hi, po["perms"])
+        res["permutation"] = dict(n=po["n"], seed=po["seed"], max_r2=max_r2,
+                                  **cis_permutation_summary(max_r2, best_snp, best_r, best_p, df))
+    return res
+
+
+def _per_predictor(values, p_given, name):
+    a = np.asarray(values)
+    if a.ndim != 1 or a.shape[0] != int(p_given):
+        raise AtlasqtlError(f"cis_screen: {name} must hold one value per predictor given ({int(p_given)}), not {a.shape}.")
+    return a
+
+
+def cis_screen(Y, X, trait_chrom, trait_start, trait_end=None, window=1_000_000, snp_chrom=None, snp_pos=None, p_value=None,
+               fdr=None, max_pairs=None, permutations=None, covariates=None, ld_prune=None, transform_y=None, device=0):
+    """Every trait of Y tested against the predictors of X within `window` base pairs of it, on the GPU: cis-QTL mapping.
+
+    X and Y are prepared exactly as marginal_screen() prepares them.  trait_chrom, trait_start, trait_end (default:
+    trait_start): one value per trait; the window of trait t is the kept predictors on its chromosome with trait_start -
+    window <= pos <= trait_end + window (cis_windows, which needs the predictors ordered by chromosome and position).
+    snp_chrom, snp_pos: one value per predictor GIVEN, cut to the kept columns as names_x is; they default to the chrom and
+    pos of a plink.PlinkBed.  For every pair inside a window: the Pearson correlation r over the trait's observed rows,
+    t = r sqrt(df / (1 - r^2)) with df = m_t - 2 - d and the two-sided p-value of Student's t, as in marginal_screen().  A pair
+    outside its trait's window does not exist.
+
+    Selection as in marginal_screen(), with M = the number of in-window pairs in the place of p q: p_value=c keeps p <= c;
+    fdr=a keeps the Benjamini-Hochberg set at level a over the M - (undefined in-window pairs) tests; neither means
+    Bonferroni, p_value = 0.05 / M.  The table is ordered by (p-value, -|t|, position snp + p trait); max_pairs cuts it.
+
+    Returns an AtlasqtlResult with
+      assoc: the columns of marginal_screen()'s;
+      per trait: window (s_lo, s_hi: index ranges into names_x), n_cis (predictors in the window), n_tests (defined pairs
+        among them), n_undefined, best_snp, best_r, best_pvalue (the in-window predictor of largest r^2, the lowest index on
+        a tie; -1 / NaN / NaN where the window is empty or holds no defined pair), n_obs, df;
+      threshold: dict(mode, level, r2_cut, n_tests); plan: the dict of aq_cis_plan, whose window_pairs / staged_pairs is the
+        fill of the band; names_x, names_y, n, p, q, n_covariates and rmvd_cst_x, rmvd_coll_x, rmvd_cov_x, rmvd_ld_x.
+
+    permutations (as in marginal_screen(): None, B, {"n": B, "seed": s} or a B x n array) adds the permutation null of every
+    trait's best cis predictor, computed on the GPU over the same windows (aq_prep_cis_perm): the result then carries
+      permutation: dict(n, seed, max_r2 [B x q: the largest in-window r^2 per permutation, -1 where none is defined],
+        trait_pvalue [(1 + #{b: max_r2[b][t] >= best_r[t]^2}) / (B + 1); NaN where best_snp < 0],
+        beta_shape1, beta_shape2, trait_pvalue_beta [the beta approximation of that p-value in the moment-matched form of
+        FastQTL's, without its likelihood refinement and its estimate of the degrees of freedom: with p_b the two-sided
+        Student p-value of max_r2[b][t] at df_t, m and v the mean and the (B - 1)-denominator variance of the p_b,
+        shape1 = m (m (1 - m) / v - 1), shape2 = shape1 (1 / m - 1), trait_pvalue_beta = Beta(shape1, shape2).cdf(best_pvalue);
+        NaN where B < 2, v = 0 or a shape <= 0],
+        trait_qvalue [Benjamini-Hochberg of trait_pvalue_beta over the traits with a defined pair: the eGenes are
+        trait_qvalue <= level]).
+    With covariates= the residualised Y is permuted, as marginal_screen() describes."""
+    from .plink import PlinkBed
+    cis_options(p_value, fdr, max_pairs)                       # before the first device call
+    permutation_options(permutations)
+    if not _is_whole(window) or int(window) < 0:
+        raise AtlasqtlError(f"cis_screen: window must be a whole number >= 0, not {window!r}.")
+    if isinstance(X, PlinkBed):
+        snp_chrom = X.chrom if snp_chrom is None else snp_chrom
+        snp_pos = X.pos if snp_pos is None else snp_pos
+    if snp_chrom is None or snp_pos is None:
+        raise AtlasqtlError("cis_screen: snp_chrom and snp_pos are required unless X is a PlinkBed.")
+    p_given = X.shape[1] if hasattr(X, "shape") else np.asarray(X).shape[1]
+    snp_chrom = _per_predictor(snp_chrom, p_given, "snp_chrom")
+    snp_pos = _per_predictor(snp_pos, p_given, "snp_pos")
+    dat = prepare_data_(Y, X, 0.1, 1, None, 0, None, None, device=device, covariates=covariates, ld_prune=ld_prune,
+                        transform_y=transform_y)
+    prep = dat["X"]
+    try:
+        kept = ~np.asarray(dat["bool_rmvd_x"], dtype=bool)
+        if len(np.atleast_1d(trait_start)) != int(prep.q):
+            raise AtlasqtlError(f"cis_screen: trait_chrom, trait_start and trait_end must hold one value per trait ({int(prep.q)}).")
+        s_lo, s_hi = cis_windows(snp_chrom[kept], snp_pos[kept], trait_chrom, trait_start, trait_end, window)
+        res = cis_handle(prep, dat["names_x"], dat["names_y"], s_lo, s_hi, p_value, fdr, max_pairs, permutations)
+    finally:
+        prep.close()
+    for key in ("rmvd_cst_x", "rmvd_coll_x", "rmvd_cov_x", "rmvd_ld_x"):
+        res[key] = dat[key]
+    res["n_covariates"] = dat["n_covariates"]
+    return res

@@ -1,0 +1,351 @@
+// aq_prep_cis.hip -- the cis scan of a finished prepare handle (include/atlasqtl_hip.h): aq_prep_cis tests every trait against
+// the predictors of its own window on the f64 matrix pipe (aq_cis_kernels.h; order, work items and plan by aq_cis_plan.h) and
+// returns the selected pairs, each trait's best in-window predictor and its undefined pairs; aq_prep_cis_perm evaluates the
+// same statistic on permuted responses and returns each trait's largest in-window r^2 per permutation; aq_prep_cis_time times
+// the kernels alone, aq_cis_plan_query runs the planner on the host.  The kernels are plain HIP that issues no hand-written
+// load: the ISA proof of the look-ahead sweep units does not cover them and need not.
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdlib>
+#include <limits>
+#include <stdint.h>
+#include <string>
+#include <vector>
+#include "aq_prep.h"          // aq_prep, aq_time_launches; aq_internal.h: aq_fail, AQ_HIP, aq_need_device, aq_need_acc_layout, AqDev
+#include "aq_cis_kernels.h"   // aq_k_cis_*; aq_k_ms_traitstats, aq_k_ms_colstats; aq_cis_make_plan
+#include "aq_msperm_plan.h"   // aq_msperm_check_rows (the plan header alone: aq_msperm_kernels.h defines a non-static kernel)
+
+extern "C" int aq_cis_plan_query(int32_t n, int32_t p1, int32_t q, int32_t masked, int32_t ncu, const int32_t *s_lo, const int32_t *s_hi,
+                                 int32_t n_perm, aq_cis_plan *out) {
+  if (!out) return aq_fail(AQ_ERR_ARG, "aq_cis_plan_query: NULL argument");
+  *out = aq_cis_plan{};
+  std::string err;
+  const int rc = aq_cis_make_plan(n, p1, q, masked, ncu, s_lo, s_hi, n_perm, 0, 0, "aq_cis_plan_query", out, nullptr, &err);
+  if (rc != AQ_OK) *out = aq_cis_plan{};
+  return rc == AQ_OK ? AQ_OK : aq_fail(rc, err);
+}
+
+// the device side of one call: what does not change with the permutation, the scan's outputs, and the buffers of one launch of
+// permutations
+struct AqCisBuf {
+  AqDev<double> Yo, sx, sxx, syy, cut, part_r, best_r, r, Yp, max_r2;
+  AqDev<int> mt;
+  AqDev<int32_t> order, lo, hi, first_item, item_tile, item_p0, part_s, best_s, snp, trait, perm;
+  AqDev<unsigned long long> counter, undef, key;
+  std::vector<int> mt_host;                  // m_t per ordered trait with a window
+  aq_cis_plan pl{};
+  aq_cis_work wk;
+  int64_t cap = 0;
+};
+
+// an environment variable that forces a plan field: 0 when it is not set, -1 when it is no number >= 1 (the planner's message)
+static int aq_cis_env(const char *name) {
+  const char *e = getenv(name);
+  if (!e) return 0;
+  const int v = atoi(e);
+  return v < 1 ? -1 : v;
+}
+
+template <typename T>
+static int aq_cis_upload(AqDev<T> *dst, const std::vector<T> &src) {
+  AQ_TRY(dst->alloc(src.size() > 0 ? src.size() : 1));
+  if (!src.empty()) AQ_HIP(hipMemcpy(dst->get(), src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return AQ_OK;
+}
+
+// Syy_t and m_t of the handle's traits, whether any value is missing (over ALL traits, as aq_prep_marginal decides it, so
+// that the same instance computes the same bits), the plan, the order and the work list; the per-trait arrays in the order;
+// the buffers of the scan (scan) and of one launch of permutations (n_perm > 0).  r2_cut may be NULL (the *_time entry sets
+// its own, the permutations use none).
+static int aq_cis_setup(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, const double *r2_cut, int64_t cap, bool scan, int n_perm,
+                        const char *who, AqCisBuf *b) {
+  const size_t p1 = (size_t)h->p_kept, q = (size_t)h->q, n = (size_t)h->n;
+  std::vector<double> syy(q);
+  std::vector<int> mt(q);
+  {
+    AqDev<double> dsyy;
+    AqDev<int> dmt;
+    AQ_TRY(dsyy.alloc(q));
+    AQ_TRY(dmt.alloc(q));
+    hipLaunchKernelGGL(aq_k_ms_traitstats, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, h->Yc.get(), h->n, h->q, dsyy.get(),
+                       dmt.get());
+    AQ_HIP(hipGetLastError());
+    AQ_HIP(hipMemcpy(syy.data(), dsyy.get(), q * sizeof(double), hipMemcpyDeviceToHost));
+    AQ_HIP(hipMemcpy(mt.data(), dmt.get(), q * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  int masked = 0;
+  for (size_t t = 0; t < q; t++) masked |= mt[t] < h->n;
+  int ncu = 0;
+  AQ_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
+  std::string err;
+  const int rc = aq_cis_make_plan(h->n, h->p_kept, h->q, masked, ncu > 0 ? ncu : 256, s_lo, s_hi, n_perm,
+                                  n_perm > 0 ? aq_cis_env("AQ_CIS_PB") : 0, n_perm > 0 ? aq_cis_env("AQ_CIS_BATCH") : 0, who, &b->pl, &b->wk,
+                                  &err);
+  if (rc != AQ_OK) return aq_fail(rc, err);
+  const size_t qa = (size_t)b->wk.q_active, W = (size_t)b->pl.n_items;
+  b->cap = cap;
+  {
+    std::vector<double> syy_o(qa), cut_o(qa);
+    std::vector<int32_t> lo_o(qa), hi_o(qa);
+    b->mt_host.resize(qa);
+    for (size_t j = 0; j < qa; j++) {
+      const size_t t = (size_t)b->wk.order[j];
+      syy_o[j] = syy[t];
+      b->mt_host[j] = mt[t];
+      cut_o[j] = r2_cut ? r2_cut[t] : std::numeric_limits<double>::infinity();
+      lo_o[j] = s_lo[t];
+      hi_o[j] = s_hi[t];
+    }
+    AQ_TRY(aq_cis_upload(&b->syy, syy_o));
+    AQ_TRY(aq_cis_upload(&b->mt, b->mt_host));
+    AQ_TRY(aq_cis_upload(&b->cut, cut_o));
+    AQ_TRY(aq_cis_upload(&b->lo, lo_o));
+    AQ_TRY(aq_cis_upload(&b->hi, hi_o));
+  }
+  AQ_TRY(aq_cis_upload(&b->order, b->wk.order));
+  AQ_TRY(aq_cis_upload(&b->first_item, b->wk.first_item));
+  AQ_TRY(aq_cis_upload(&b->item_tile, b->wk.item_tile));
+  AQ_TRY(aq_cis_upload(&b->item_p0, b->wk.item_p0));
+  if (!masked) {
+    AQ_TRY(b->sx.alloc(p1));
+    AQ_TRY(b->sxx.alloc(p1));
+  }
+  if (scan) {
+    AQ_TRY(b->Yo.alloc(qa > 0 ? qa * n : 1));
+    AQ_TRY(b->counter.alloc(1));
+    AQ_TRY(b->undef.alloc(q));
+    AQ_TRY(b->part_r.alloc(W > 0 ? W * AQ_CIS_TILE : 1));
+    AQ_TRY(b->part_s.alloc(W > 0 ? W * AQ_CIS_TILE : 1));
+    AQ_TRY(b->best_r.alloc(q));
+    AQ_TRY(b->best_s.alloc(q));
+    if (cap > 0) {
+      AQ_TRY(b->snp.alloc((size_t)cap));
+      AQ_TRY(b->trait.alloc((size_t)cap));
+      AQ_TRY(b->r.alloc((size_t)cap));
+    }
+  }
+  if (n_perm > 0) {
+    const size_t batch = (size_t)b->pl.batch;
+    AQ_TRY(b->Yp.alloc(batch * (qa > 0 ? qa : 1) * n));
+    AQ_TRY(b->perm.alloc(batch * n));
+    AQ_TRY(b->key.alloc(batch * q));
+    AQ_TRY(b->max_r2.alloc(batch * q));
+  }
+  return AQ_OK;
+}
+
+static aq_cis_args aq_cis_common_args(aq_prep *h, AqCisBuf &b) {
+  aq_cis_args a{};
+  a.Xs = h->Xs.get();
+  a.n = h->n; a.p1 = h->p_kept; a.q = h->q; a.qa = b.wk.q_active; a.n_cov = h->n_cov; a.W = (int)b.pl.n_items;
+  a.item_tile = b.item_tile.get(); a.item_p0 = b.item_p0.get();
+  a.sx = b.sx.get(); a.sxx = b.sxx.get(); a.syy = b.syy.get(); a.cut = b.cut.get(); a.mt = b.mt.get();
+  a.lo = b.lo.get(); a.hi = b.hi.get(); a.orig = b.order.get();
+  return a;
+}
+
+// Sx and Sxx of every column for the complete instances.  Asynchronous.
+static int aq_cis_colstats(aq_prep *h, AqCisBuf &b) {
+  if (!b.pl.masked) {
+    hipLaunchKernelGGL(aq_k_ms_colstats, dim3((unsigned)h->p_kept), dim3(256), 0, 0, h->Xs.get(), h->n, b.sx.get(), b.sxx.get());
+    AQ_HIP(hipGetLastError());
+  }
+  return AQ_OK;
+}
+
+// every kernel of one scan after aq_cis_setup.  Asynchronous.
+static int aq_cis_launch_scan(aq_prep *h, AqCisBuf &b) {
+  const int q = h->q, qa = b.wk.q_active;
+  const unsigned W = (unsigned)b.pl.n_items;
+  AQ_HIP(hipMemsetAsync(b.counter.get(), 0, sizeof(unsigned long long), 0));
+  AQ_HIP(hipMemsetAsync(b.undef.get(), 0, (size_t)q * sizeof(unsigned long long), 0));
+  AQ_TRY(aq_cis_colstats(h, b));
+  if (W > 0) {
+    hipLaunchKernelGGL(aq_k_cis_gather, dim3((unsigned)(qa < (1 << 20) ? qa : (1 << 20))), dim3(256), 0, 0, h->Yc.get(), b.order.get(),
+                       (const int32_t *)nullptr, h->n, qa, 1, b.Yo.get());
+    aq_cis_args a = aq_cis_common_args(h, b);
+    a.Yo = b.Yo.get();
+    a.nb = 1;
+    a.snp = b.snp.get(); a.trait = b.trait.get(); a.r = b.r.get(); a.cap = (long long)b.cap;
+    a.n_pairs = b.counter.get(); a.n_undef = b.undef.get();
+    a.part_r = b.part_r.get(); a.part_s = b.part_s.get();
+    const bool a16 = (h->n & 1) == 0;            // even n: every column starts at a multiple of 16 bytes
+    if (b.pl.masked) {
+      if (a16)
+        hipLaunchKernelGGL((aq_k_cis_tile<true, true>), dim3(W), dim3(256), 0, 0, a);
+      else
+        hipLaunchKernelGGL((aq_k_cis_tile<true, false>), dim3(W), dim3(256), 0, 0, a);
+    } else {
+      if (a16)
+        hipLaunchKernelGGL((aq_k_cis_tile<false, true>), dim3(W), dim3(256), 0, 0, a);
+      else
+        hipLaunchKernelGGL((aq_k_cis_tile<false, false>), dim3(W), dim3(256), 0, 0, a);
+    }
+  }
+  hipLaunchKernelGGL(aq_k_cis_best, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, b.part_r.get(), b.part_s.get(), b.first_item.get(),
+                     b.order.get(), qa, q, b.best_s.get(), b.best_r.get());
+  AQ_HIP(hipGetLastError());
+  return AQ_OK;
+}
+
+template <bool MASKED, int PB>
+static void aq_cis_launch_perm_tile(bool a16, unsigned grid, const aq_cis_args &a) {
+  if (a16)
+    hipLaunchKernelGGL((aq_k_cis_perm_tile<MASKED, true, PB>), dim3(grid), dim3(256), 0, 0, a);
+  else
+    hipLaunchKernelGGL((aq_k_cis_perm_tile<MASKED, false, PB>), dim3(grid), dim3(256), 0, 0, a);
+}
+
+// the kernels of one launch over the nb <= batch permutations whose rows lie in b.perm; Sx and Sxx have been formed.
+// Asynchronous.
+static int aq_cis_launch_perm(aq_prep *h, AqCisBuf &b, int nb) {
+  const int q = h->q, qa = b.wk.q_active, pb = b.pl.pb;
+  const long long W = b.pl.n_items;
+  AQ_HIP(hipMemsetAsync(b.key.get(), 0, (size_t)nb * (size_t)q * sizeof(unsigned long long), 0));
+  if (W > 0) {
+    const long long cols = (long long)nb * (long long)qa;
+    hipLaunchKernelGGL(aq_k_cis_gather, dim3((unsigned)(cols < (1ll << 20) ? cols : (1ll << 20))), dim3(256), 0, 0, h->Yc.get(),
+                       b.order.get(), (const int32_t *)b.perm.get(), h->n, qa, nb, b.Yp.get());
+    aq_cis_args a = aq_cis_common_args(h, b);
+    a.Yo = b.Yp.get();
+    a.nb = nb;
+    a.key = b.key.get();
+    const bool a16 = (h->n & 1) == 0;
+    const unsigned grid = (unsigned)(W * ((nb + pb - 1) / pb));   // < 2^31: the plan
+    if (b.pl.masked) {
+      if (pb == 2)
+        aq_cis_launch_perm_tile<true, 2>(a16, grid, a);
+      else
+        aq_cis_launch_perm_tile<true, 1>(a16, grid, a);
+    } else if (pb == 4) {
+      aq_cis_launch_perm_tile<false, 4>(a16, grid, a);
+    } else if (pb == 2) {
+      aq_cis_launch_perm_tile<false, 2>(a16, grid, a);
+    } else {
+      aq_cis_launch_perm_tile<false, 1>(a16, grid, a);
+    }
+  }
+  const long long count = (long long)nb * (long long)q;
+  hipLaunchKernelGGL(aq_k_cis_reduce, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, b.key.get(), count, b.max_r2.get());
+  AQ_HIP(hipGetLastError());
+  return AQ_OK;
+}
+
+// the window checks that need the handle's p1 and q, under the entry's name
+static int aq_cis_need_windows(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, const char *who) {
+  std::string err;
+  const int rc = aq_cis_check_windows(s_lo, s_hi, h->q, h->p_kept, who, &err);
+  return rc == AQ_OK ? AQ_OK : aq_fail(rc, err);
+}
+
+extern "C" int aq_prep_cis(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, const double *r2_cut, int64_t cap, int32_t *snp,
+                           int32_t *trait, double *r, int64_t *n_pairs, int32_t *best_snp, double *best_r, int64_t *n_undef,
+                           aq_cis_plan *plan_out) {
+  if (!s_lo || !s_hi || !r2_cut) return aq_fail(AQ_ERR_ARG, "aq_prep_cis: NULL s_lo, s_hi or r2_cut");
+  if (cap < 0) return aq_fail(AQ_ERR_ARG, "aq_prep_cis: cap >= 0 required, " + std::to_string(cap) + " given");
+  if (!h) return aq_fail(AQ_ERR_ARG, "aq_prep_cis: NULL handle");
+  AQ_TRY(aq_cis_need_windows(h, s_lo, s_hi, "aq_prep_cis"));
+  for (int t = 0; t < h->q; t++)
+    if (std::isnan(r2_cut[t])) return aq_fail(AQ_ERR_ARG, "aq_prep_cis: r2_cut[" + std::to_string(t) + "] is NaN");
+  AQ_TRY(aq_need_device(h->device));
+  AQ_TRY(aq_need_acc_layout("aq_prep_cis"));
+  const size_t q = (size_t)h->q;
+  AqCisBuf b;
+  AQ_TRY(aq_cis_setup(h, s_lo, s_hi, r2_cut, cap, true, 0, "aq_prep_cis", &b));
+  if (plan_out) *plan_out = b.pl;
+  AQ_TRY(aq_cis_launch_scan(h, b));
+  unsigned long long cnt = 0;
+  AQ_HIP(hipMemcpy(&cnt, b.counter.get(), sizeof(cnt), hipMemcpyDeviceToHost));
+  if (n_pairs) *n_pairs = (int64_t)cnt;
+  const size_t rows = cnt < (unsigned long long)cap ? (size_t)cnt : (size_t)cap;
+  if (rows > 0) {
+    if (snp) AQ_HIP(hipMemcpy(snp, b.snp.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (trait) AQ_HIP(hipMemcpy(trait, b.trait.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (r) AQ_HIP(hipMemcpy(r, b.r.get(), rows * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
+  if (best_snp) AQ_HIP(hipMemcpy(best_snp, b.best_s.get(), q * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (best_r) AQ_HIP(hipMemcpy(best_r, b.best_r.get(), q * sizeof(double), hipMemcpyDeviceToHost));
+  if (n_undef) AQ_HIP(hipMemcpy(n_undef, b.undef.get(), q * sizeof(int64_t), hipMemcpyDeviceToHost));
+  return AQ_OK;
+}
+
+extern "C" int aq_prep_cis_perm(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, int32_t n_perm, const int32_t *perm,
+                                double *max_r2) {
+  if (n_perm < 1) return aq_fail(AQ_ERR_ARG, "aq_prep_cis_perm: n_perm >= 1 required, " + std::to_string(n_perm) + " given");
+  if (!s_lo || !s_hi || !perm) return aq_fail(AQ_ERR_ARG, "aq_prep_cis_perm: NULL s_lo, s_hi or perm");
+  if (!h) return aq_fail(AQ_ERR_ARG, "aq_prep_cis_perm: NULL handle");
+  AQ_TRY(aq_cis_need_windows(h, s_lo, s_hi, "aq_prep_cis_perm"));
+  {
+    std::string err;                             // an index out of range never reaches the gather kernel
+    const int rc = aq_msperm_check_rows(perm, n_perm, h->n, "aq_prep_cis_perm", &err);
+    if (rc != AQ_OK) return aq_fail(rc, err);
+  }
+  AQ_TRY(aq_need_device(h->device));
+  AQ_TRY(aq_need_acc_layout("aq_prep_cis_perm"));
+  const size_t q = (size_t)h->q, n = (size_t)h->n;
+  AqCisBuf b;
+  AQ_TRY(aq_cis_setup(h, s_lo, s_hi, nullptr, 0, false, n_perm, "aq_prep_cis_perm", &b));
+  AQ_TRY(aq_cis_colstats(h, b));
+  for (int done = 0; done < n_perm; done += b.pl.batch) {
+    const int nb = n_perm - done < b.pl.batch ? n_perm - done : b.pl.batch;
+    AQ_HIP(hipMemcpy(b.perm.get(), perm + (size_t)done * n, (size_t)nb * n * sizeof(int32_t), hipMemcpyHostToDevice));
+    AQ_TRY(aq_cis_launch_perm(h, b, nb));
+    if (max_r2) AQ_HIP(hipMemcpy(max_r2 + (size_t)done * q, b.max_r2.get(), (size_t)nb * q * sizeof(double), hipMemcpyDeviceToHost));
+    AQ_HIP(hipDeviceSynchronize());              // the next launch overwrites the buffers
+  }
+  return AQ_OK;
+}
+
+// Timing hook: the scan's kernels `reps` times between two events, counting only (cap = 0), with the cutoff t^2 = 40 of
+// aq_prep_marginal_time, r2_cut = 40 / (40 + df_t), +inf where df_t < 1; then, with n_perm >= 1, the gather, tile and reduce
+// kernels of n_perm permutations launch by launch, on one batch of rows generated as in aq_prep_marginal_perm_time.
+extern "C" int aq_prep_cis_time(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, int32_t n_perm, int32_t reps, double *ms_scan,
+                                double *ms_per_perm, aq_cis_plan *plan_out) {
+  if (!s_lo || !s_hi || !ms_scan || !ms_per_perm) return aq_fail(AQ_ERR_ARG, "aq_prep_cis_time: NULL argument");
+  if (n_perm < 0 || reps < 1) return aq_fail(AQ_ERR_ARG, "aq_prep_cis_time: n_perm >= 0 and reps >= 1 required");
+  if (!h) return aq_fail(AQ_ERR_ARG, "aq_prep_cis_time: NULL handle");
+  AQ_TRY(aq_cis_need_windows(h, s_lo, s_hi, "aq_prep_cis_time"));
+  AQ_TRY(aq_need_device(h->device));
+  AQ_TRY(aq_need_acc_layout("aq_prep_cis_time"));
+  const size_t n = (size_t)h->n;
+  AqCisBuf b;
+  AQ_TRY(aq_cis_setup(h, s_lo, s_hi, nullptr, 0, true, n_perm, "aq_prep_cis_time", &b));
+  if (plan_out) *plan_out = b.pl;
+  {
+    const size_t qa = (size_t)b.wk.q_active;
+    std::vector<double> cut(qa);
+    for (size_t j = 0; j < qa; j++) {
+      const int df = b.mt_host[j] - 2 - h->n_cov;
+      cut[j] = df >= 1 ? 40.0 / (40.0 + (double)df) : std::numeric_limits<double>::infinity();
+    }
+    if (qa > 0) AQ_HIP(hipMemcpy(b.cut.get(), cut.data(), qa * sizeof(double), hipMemcpyHostToDevice));
+  }
+  AQ_TRY(aq_time_launches(reps, ms_scan, [&] { return aq_cis_launch_scan(h, b); }));
+  *ms_per_perm = 0.0;
+  if (n_perm > 0) {
+    const size_t rows = (size_t)b.pl.batch;
+    std::vector<int32_t> perm(rows * n);
+    uint64_t state = 0x9e3779b97f4a7c15ull;
+    for (size_t r = 0; r < rows; r++) {
+      int32_t *row = perm.data() + r * n;
+      for (size_t i = 0; i < n; i++) row[i] = (int32_t)i;
+      for (size_t i = n; i > 1; i--) {
+        state = state * 6364136223846793005ull + 1442695040888963407ull;
+        const size_t j = (size_t)((state >> 33) % i);
+        const int32_t tmp = row[i - 1];
+        row[i - 1] = row[j];
+        row[j] = tmp;
+      }
+    }
+    AQ_HIP(hipMemcpy(b.perm.get(), perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    double ms = 0.0;
+    AQ_TRY(aq_time_launches(reps, &ms, [&] {
+      for (int done = 0; done < n_perm; done += b.pl.batch)
+        AQ_TRY(aq_cis_launch_perm(h, b, n_perm - done < b.pl.batch ? n_perm - done : b.pl.batch));
+      return (int)AQ_OK;
+    }));
+    *ms_per_perm = ms / (double)n_perm;
+  }
+  return AQ_OK;
+}

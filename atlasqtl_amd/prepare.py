@@ -229,6 +229,55 @@ class PreparedData:
                    "aq_prep_marginal_perm")
         return dict(max_r2=max_r2, hs_max=hs, n_sel=nsel, n_undef=nundef)
 
+    def _cis_windows_arg(self, s_lo, s_hi, who):
+        """The windows as the library takes them: two contiguous int32 vectors of q entries with 0 <= s_lo <= s_hi <= p,
+        checked before the cast to int32 can wrap a value (the library checks them again, and names the trait)."""
+        lo, hi = np.asarray(s_lo), np.asarray(s_hi)
+        for a in (lo, hi):
+            if a.shape != (self.q,) or not np.issubdtype(a.dtype, np.integer):
+                raise AtlasqtlError(f"{who}: s_lo and s_hi must hold one whole number per trait ({self.q}), not {a.dtype} {a.shape}.")
+        if lo.size and (lo.min() < 0 or hi.max() > self.p or np.any(lo > hi)):
+            raise AtlasqtlError(f"{who}: every window must satisfy 0 <= s_lo <= s_hi <= p = {self.p}.")
+        return np.ascontiguousarray(lo, dtype=np.int32), np.ascontiguousarray(hi, dtype=np.int32)
+
+    def cis(self, s_lo, s_hi, r2_cut, cap):
+        """The cis scan of the matrix as it stands: aq_prep_cis.  Trait t is tested against the predictors s_lo[t] <= s <
+        s_hi[t] only.  r2_cut, cap: as for marginal().  Returns dict(snp, trait, r: the min(n_pairs, cap) rows written, in no
+        particular order; n_pairs: the full count; best_snp, best_r: per trait, the in-window predictor of largest r^2 (-1 /
+        NaN: none defined); n_undef: per trait, the undefined pairs inside its window; plan: the dict of aq_cis_plan)."""
+        import ctypes as C
+        lo, hi = self._cis_windows_arg(s_lo, s_hi, "cis")
+        cut = np.ascontiguousarray(r2_cut, dtype=np.float64)
+        if cut.shape != (self.q,):
+            raise AtlasqtlError(f"cis: r2_cut must hold one cutoff per trait ({self.q}), not {cut.shape}.")
+        cap = int(cap)
+        rows = max(cap, 0)
+        snp = np.empty(rows, dtype=np.int32); trait = np.empty(rows, dtype=np.int32); r = np.empty(rows)
+        best_snp = np.empty(self.q, dtype=np.int32); best_r = np.empty(self.q); n_undef = np.zeros(self.q, dtype=np.int64)
+        n_pairs, plan = C.c_int64(0), _lib.AqCisPlan()
+        _lib.check(_lib.lib().aq_prep_cis(self.handle, _lib.as_ip(lo), _lib.as_ip(hi), _lib.as_dp(cut), cap, _lib.as_ip(snp),
+                                          _lib.as_ip(trait), _lib.as_dp(r), C.byref(n_pairs), _lib.as_ip(best_snp), _lib.as_dp(best_r),
+                                          n_undef.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(plan)), "aq_prep_cis")
+        k = min(int(n_pairs.value), rows)
+        return dict(snp=snp[:k], trait=trait[:k], r=r[:k], n_pairs=int(n_pairs.value), best_snp=best_snp, best_r=best_r,
+                    n_undef=n_undef, plan={name: int(getattr(plan, name)) for name, _ in _lib.AqCisPlan._fields_})
+
+    def cis_permute(self, s_lo, s_hi, perms):
+        """Permutation nulls of the cis scan: aq_prep_cis_perm.  perms: B x n integers as for marginal_permute().  Returns
+        max_r2, B x q: the largest defined r^2 of every trait over its window under every permutation (-1.0: none)."""
+        lo, hi = self._cis_windows_arg(s_lo, s_hi, "cis_permute")
+        perms = np.asarray(perms)
+        if perms.ndim != 2 or perms.shape[0] < 1 or perms.shape[1] != self.n or not np.issubdtype(perms.dtype, np.integer):
+            raise AtlasqtlError(f"cis_permute: perms must be a B x n integer array with n = {self.n}, not {perms.dtype} {perms.shape}.")
+        if perms.size and (perms.min() < 0 or perms.max() >= self.n):       # before the cast to int32 can wrap a value
+            raise AtlasqtlError(f"cis_permute: every row of perms must be a permutation of 0 ... {self.n - 1}.")
+        perms = np.ascontiguousarray(perms, dtype=np.int32)
+        B = perms.shape[0]
+        max_r2 = np.empty((B, self.q))
+        _lib.check(_lib.lib().aq_prep_cis_perm(self.handle, _lib.as_ip(lo), _lib.as_ip(hi), B, _lib.as_ip(perms), _lib.as_dp(max_r2)),
+                   "aq_prep_cis_perm")
+        return max_r2
+
     def close(self):
         if self.handle is not None:
             _lib.lib().aq_prep_destroy(self.handle)

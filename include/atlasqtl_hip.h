@@ -746,6 +746,69 @@ int aq_prep_marginal_perm(aq_prep_handle h, const double *r2_cut, int32_t n_perm
 int aq_prep_marginal_perm_time(aq_prep_handle h, int32_t n_perm, int32_t reps, double *ms_per_perm, aq_msperm_plan *plan_out);
 
 /* ------------------------------------------------------------------------------------------
+ * Cis scan of a finished handle: every trait (gene) tested only against the predictors of its own window, and the
+ * permutation null of its best cis predictor.  The window of trait t is a half-open range of indices into the handle's
+ * CURRENT matrix Xs (p1 columns): s_lo[t] <= s < s_hi[t], 0 <= s_lo[t] <= s_hi[t] <= p1; an empty window is allowed.  The
+ * statistic, the rule for an undefined pair, m_t, Syy_t and df_t are those of the marginal screen above.  A pair outside its
+ * trait's window does not exist: it is neither selected, nor counted as undefined, nor a candidate for the best predictor.
+ * Only the band is computed.  The traits are ordered by (s_lo, s_hi, t), those with an empty window last; 64 consecutive
+ * traits of the order form a trait tile with the union range [L, H) of their windows; the work items of a tile are the
+ * predictor ranges [p0, p0 + 64), p0 = L, L + 64, ... < H, and a plain grid of one workgroup per item takes the place of the
+ * grid of all predictor tiles x trait tiles.  The traits' columns are copied into the order once per call, so a tile's traits
+ * are contiguous.  Every pair is accumulated over the samples in the order of the marginal screen (steps of 4, one matrix
+ * instruction per step) and goes through the same epilogue: r of a pair inside its window is r_dense of aq_prep_marginal on
+ * the same handle to the bit, and max_r2 of the identity permutation is best_r^2.  No floating-point atomics: two calls give
+ * the same set of rows and the same bits in every other output; the order of the rows is unspecified.
+ *   aq_prep_cis        r2_cut: q doubles, trait t selects its in-window pairs with r^2 >= r2_cut[t] (+inf: none).  cap: rows
+ *                      of the table snp / trait / r (cap = 0 only counts); n_pairs: always the full count, of which
+ *                      min(n_pairs, cap) rows are written.  best_snp: int32[q], the in-window predictor of largest r^2, the
+ *                      lowest index on a tie, -1 where the window holds no defined pair; best_r: double[q], its r (NaN
+ *                      there).  n_undef: int64[q], undefined pairs inside each trait's window.  plan_out: the plan used.
+ *                      Any output may be NULL.  The handle is not changed.
+ *   aq_prep_cis_perm   perm: [n_perm][n] int32 as in aq_prep_marginal_perm.  max_r2: [n_perm][q] doubles, row-major, the
+ *                      largest defined r^2 of trait t over its window under permutation b; -1.0 where there is none.
+ *   aq_cis_plan_query  the plan without a device, a pure function of its arguments; n_perm = 0 plans the scan alone (pb,
+ *                      batch, launches, perm_lds_bytes, yp_bytes = 0).  PB: complete Y 2, masked 1 (measured: DESIGN.md
+ *                      section 9; the defaults of aq_msperm_plan_query at tile 64); the batch by the rules there, with the panel 8 n
+ *                      max(q_active, 1) bytes.  The environment variables AQ_CIS_PB (complete Y: 1 | 2 | 4; masked: 1 | 2)
+ *                      and AQ_CIS_BATCH (a multiple of PB within the bounds) force the two in aq_prep_cis_perm and
+ *                      aq_prep_cis_time (tests, small shapes); the query does not read them.  More than 2^31 - 1 work items
+ *                      or a panel above 1 GiB are AQ_ERR_UNSUPPORTED.
+ *   aq_prep_cis_time   measurement: ms_scan, the kernels of one scan (the ordered copy of Y, the column sums, the tile
+ *                      kernel, the reduction of the bests), counting only, cutoffs as in aq_prep_marginal_time; ms_per_perm,
+ *                      with n_perm >= 1, the gather, tile and reduce kernels of n_perm generated permutations, per
+ *                      permutation (n_perm = 0: not measured, 0.0).  Each `reps` times between two events after a warm-up.
+ * AQ_ERR_ARG, in this order, before any device call: n_perm < 1 (aq_prep_cis_perm); a NULL s_lo, s_hi, r2_cut or perm;
+ * cap < 0; a NULL handle; a bound outside [0, p1] or s_lo > s_hi (the message names the trait); a NaN cutoff; a row of perm
+ * that is not a permutation of 0 ... n - 1.  No index out of range reaches a kernel.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_cis_plan {
+  int32_t tile;               /* edge of a work item: predictors and traits per workgroup, 64     */
+  int32_t sample_chunk;       /* samples staged per step                                         */
+  int32_t trait_tiles;        /* ceil(q_active / tile)                                           */
+  int32_t q_active;           /* traits with a non-empty window                                  */
+  int32_t masked;             /* 1: the three-stream instances for Yc with missing values        */
+  int32_t lds_bytes;          /* static LDS of a workgroup of the scan, <= 64 KiB                */
+  int32_t perm_lds_bytes;     /* ... of the permutation kernel                                   */
+  int32_t pb;                 /* permutations per workgroup: they share the staged panel of Xs   */
+  int32_t batch;              /* permutations per launch, a multiple of pb                       */
+  int32_t launches;           /* ceil(n_perm / batch); the last one may be ragged                */
+  int64_t n_items;            /* W, the work items: the grid of the scan                         */
+  int64_t window_pairs;       /* sum of s_hi - s_lo: the pairs that exist                        */
+  int64_t staged_pairs;       /* tile tile W >= window_pairs; the ratio is the fill of the band  */
+  int64_t yp_bytes;           /* the gathered panels of a launch: 8 batch max(q_active, 1) n     */
+  int64_t scratch_bytes;      /* 12 tile W (each item's best per trait) + batch (16 q + 4 n)     */
+} aq_cis_plan;
+int aq_cis_plan_query(int32_t n, int32_t p1, int32_t q, int32_t masked, int32_t ncu, const int32_t *s_lo, const int32_t *s_hi,
+                      int32_t n_perm, aq_cis_plan *out);
+int aq_prep_cis(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, const double *r2_cut, int64_t cap, int32_t *snp,
+                int32_t *trait, double *r, int64_t *n_pairs, int32_t *best_snp, double *best_r, int64_t *n_undef,
+                aq_cis_plan *plan_out);
+int aq_prep_cis_perm(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, int32_t n_perm, const int32_t *perm, double *max_r2);
+int aq_prep_cis_time(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, int32_t n_perm, int32_t reps, double *ms_scan,
+                     double *ms_per_perm, aq_cis_plan *plan_out);
+
+/* ------------------------------------------------------------------------------------------
  * Prediction: the fitted model applied to genotypes,
  *   Yhat = Xt B,   B = beta_vb = gam_vb * mu_beta_vb (p x q, R/update_vb.R:17),   Xt = (X_new - center) / scale per column,
  * n_new x q: the genetic component of the traits on the scale of the prepared Y, in-sample (the X_beta_vb that the reference's
