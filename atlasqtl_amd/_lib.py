@@ -95,6 +95,11 @@ class AqCisPlan(C.Structure):
                 ("yp_bytes", C.c_int64), ("scratch_bytes", C.c_int64)]
 
 
+class AqCiscondPlan(C.Structure):
+    _fields_ = [("cis", AqCisPlan), ("kc", C.c_int32), ("max_k", C.c_int32), ("lds_bytes", C.c_int32), ("streams", C.c_int32),
+                ("qo_bytes", C.c_int64), ("yo_bytes", C.c_int64)]
+
+
 class AqPredictPlan(C.Structure):
     _fields_ = [("sample_tiles", C.c_int32), ("trait_tiles", C.c_int32), ("sample_blocks", C.c_int32), ("trait_groups", C.c_int32),
                 ("splits", C.c_int32), ("chunk", C.c_int32), ("chunks_per_split", C.c_int32), ("n_pad", C.c_int32),
@@ -223,6 +228,10 @@ SYMBOLS = {
                               C.POINTER(AqCisPlan)]),
     "aq_prep_cis_perm": (C.c_int, [C.c_void_p, ip, ip, C.c_int32, ip, dp]),
     "aq_prep_cis_time": (C.c_int, [C.c_void_p, ip, ip, C.c_int32, C.c_int32, dp, dp, C.POINTER(AqCisPlan)]),
+    "aq_ciscond_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, ip, ip, C.POINTER(AqCiscondPlan)]),
+    "aq_prep_cis_cond": (C.c_int, [C.c_void_p, ip, ip, ip, ip, dp, C.c_int64, ip, ip, dp, C.POINTER(C.c_int64), ip, dp,
+                                   C.POINTER(C.c_int64), ip, C.POINTER(AqCiscondPlan)]),
+    "aq_prep_cis_cond_time": (C.c_int, [C.c_void_p, ip, ip, ip, ip, C.c_int32, dp, dp, C.POINTER(AqCiscondPlan)]),
     "aq_predict_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AqPredictPlan)]),
     "aq_vb_predict": (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int8), C.c_int32, dp, dp, dp]),
     "aq_vb_fitted": (C.c_int, [C.c_void_p, C.c_void_p, dp]),

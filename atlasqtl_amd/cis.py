@@ -11,6 +11,11 @@ came back, and the permutation p-value of every trait's best predictor with its 
 The statistic is the marginal screen's (marginal.py): r over the m_t observed rows of the trait, df_t = m_t - 2 - n_cov, a pair
 undefined when the predictor is constant over those rows, Syy_t = 0 or df_t < 1.  A pair outside its trait's window does not
 exist: it is neither selected, nor counted as undefined, nor a candidate for the best predictor.
+
+condition_on= turns the scan into the conditional one (aq_prep_cis_cond, csrc/aq_prep_cis_cond.hip): r becomes the partial
+correlation given the trait's own conditioning variants, df_t = n - 2 - n_cov - k_eff[t].  cis_independent() runs the
+forward-backward conditional pass of QTLtools and tensorQTL's map_independent on top of it: the loop itself is
+independent_signals_, which takes the scan as a callable.
 """
 from __future__ import annotations
 
@@ -135,12 +140,74 @@ def cis_options(p_value=None, fdr=None, max_pairs=None):
     return dict(mode=o["mode"], level=o["level"], max_pairs=o["max_pairs"])
 
 
-def cis_handle(prep, names_x, names_y, s_lo, s_hi, p_value=None, fdr=None, max_pairs=None, permutations=None):
+def condition_lists(condition_on, names_x, names_y):
+    """The condition_on argument of cis_screen() checked on the host: q lists of indices into names_x.  condition_on: a dict
+    trait -> variants (a trait is an index into names_y or a name in it; traits not named get an empty list), or a list of q
+    lists.  A variant is an index into names_x or a name in it; a single variant may stand without a list.  At most 4
+    distinct variants per trait."""
+    names_x, names_y = list(names_x), list(names_y)
+    q = len(names_y)
+    by_name = {}                                       # "trait" / "variant" -> name -> first index, built when a name is met
+
+    def lookup(v, names, what):
+        if isinstance(v, (str, np.str_)):
+            if what not in by_name:
+                by_name[what] = {str(nm): i for i, nm in reversed(list(enumerate(names)))}
+            if str(v) not in by_name[what]:
+                raise AtlasqtlError(f"cis_screen: condition_on names the {what} {v!r}, which is not among the {what}s kept.")
+            return by_name[what][str(v)]
+        if not _is_whole(v) or isinstance(v, (bool, np.bool_)):
+            raise AtlasqtlError(f"cis_screen: condition_on must name a {what} by its name or its index, not {v!r}.")
+        if not 0 <= int(v) < len(names):
+            raise AtlasqtlError(f"cis_screen: condition_on has the {what} index {int(v)} outside [0, {len(names)}).")
+        return int(v)
+
+    if isinstance(condition_on, dict):
+        items = [[] for _ in range(q)]
+        for key, vs in condition_on.items():
+            t = lookup(key, names_y, "trait")
+            if items[t]:
+                raise AtlasqtlError(f"cis_screen: condition_on names trait {t} twice.")
+            items[t] = vs
+    else:
+        try:
+            items = list(condition_on)
+        except TypeError:
+            items = None
+        if items is None or len(items) != q or isinstance(condition_on, str):
+            raise AtlasqtlError(f"cis_screen: condition_on must be a dict trait -> variants or a list of one list per trait ({q}).")
+    out = []
+    for t, vs in enumerate(items):
+        if isinstance(vs, (str, np.str_)) or np.ndim(vs) == 0:
+            vs = [vs]
+        lst = [lookup(v, names_x, "variant") for v in vs]
+        if len(lst) > 4:
+            raise AtlasqtlError(f"cis_screen: trait {t} conditions on {len(lst)} variants; at most 4 are supported.")
+        if len(set(lst)) != len(lst):
+            raise AtlasqtlError(f"cis_screen: condition_on names a variant of trait {t} more than once.")
+        out.append(lst)
+    return out
+
+
+def _refuse_with_condition(permutations, Y):
+    if permutations is not None:
+        raise AtlasqtlError("cis_screen: condition_on= together with permutations= is not supported: permutation nulls are "
+                            "computed for the unconditional scan only. Run the two separately, or cis_independent().")
+    if Y is not None and np.isnan(np.asarray(Y, dtype=np.float64)).any():
+        raise AtlasqtlError("cis_screen: condition_on= needs complete Y; Y has missing values.")
+
+
+def cis_handle(prep, names_x, names_y, s_lo, s_hi, p_value=None, fdr=None, max_pairs=None, permutations=None, condition_on=None):
     """The cis scan on a PreparedData as it stands, with the windows given as index ranges over its columns: cis_screen()
-    without the preparation and without cis_windows.  Returns the result without the rmvd_* fields."""
+    without the preparation and without cis_windows.  condition_on: as for cis_screen(), by index into names_x / names_y or by
+    name; None takes the unconditional path unchanged.  Returns the result without the rmvd_* fields."""
     from .api import AtlasqtlResult
     p, q = int(prep.p), int(prep.q)
     o = cis_options(p_value, fdr, max_pairs)
+    cond = None
+    if condition_on is not None:
+        cond = condition_lists(condition_on, names_x, names_y)
+        _refuse_with_condition(permutations, prep.Y)
     po = permutation_options(permutations, int(prep.n))
     s_lo, s_hi = prep._cis_windows_arg(s_lo, s_hi, "cis_screen")
     n_cis = (s_hi.astype(np.int64) - s_lo.astype(np.int64))
@@ -148,11 +215,23 @@ def cis_handle(prep, names_x, names_y, s_lo, s_hi, p_value=None, fdr=None, max_p
     level = o["level"] if o["mode"] != "bonferroni" else 0.05 / max(M, 1)
     n_obs = np.sum(~np.isnan(prep.Y), axis=0).astype(np.int64)
     df = n_obs - 2 - int(prep.n_cov)
-    cut = r2_cutoff(level, df)
     cap = int(min(M, INITIAL_CAP))
-    out = prep.cis(s_lo, s_hi, cut, cap)
+    if cond is None:
+        def scan(cut, cap):
+            return prep.cis(s_lo, s_hi, cut, cap)
+    else:
+        def scan(cut, cap):
+            return prep.cis_conditional(s_lo, s_hi, cond, cut, cap)
+        # the cutoff on r^2 needs df_t, which needs k_eff: the list's length, unless the device drops a collinear column
+        df = df - np.where(n_cis > 0, np.asarray([len(c) for c in cond], dtype=np.int64), 0)
+    cut = r2_cutoff(level, df)
+    out = scan(cut, cap)
+    if cond is not None and np.any(n_obs - 2 - int(prep.n_cov) - out["k_eff"] != df):   # then once more, with the k_eff reported
+        df = n_obs - 2 - int(prep.n_cov) - out["k_eff"]
+        cut = r2_cutoff(level, df)
+        out = scan(cut, cap)
     if out["n_pairs"] > cap:                                  # the complete set, whatever order the first call filled its rows in
-        out = prep.cis(s_lo, s_hi, cut, out["n_pairs"])
+        out = scan(cut, out["n_pairs"])
     snp, trait, r = out["snp"], out["trait"], out["r"]
     dfr = df[trait].astype(np.float64)
     t, pv = t_and_pvalue(r, dfr)
@@ -177,6 +256,9 @@ def cis_handle(prep, names_x, names_y, s_lo, s_hi, p_value=None, fdr=None, max_p
                          best_pvalue=best_p, n_obs=n_obs, df=df, n_undefined=out["n_undef"], n=int(prep.n), p=p, q=q,
                          threshold=dict(mode=o["mode"], level=level, r2_cut=cut, n_tests=n_tests), plan=out["plan"],
                          names_x=list(names_x), names_y=list(names_y))
+    if cond is not None:
+        res["condition_on"] = cond
+        res["k_eff"] = out["k_eff"]
     if po is not None:
         max_r2 = prep.cis_permute(s_lo, s_hi, po["perms"])
         res["permutation"] = dict(n=po["n"], seed=po["seed"], max_r2=max_r2,
@@ -192,7 +274,8 @@ def _per_predictor(values, p_given, name):
 
 
 def cis_screen(Y, X, trait_chrom, trait_start, trait_end=None, window=1_000_000, snp_chrom=None, snp_pos=None, p_value=None,
-               fdr=None, max_pairs=None, permutations=None, covariates=None, ld_prune=None, transform_y=None, device=0):
+               fdr=None, max_pairs=None, permutations=None, covariates=None, ld_prune=None, transform_y=None, device=0,
+               condition_on=None):
     """Every trait of Y tested against the predictors of X within `window` base pairs of it, on the GPU: cis-QTL mapping.
 
     X and Y are prepared exactly as marginal_screen() prepares them.  trait_chrom, trait_start, trait_end (default:
@@ -226,10 +309,21 @@ def cis_screen(Y, X, trait_chrom, trait_start, trait_end=None, window=1_000_000,
         NaN where B < 2, v = 0 or a shape <= 0],
         trait_qvalue [Benjamini-Hochberg of trait_pvalue_beta over the traits with a defined pair: the eGenes are
         trait_qvalue <= level]).
-    With covariates= the residualised Y is permuted, as marginal_screen() describes."""
+    With covariates= the residualised Y is permuted, as marginal_screen() describes.
+
+    condition_on (None; a dict trait -> variants; or a list of q lists; traits and variants by index into names_y / names_x,
+    the kept columns, or by name) makes the scan conditional: trait t is tested after its own at most 4 variants, inside its
+    window or not, have been regressed out of it and of every predictor (aq_prep_cis_cond).  r is then the partial
+    correlation, df = n - 2 - d - k_eff, and a pair is also undefined when the predictor is collinear with the list (each
+    listed variant itself is) or the list explains the whole trait.  The result then also carries condition_on (the q index
+    lists) and k_eff (per trait, the listed variants not collinear with the earlier ones; 0 where the window is empty).
+    Complete Y only, and not together with permutations=: both are refused before anything is computed.  A window of
+    [0, p) for every trait is the conditional trans scan.  Without the argument the call is the unconditional scan above."""
     from .plink import PlinkBed
     cis_options(p_value, fdr, max_pairs)                       # before the first device call
     permutation_options(permutations)
+    if condition_on is not None:
+        _refuse_with_condition(permutations, None if isinstance(Y, str) else Y)
     if not _is_whole(window) or int(window) < 0:
         raise AtlasqtlError(f"cis_screen: window must be a whole number >= 0, not {window!r}.")
     if isinstance(X, PlinkBed):
@@ -248,7 +342,165 @@ def cis_screen(Y, X, trait_chrom, trait_start, trait_end=None, window=1_000_000,
         if len(np.atleast_1d(trait_start)) != int(prep.q):
             raise AtlasqtlError(f"cis_screen: trait_chrom, trait_start and trait_end must hold one value per trait ({int(prep.q)}).")
         s_lo, s_hi = cis_windows(snp_chrom[kept], snp_pos[kept], trait_chrom, trait_start, trait_end, window)
-        res = cis_handle(prep, dat["names_x"], dat["names_y"], s_lo, s_hi, p_value, fdr, max_pairs, permutations)
+        res = cis_handle(prep, dat["names_x"], dat["names_y"], s_lo, s_hi, p_value, fdr, max_pairs, permutations, condition_on)
+    finally:
+        prep.close()
+    for key in ("rmvd_cst_x", "rmvd_coll_x", "rmvd_cov_x", "rmvd_ld_x"):
+        res[key] = dat[key]
+    res["n_covariates"] = dat["n_covariates"]
+    return res
+
+
+MAX_SIGNALS = 5                                        # one more than the variants a trait can be conditioned on
+
+
+def independent_signals_(scan, best_snp, best_pvalue, threshold, max_signals=MAX_SIGNALS, best_r=None, df=None):
+    """The forward-backward conditional pass of QTLtools (and tensorQTL's map_independent) over all traits together, on the
+    host: the scans themselves are `scan`, so the loop runs against the GPU or against numpy alike.
+
+    scan(cond, active) -> dict(best_snp, best_pvalue[, best_r, df]), q entries each: the conditional scan in which trait t is
+    conditioned on the variants cond[t]; only the entries of the traits with active[t] are read (the others may be scanned
+    with an empty window, so that they cost nothing), best_snp < 0 meaning that no pair is defined.
+    best_snp, best_pvalue[, best_r, df]: the unconditional scan's.  threshold: per trait, the nominal p-value a signal must
+    reach; NaN for a trait that is no eGene.  max_signals: 1 ... 5.
+
+    Signal 1 of a trait with a threshold is its best_snp.  Forward rounds j = 1 ... max_signals - 1: one scan covers all
+    traits still active, each conditioned on its own j signals; a trait whose conditional best has p <= threshold gains that
+    variant and stays active, the others leave; the rounds stop when no trait gains one.  Backward rounds i = 0, 1, ... for the
+    traits with m >= 2 signals: conditioned on the forward set without signal i -- the forward sets stay fixed throughout --
+    the best variant replaces signal i's lead if its p <= threshold, otherwise the signal is dropped.  A trait with one signal
+    keeps it as it is.
+    Returns dict(forward: per trait the forward variants; signals: per trait a list of dict(rank [1-based position in the
+    forward set], snp, forward_snp, pvalue, r, df [NaN / -1 where the scan does not give them]); n_signals)."""
+    if not _is_whole(max_signals) or not 1 <= int(max_signals) <= MAX_SIGNALS:
+        raise AtlasqtlError(f"cis_independent: max_signals must be a whole number from 1 to {MAX_SIGNALS}, not {max_signals!r}.")
+    best_snp = np.asarray(best_snp)
+    best_pvalue = np.asarray(best_pvalue, dtype=np.float64)
+    threshold = np.asarray(threshold, dtype=np.float64)
+    q = best_snp.shape[0]
+
+    def row(out, t):
+        r = out.get("best_r")
+        d = out.get("df")
+        return dict(snp=int(out["best_snp"][t]), pvalue=float(out["best_pvalue"][t]), r=float(r[t]) if r is not None else np.nan,
+                    df=int(d[t]) if d is not None else -1)
+
+    active = ~np.isnan(threshold) & (best_snp >= 0)
+    forward = [[int(best_snp[t])] if active[t] else [] for t in range(q)]
+    for _ in range(1, int(max_signals)):
+        if not active.any():
+            break
+        out = scan([list(forward[t]) if active[t] else [] for t in range(q)], active.copy())
+        for t in np.nonzero(active)[0]:
+            if out["best_snp"][t] >= 0 and out["best_pvalue"][t] <= threshold[t]:
+                forward[t].append(int(out["best_snp"][t]))
+            else:
+                active[t] = False
+    primary = dict(best_snp=best_snp, best_pvalue=best_pvalue, best_r=best_r, df=df)
+    signals = [[dict(rank=1, forward_snp=f[0], **row(primary, t))] if len(f) == 1 else [] for t, f in enumerate(forward)]
+    for i in range(max((len(f) for f in forward), default=0)):
+        active = np.asarray([len(f) >= 2 and len(f) > i for f in forward], dtype=bool)
+        if not active.any():
+            break
+        out = scan([f[:i] + f[i + 1:] if active[t] else [] for t, f in enumerate(forward)], active.copy())
+        for t in np.nonzero(active)[0]:
+            if out["best_snp"][t] >= 0 and out["best_pvalue"][t] <= threshold[t]:
+                signals[t].append(dict(rank=i + 1, forward_snp=forward[t][i], **row(out, t)))
+    return dict(forward=forward, signals=signals, n_signals=np.asarray([len(s) for s in signals], dtype=np.int64))
+
+
+def cis_independent_handle(prep, names_x, names_y, s_lo, s_hi, fdr=0.05, permutations=1000, max_signals=MAX_SIGNALS):
+    """cis_independent() on a PreparedData as it stands, with the windows given as index ranges over its columns.  Returns
+    the result without the rmvd_* fields."""
+    from scipy.stats import beta
+    from .api import AtlasqtlResult
+    if isinstance(fdr, (bool, np.bool_)) or not isinstance(fdr, (int, float, np.integer, np.floating)) or not 0 < float(fdr) <= 1:
+        raise AtlasqtlError(f"cis_independent: fdr must be a number in (0, 1], not {fdr!r}.")
+    if permutations is None:
+        raise AtlasqtlError("cis_independent: permutations are required: they decide the eGenes and each gene's threshold.")
+    if not _is_whole(max_signals) or not 1 <= int(max_signals) <= MAX_SIGNALS:
+        raise AtlasqtlError(f"cis_independent: max_signals must be a whole number from 1 to {MAX_SIGNALS}, not {max_signals!r}.")
+    if np.isnan(prep.Y).any():
+        raise AtlasqtlError("cis_independent: the conditional scans need complete Y; Y has missing values.")
+    primary = cis_handle(prep, names_x, names_y, s_lo, s_hi, permutations=permutations)
+    s_lo, s_hi = primary["window"]
+    q = int(prep.q)
+    perm = primary["permutation"]
+    pbeta = perm["trait_pvalue_beta"]
+    with np.errstate(invalid="ignore"):
+        egene = perm["trait_qvalue"] <= float(fdr)
+    threshold = np.full(q, np.nan)
+    if egene.any():
+        ok = ~np.isnan(perm["beta_shape1"])
+        threshold[ok] = beta.ppf(float(np.max(pbeta[egene])), perm["beta_shape1"][ok], perm["beta_shape2"][ok])
+    base_df = primary["df"]
+    no_cut = np.full(q, np.inf)
+
+    def scan(cond, active):
+        out = prep.cis_conditional(np.where(active, s_lo, 0), np.where(active, s_hi, 0), cond, no_cut, 0)
+        d = base_df - out["k_eff"]
+        pv = np.full(q, np.nan)
+        has = out["best_snp"] >= 0
+        pv[has] = t_and_pvalue(out["best_r"][has], d[has])[1]
+        return dict(best_snp=out["best_snp"], best_pvalue=pv, best_r=out["best_r"], df=d)
+
+    loop = independent_signals_(scan, primary["best_snp"], primary["best_pvalue"], np.where(egene, threshold, np.nan), max_signals,
+                                best_r=primary["best_r"], df=base_df)
+    rows = [(t, s) for t in range(q) for s in loop["signals"][t]]
+    snp = np.asarray([s["snp"] for _, s in rows], dtype=np.int32)
+    trait = np.asarray([t for t, _ in rows], dtype=np.int32)
+    r = np.asarray([s["r"] for _, s in rows], dtype=np.float64)
+    dfs = np.asarray([s["df"] for _, s in rows], dtype=np.int64)
+    signals = dict(trait=trait, rank=np.asarray([s["rank"] for _, s in rows], dtype=np.int32), snp=snp,
+                   forward_snp=np.asarray([s["forward_snp"] for _, s in rows], dtype=np.int32), r=r,
+                   t=t_and_pvalue(r, dfs)[0] if rows else np.zeros(0), df=dfs,
+                   pvalue=np.asarray([s["pvalue"] for _, s in rows], dtype=np.float64),
+                   snp_name=np.asarray(names_x, dtype=object)[snp], trait_name=np.asarray(names_y, dtype=object)[trait])
+    return AtlasqtlResult(signals=signals, n_signals=loop["n_signals"], forward=loop["forward"], threshold=threshold, egene=egene,
+                          fdr=float(fdr), max_signals=int(max_signals), primary=primary, n=int(prep.n), p=int(prep.p), q=q,
+                          names_x=list(names_x), names_y=list(names_y))
+
+
+def cis_independent(Y, X, trait_chrom, trait_start, trait_end=None, window=1_000_000, snp_chrom=None, snp_pos=None, fdr=0.05,
+                    permutations=1000, max_signals=MAX_SIGNALS, covariates=None, ld_prune=None, transform_y=None, device=0):
+    """The independent cis signals of every eGene, by the forward-backward conditional pass of QTLtools (tensorQTL's
+    map_independent), on one prepared handle on the GPU.  Arguments as for cis_screen(); complete Y only.
+
+    (a) The unconditional scan with permutations (cis_screen(permutations=...)).  The eGenes are the traits with
+        trait_qvalue <= fdr; p* is the largest trait_pvalue_beta among them; each trait's nominal threshold is
+        Beta(beta_shape1_t, beta_shape2_t).ppf(p*).  Signal 1 of an eGene is its best_snp.
+    (b), (c) independent_signals_ with the conditional scan (cis_screen(condition_on=...)): every round is ONE scan over all
+        genes still active, each conditioned on its own variants, the others with an empty window; a conditional best is
+        compared at its reduced df = n - 2 - d - k_eff.
+    Returns an AtlasqtlResult with
+      signals: one row per signal kept, ordered by (trait, rank): trait, rank (1-based position in the forward set), snp (the
+        lead after the backward pass), forward_snp (the variant the forward pass found), r, t, df, pvalue (conditional on the
+        trait's other forward variants; unconditional for a trait with one signal), snp_name, trait_name;
+      n_signals: per trait; forward: per trait the forward variants; threshold: per trait (NaN where the beta approximation
+      is NaN, or there is no eGene); egene; primary: the result of (a); names_x, names_y, n, p, q, n_covariates, rmvd_*."""
+    from .plink import PlinkBed
+    if isinstance(X, PlinkBed):
+        snp_chrom = X.chrom if snp_chrom is None else snp_chrom
+        snp_pos = X.pos if snp_pos is None else snp_pos
+    if snp_chrom is None or snp_pos is None:
+        raise AtlasqtlError("cis_independent: snp_chrom and snp_pos are required unless X is a PlinkBed.")
+    if not _is_whole(max_signals) or not 1 <= int(max_signals) <= MAX_SIGNALS:
+        raise AtlasqtlError(f"cis_independent: max_signals must be a whole number from 1 to {MAX_SIGNALS}, not {max_signals!r}.")
+    if permutations is None:
+        raise AtlasqtlError("cis_independent: permutations are required: they decide the eGenes and each gene's threshold.")
+    permutation_options(permutations)
+    p_given = X.shape[1] if hasattr(X, "shape") else np.asarray(X).shape[1]
+    snp_chrom = _per_predictor(snp_chrom, p_given, "snp_chrom")
+    snp_pos = _per_predictor(snp_pos, p_given, "snp_pos")
+    dat = prepare_data_(Y, X, 0.1, 1, None, 0, None, None, device=device, covariates=covariates, ld_prune=ld_prune,
+                        transform_y=transform_y)
+    prep = dat["X"]
+    try:
+        kept = ~np.asarray(dat["bool_rmvd_x"], dtype=bool)
+        if len(np.atleast_1d(trait_start)) != int(prep.q):
+            raise AtlasqtlError(f"cis_independent: trait_chrom, trait_start and trait_end must hold one value per trait ({int(prep.q)}).")
+        s_lo, s_hi = cis_windows(snp_chrom[kept], snp_pos[kept], trait_chrom, trait_start, trait_end, window)
+        res = cis_independent_handle(prep, dat["names_x"], dat["names_y"], s_lo, s_hi, fdr, permutations, max_signals)
     finally:
         prep.close()
     for key in ("rmvd_cst_x", "rmvd_coll_x", "rmvd_cov_x", "rmvd_ld_x"):

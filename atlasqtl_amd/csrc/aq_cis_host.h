@@ -1,0 +1,148 @@
+// aq_cis_host.h -- the host side that the entries of the cis scan share (aq_prep_cis.hip: the plain scan and its permutation
+// nulls; aq_prep_cis_cond.hip: the conditional scan): the device buffers of one call, the set-up that runs the planner of
+// aq_cis_plan.h and uploads the order, the work list and the per-trait arrays, the arguments every tile kernel takes, and
+// the column sums.  Static functions: each of the two units has its own copy.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdlib>
+#include <limits>
+#include <stdint.h>
+#include <string>
+#include <vector>
+#include "aq_prep.h"          // aq_prep, aq_time_launches; aq_internal.h: aq_fail, AQ_HIP, aq_need_device, aq_need_acc_layout, AqDev
+#include "aq_cis_kernels.h"   // aq_k_cis_*; aq_k_ms_traitstats, aq_k_ms_colstats; aq_cis_make_plan
+
+// the device side of one call: what does not change with the permutation, the scan's outputs, and the buffers of one launch of
+// permutations
+struct AqCisBuf {
+  AqDev<double> Yo, sx, sxx, syy, cut, part_r, best_r, r, Yp, max_r2;
+  AqDev<int> mt;
+  AqDev<int32_t> order, lo, hi, first_item, item_tile, item_p0, part_s, best_s, snp, trait, perm;
+  AqDev<unsigned long long> counter, undef, key;
+  std::vector<int> mt_host;                  // m_t per ordered trait with a window
+  aq_cis_plan pl{};
+  aq_cis_work wk;
+  int64_t cap = 0;
+};
+
+// an environment variable that forces a plan field: 0 when it is not set, -1 when it is no number >= 1 (the planner's message)
+static int aq_cis_env(const char *name) {
+  const char *e = getenv(name);
+  if (!e) return 0;
+  const int v = atoi(e);
+  return v < 1 ? -1 : v;
+}
+
+template <typename T>
+static int aq_cis_upload(AqDev<T> *dst, const std::vector<T> &src) {
+  AQ_TRY(dst->alloc(src.size() > 0 ? src.size() : 1));
+  if (!src.empty()) AQ_HIP(hipMemcpy(dst->get(), src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return AQ_OK;
+}
+
+// Syy_t and m_t of the handle's traits, whether any value is missing (over ALL traits, as aq_prep_marginal decides it, so
+// that the same instance computes the same bits), the plan, the order and the work list; the per-trait arrays in the order;
+// the buffers of the scan (scan) and of one launch of permutations (n_perm > 0).  r2_cut may be NULL (the *_time entry sets
+// its own, the permutations use none).
+static int aq_cis_setup(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, const double *r2_cut, int64_t cap, bool scan, int n_perm,
+                        const char *who, AqCisBuf *b) {
+  const size_t p1 = (size_t)h->p_kept, q = (size_t)h->q, n = (size_t)h->n;
+  std::vector<double> syy(q);
+  std::vector<int> mt(q);
+  {
+    AqDev<double> dsyy;
+    AqDev<int> dmt;
+    AQ_TRY(dsyy.alloc(q));
+    AQ_TRY(dmt.alloc(q));
+    hipLaunchKernelGGL(aq_k_ms_traitstats, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, h->Yc.get(), h->n, h->q, dsyy.get(),
+                       dmt.get());
+    AQ_HIP(hipGetLastError());
+    AQ_HIP(hipMemcpy(syy.data(), dsyy.get(), q * sizeof(double), hipMemcpyDeviceToHost));
+    AQ_HIP(hipMemcpy(mt.data(), dmt.get(), q * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  int masked = 0;
+  for (size_t t = 0; t < q; t++) masked |= mt[t] < h->n;
+  int ncu = 0;
+  AQ_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
+  std::string err;
+  const int rc = aq_cis_make_plan(h->n, h->p_kept, h->q, masked, ncu > 0 ? ncu : 256, s_lo, s_hi, n_perm,
+                                  n_perm > 0 ? aq_cis_env("AQ_CIS_PB") : 0, n_perm > 0 ? aq_cis_env("AQ_CIS_BATCH") : 0, who, &b->pl, &b->wk,
+                                  &err);
+  if (rc != AQ_OK) return aq_fail(rc, err);
+  const size_t qa = (size_t)b->wk.q_active, W = (size_t)b->pl.n_items;
+  b->cap = cap;
+  {
+    std::vector<double> syy_o(qa), cut_o(qa);
+    std::vector<int32_t> lo_o(qa), hi_o(qa);
+    b->mt_host.resize(qa);
+    for (size_t j = 0; j < qa; j++) {
+      const size_t t = (size_t)b->wk.order[j];
+      syy_o[j] = syy[t];
+      b->mt_host[j] = mt[t];
+      cut_o[j] = r2_cut ? r2_cut[t] : std::numeric_limits<double>::infinity();
+      lo_o[j] = s_lo[t];
+      hi_o[j] = s_hi[t];
+    }
+    AQ_TRY(aq_cis_upload(&b->syy, syy_o));
+    AQ_TRY(aq_cis_upload(&b->mt, b->mt_host));
+    AQ_TRY(aq_cis_upload(&b->cut, cut_o));
+    AQ_TRY(aq_cis_upload(&b->lo, lo_o));
+    AQ_TRY(aq_cis_upload(&b->hi, hi_o));
+  }
+  AQ_TRY(aq_cis_upload(&b->order, b->wk.order));
+  AQ_TRY(aq_cis_upload(&b->first_item, b->wk.first_item));
+  AQ_TRY(aq_cis_upload(&b->item_tile, b->wk.item_tile));
+  AQ_TRY(aq_cis_upload(&b->item_p0, b->wk.item_p0));
+  if (!masked) {
+    AQ_TRY(b->sx.alloc(p1));
+    AQ_TRY(b->sxx.alloc(p1));
+  }
+  if (scan) {
+    AQ_TRY(b->Yo.alloc(qa > 0 ? qa * n : 1));
+    AQ_TRY(b->counter.alloc(1));
+    AQ_TRY(b->undef.alloc(q));
+    AQ_TRY(b->part_r.alloc(W > 0 ? W * AQ_CIS_TILE : 1));
+    AQ_TRY(b->part_s.alloc(W > 0 ? W * AQ_CIS_TILE : 1));
+    AQ_TRY(b->best_r.alloc(q));
+    AQ_TRY(b->best_s.alloc(q));
+    if (cap > 0) {
+      AQ_TRY(b->snp.alloc((size_t)cap));
+      AQ_TRY(b->trait.alloc((size_t)cap));
+      AQ_TRY(b->r.alloc((size_t)cap));
+    }
+  }
+  if (n_perm > 0) {
+    const size_t batch = (size_t)b->pl.batch;
+    AQ_TRY(b->Yp.alloc(batch * (qa > 0 ? qa : 1) * n));
+    AQ_TRY(b->perm.alloc(batch * n));
+    AQ_TRY(b->key.alloc(batch * q));
+    AQ_TRY(b->max_r2.alloc(batch * q));
+  }
+  return AQ_OK;
+}
+
+static aq_cis_args aq_cis_common_args(aq_prep *h, AqCisBuf &b) {
+  aq_cis_args a{};
+  a.Xs = h->Xs.get();
+  a.n = h->n; a.p1 = h->p_kept; a.q = h->q; a.qa = b.wk.q_active; a.n_cov = h->n_cov; a.W = (int)b.pl.n_items;
+  a.item_tile = b.item_tile.get(); a.item_p0 = b.item_p0.get();
+  a.sx = b.sx.get(); a.sxx = b.sxx.get(); a.syy = b.syy.get(); a.cut = b.cut.get(); a.mt = b.mt.get();
+  a.lo = b.lo.get(); a.hi = b.hi.get(); a.orig = b.order.get();
+  return a;
+}
+
+// Sx and Sxx of every column for the complete instances.  Asynchronous.
+static int aq_cis_colstats(aq_prep *h, AqCisBuf &b) {
+  if (!b.pl.masked) {
+    hipLaunchKernelGGL(aq_k_ms_colstats, dim3((unsigned)h->p_kept), dim3(256), 0, 0, h->Xs.get(), h->n, b.sx.get(), b.sxx.get());
+    AQ_HIP(hipGetLastError());
+  }
+  return AQ_OK;
+}
+
+// the window checks that need the handle's p1 and q, under the entry's name
+static int aq_cis_need_windows(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, const char *who) {
+  std::string err;
+  const int rc = aq_cis_check_windows(s_lo, s_hi, h->q, h->p_kept, who, &err);
+  return rc == AQ_OK ? AQ_OK : aq_fail(rc, err);
+}

@@ -278,6 +278,61 @@ class PreparedData:
                    "aq_prep_cis_perm")
         return max_r2
 
+    def _cis_cond_arg(self, cond, who):
+        """The conditioning lists as the library takes them, (cond_ptr [q + 1 offsets], cond_idx), int32 each: `cond` is q lists
+        of at most 4 distinct column indices in [0, p), checked before the cast to int32 can wrap a value."""
+        cond = list(cond)
+        if len(cond) != self.q:
+            raise AtlasqtlError(f"{who}: cond must hold one list per trait ({self.q}), not {len(cond)}.")
+        ptr = np.zeros(self.q + 1, dtype=np.int32)
+        idx = []
+        for t, c in enumerate(cond):
+            a = np.atleast_1d(np.asarray(c))
+            if a.size == 0:
+                a = np.zeros(0, dtype=np.int64)
+            if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+                raise AtlasqtlError(f"{who}: the conditioning list of trait {t} must hold whole numbers, not {a.dtype} {a.shape}.")
+            if a.size > 4:
+                raise AtlasqtlError(f"{who}: trait {t} conditions on {a.size} variants; at most 4 are supported.")
+            if a.size and (a.min() < 0 or a.max() >= self.p):
+                raise AtlasqtlError(f"{who}: the conditioning list of trait {t} must hold column indices in [0, {self.p}).")
+            if np.unique(a).size != a.size:
+                raise AtlasqtlError(f"{who}: the conditioning list of trait {t} names a variant more than once.")
+            idx += [int(v) for v in a]
+            ptr[t + 1] = len(idx)
+        return ptr, np.ascontiguousarray(idx + [0], dtype=np.int32)      # one spare entry: never an empty buffer
+
+    def cis_conditional(self, s_lo, s_hi, cond, r2_cut, cap):
+        """The conditional cis scan of the matrix as it stands: aq_prep_cis_cond.  s_lo, s_hi, r2_cut, cap: as for cis().
+        cond: q lists, trait t is tested after the columns cond[t] (at most 4 distinct indices, in this order, inside the
+        trait's window or not) have been regressed out of it and of every predictor.  Complete Y only.  Returns the dict of
+        cis() with r the partial correlation, and k_eff: per trait, the columns of its list that were not collinear with the
+        earlier ones (df_t = n - 2 - n_cov - k_eff[t]; 0 for a trait with an empty window); plan: the dict of
+        aq_ciscond_plan, the fields of its aq_cis_plan alongside."""
+        import ctypes as C
+        lo, hi = self._cis_windows_arg(s_lo, s_hi, "cis_conditional")
+        ptr, idx = self._cis_cond_arg(cond, "cis_conditional")
+        cut = np.ascontiguousarray(r2_cut, dtype=np.float64)
+        if cut.shape != (self.q,):
+            raise AtlasqtlError(f"cis_conditional: r2_cut must hold one cutoff per trait ({self.q}), not {cut.shape}.")
+        if np.isnan(self.Y).any():
+            raise AtlasqtlError("cis_conditional: Y has missing values; the conditional scan takes complete Y only.")
+        cap = int(cap)
+        rows = max(cap, 0)
+        snp = np.empty(rows, dtype=np.int32); trait = np.empty(rows, dtype=np.int32); r = np.empty(rows)
+        best_snp = np.empty(self.q, dtype=np.int32); best_r = np.empty(self.q); n_undef = np.zeros(self.q, dtype=np.int64)
+        k_eff = np.zeros(self.q, dtype=np.int32)
+        n_pairs, plan = C.c_int64(0), _lib.AqCiscondPlan()
+        _lib.check(_lib.lib().aq_prep_cis_cond(self.handle, _lib.as_ip(lo), _lib.as_ip(hi), _lib.as_ip(ptr), _lib.as_ip(idx),
+                                               _lib.as_dp(cut), cap, _lib.as_ip(snp), _lib.as_ip(trait), _lib.as_dp(r), C.byref(n_pairs),
+                                               _lib.as_ip(best_snp), _lib.as_dp(best_r), n_undef.ctypes.data_as(C.POINTER(C.c_int64)),
+                                               _lib.as_ip(k_eff), C.byref(plan)), "aq_prep_cis_cond")
+        k = min(int(n_pairs.value), rows)
+        pd = {name: int(getattr(plan.cis, name)) for name, _ in _lib.AqCisPlan._fields_}
+        pd.update({name: int(getattr(plan, name)) for name, _ in _lib.AqCiscondPlan._fields_ if name != "cis"})
+        return dict(snp=snp[:k], trait=trait[:k], r=r[:k], n_pairs=int(n_pairs.value), best_snp=best_snp, best_r=best_r,
+                    n_undef=n_undef, k_eff=k_eff, plan=pd)
+
     def close(self):
         if self.handle is not None:
             _lib.lib().aq_prep_destroy(self.handle)

@@ -809,6 +809,60 @@ int aq_prep_cis_time(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi,
                      double *ms_per_perm, aq_cis_plan *plan_out);
 
 /* ------------------------------------------------------------------------------------------
+ * Conditional cis scan of a finished handle: the scan of aq_prep_cis after each trait's own conditioning variants have been
+ * regressed out of the trait and of every predictor, which asks whether a second, independent signal sits in a window or only
+ * LD proxies of the first (the conditional pass of FastQTL, QTLtools and tensorQTL's map_independent).
+ * The statistic.  Complete Y only.  Xs and Yc are the prepared matrices of the handle, centred and, with covariates,
+ * residualised; n_cov as in aq_prep_marginal.  Trait t has a conditioning list C_t of 0 <= k_t <= 4 distinct predictor
+ * indices in [0, p1), in the order given, independent of the trait's window: cond_idx[cond_ptr[t]] ... cond_idx[cond_ptr[t + 1] - 1].
+ *   Basis.  Go through C_t in order.  v = Xs[:, c].  Project out the basis vectors accepted so far, twice: in each of two
+ *   passes, for every accepted q in the order of acceptance, v <- v - q (q'v) (Gram-Schmidt with one re-orthogonalisation).
+ *   If |v|^2 <= 1e-10 |Xs[:, c]|^2 the column is dropped: a conditioning variant collinear with the earlier ones.  Otherwise
+ *   q = v / |v| is accepted.  k_eff[t] is the number accepted.
+ *   Residual trait.  y~_t = y_t - sum_j q_tj (q_tj' y_t), S~yy_t = sum y~^2.  With k_eff = 0, y~_t is the copy of y_t.
+ *   Per pair with s_lo[t] <= s < s_hi[t]:  a_j = q_tj' x_s;  Vx = (Sxx - Sx^2 / n) - (a_1^2 + ... + a_k^2), the parenthesis
+ *   evaluated first, exactly as the plain scan does;  r = (x_s' y~_t) / sqrt(Vx S~yy_t);  df_t = n - 2 - n_cov - k_eff[t].
+ *   Undefined pairs.  A pair is undefined when Vx <= 1e-10 Sxx, when S~yy_t <= 1e-10 Syy_t, or when df_t < 1.  Its r is NaN;
+ *   it is counted and never selected.  The first condition removes each conditioning variant from its own trait's tests, and
+ *   anything collinear with the list.
+ * r is the partial correlation of x_s and y_t given the list, so t = r sqrt(df_t / (1 - r^2)) is the t statistic of x_s in the
+ * regression of y_t on x_s and the list.  The sums factor into 1 + KC dense products against one staged panel of Xs (the
+ * numerators, and one product per basis vector), KC = the smallest of 1, 2, 4 that holds the longest list of a trait with a
+ * window; nothing of size p1 q is stored.  A trait with an empty list gets r, best_snp, best_r and n_undef of aq_prep_cis on
+ * the same handle to the bit, whatever the other traits' lists are.  No floating-point atomics: two calls give the same set
+ * of rows and the same bits in every other output.
+ *   aq_prep_cis_cond        r2_cut, cap, snp, trait, r, n_pairs, best_snp, best_r, n_undef: as for aq_prep_cis.  k_eff:
+ *                           int32[q], 0 for a trait with an empty window (its basis is not formed).  plan_out: the plan used.
+ *                           Any output may be NULL.  The handle is not changed.
+ *   aq_ciscond_plan_query   the plan without a device, a pure function of its arguments (the lists enter by their lengths).
+ *                           A list longer than 4, or basis panels and residual traits above 4 GiB together, are
+ *                           AQ_ERR_UNSUPPORTED, as is what aq_cis_plan_query refuses.
+ *   aq_prep_cis_cond_time   measurement, after aq_prep_cis_time: ms_basis, the basis kernel alone; ms_scan, the other kernels
+ *                           of one scan (the column sums, the tile kernel, the reduction of the bests), counting only, with
+ *                           the cutoff t^2 = 40 at df_t.  Each `reps` times between two events after a warm-up.
+ * AQ_ERR_ARG, in this order, before any device call: a NULL r2_cut (ms_basis, ms_scan); cap < 0 (reps < 1); a NULL s_lo, s_hi,
+ * cond_ptr or cond_idx; a NULL handle; cond_ptr[0] != 0 or decreasing offsets; a list longer than 4; an index outside
+ * [0, p1); an index repeated within a trait; the window errors of aq_prep_cis; a NaN cutoff.  A handle whose Y has missing
+ * values is AQ_ERR_UNSUPPORTED, and the message says so.  No index out of range reaches a kernel.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_ciscond_plan {
+  aq_cis_plan cis;            /* the plan of the windows: complete Y, no permutations             */
+  int32_t kc;                 /* the tile kernel's instance: 0 (the plain scan's), 1, 2 or 4      */
+  int32_t max_k;              /* the longest list of a trait with a window                        */
+  int32_t lds_bytes;          /* static LDS of a workgroup of that instance, <= 64 KiB            */
+  int32_t streams;            /* 1 + kc matrix-instruction streams per staged panel of Xs         */
+  int64_t qo_bytes;           /* the basis panels: 8 kc max(q_active, 1) n                        */
+  int64_t yo_bytes;           /* the residual traits: 8 max(q_active, 1) n                        */
+} aq_ciscond_plan;
+int aq_ciscond_plan_query(int32_t n, int32_t p1, int32_t q, int32_t ncu, const int32_t *s_lo, const int32_t *s_hi,
+                          const int32_t *cond_ptr, aq_ciscond_plan *out);
+int aq_prep_cis_cond(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, const int32_t *cond_ptr, const int32_t *cond_idx,
+                     const double *r2_cut, int64_t cap, int32_t *snp, int32_t *trait, double *r, int64_t *n_pairs, int32_t *best_snp,
+                     double *best_r, int64_t *n_undef, int32_t *k_eff, aq_ciscond_plan *plan_out);
+int aq_prep_cis_cond_time(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, const int32_t *cond_ptr, const int32_t *cond_idx,
+                          int32_t reps, double *ms_basis, double *ms_scan, aq_ciscond_plan *plan_out);
+
+/* ------------------------------------------------------------------------------------------
  * Prediction: the fitted model applied to genotypes,
  *   Yhat = Xt B,   B = beta_vb = gam_vb * mu_beta_vb (p x q, R/update_vb.R:17),   Xt = (X_new - center) / scale per column,
  * n_new x q: the genetic component of the traits on the scale of the prepared Y, in-sample (the X_beta_vb that the reference's
