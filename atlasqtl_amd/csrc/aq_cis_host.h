@@ -1,16 +1,11 @@
 // aq_cis_host.h -- the host side that the entries of the cis scan share (aq_prep_cis.hip: the plain scan and its permutation
 // nulls; aq_prep_cis_cond.hip: the conditional scan): the device buffers of one call, the set-up that runs the planner of
 // aq_cis_plan.h and uploads the order, the work list and the per-trait arrays, the arguments every tile kernel takes, and
-// the column sums.  Static functions: each of the two units has its own copy.
+// the column sums, the launch of the plain scan's tile kernel and the copy-back of a scan's outputs.  What the marginal screen's
+// entries need as well lies beneath, in aq_screen_host.h.  Static functions: each of the two units has its own copy.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <cstdlib>
-#include <limits>
-#include <stdint.h>
-#include <string>
-#include <vector>
-#include "aq_prep.h"          // aq_prep, aq_time_launches; aq_internal.h: aq_fail, AQ_HIP, aq_need_device, aq_need_acc_layout, AqDev
-#include "aq_cis_kernels.h"   // aq_k_cis_*; aq_k_ms_traitstats, aq_k_ms_colstats; aq_cis_make_plan
+#include "aq_screen_host.h"   // aq_screen_*; aq_prep.h, aq_internal.h
+#include "aq_cis_kernels.h"   // aq_k_cis_*; aq_screen_tile.h: aq_k_ms_gather, aq_k_ms_colstats; aq_cis_make_plan
 
 // the device side of one call: what does not change with the permutation, the scan's outputs, and the buffers of one launch of
 // permutations
@@ -23,15 +18,8 @@ struct AqCisBuf {
   aq_cis_plan pl{};
   aq_cis_work wk;
   int64_t cap = 0;
+  int ncu = 0;                               // the CU count the plan was made for
 };
-
-// an environment variable that forces a plan field: 0 when it is not set, -1 when it is no number >= 1 (the planner's message)
-static int aq_cis_env(const char *name) {
-  const char *e = getenv(name);
-  if (!e) return 0;
-  const int v = atoi(e);
-  return v < 1 ? -1 : v;
-}
 
 template <typename T>
 static int aq_cis_upload(AqDev<T> *dst, const std::vector<T> &src) {
@@ -48,29 +36,21 @@ static int aq_cis_setup(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, co
                         const char *who, AqCisBuf *b) {
   const size_t p1 = (size_t)h->p_kept, q = (size_t)h->q, n = (size_t)h->n;
   std::vector<double> syy(q);
-  std::vector<int> mt(q);
+  std::vector<int> mt;
+  int masked = 0, ncu = 0;
   {
-    AqDev<double> dsyy;
+    AqDev<double> dsyy;                      // by the trait's own index: the buffers of the call hold the ordered ones
     AqDev<int> dmt;
-    AQ_TRY(dsyy.alloc(q));
-    AQ_TRY(dmt.alloc(q));
-    hipLaunchKernelGGL(aq_k_ms_traitstats, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, h->Yc.get(), h->n, h->q, dsyy.get(),
-                       dmt.get());
-    AQ_HIP(hipGetLastError());
+    AQ_TRY(aq_screen_trait_stats(h, &dsyy, &dmt, &mt, &masked, &ncu));
     AQ_HIP(hipMemcpy(syy.data(), dsyy.get(), q * sizeof(double), hipMemcpyDeviceToHost));
-    AQ_HIP(hipMemcpy(mt.data(), dmt.get(), q * sizeof(int), hipMemcpyDeviceToHost));
   }
-  int masked = 0;
-  for (size_t t = 0; t < q; t++) masked |= mt[t] < h->n;
-  int ncu = 0;
-  AQ_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
   std::string err;
-  const int rc = aq_cis_make_plan(h->n, h->p_kept, h->q, masked, ncu > 0 ? ncu : 256, s_lo, s_hi, n_perm,
-                                  n_perm > 0 ? aq_cis_env("AQ_CIS_PB") : 0, n_perm > 0 ? aq_cis_env("AQ_CIS_BATCH") : 0, who, &b->pl, &b->wk,
-                                  &err);
+  const int rc = aq_cis_make_plan(h->n, h->p_kept, h->q, masked, ncu, s_lo, s_hi, n_perm, n_perm > 0 ? aq_screen_env("AQ_CIS_PB") : 0,
+                                  n_perm > 0 ? aq_screen_env("AQ_CIS_BATCH") : 0, who, &b->pl, &b->wk, &err);
   if (rc != AQ_OK) return aq_fail(rc, err);
   const size_t qa = (size_t)b->wk.q_active, W = (size_t)b->pl.n_items;
   b->cap = cap;
+  b->ncu = ncu;
   {
     std::vector<double> syy_o(qa), cut_o(qa);
     std::vector<int32_t> lo_o(qa), hi_o(qa);
@@ -129,6 +109,39 @@ static aq_cis_args aq_cis_common_args(aq_prep *h, AqCisBuf &b) {
   a.sx = b.sx.get(); a.sxx = b.sxx.get(); a.syy = b.syy.get(); a.cut = b.cut.get(); a.mt = b.mt.get();
   a.lo = b.lo.get(); a.hi = b.hi.get(); a.orig = b.order.get();
   return a;
+}
+
+// the arguments of a scan over the ordered traits in b.Yo: the common ones and the scan's outputs
+static aq_cis_args aq_cis_scan_args(aq_prep *h, AqCisBuf &b) {
+  aq_cis_args a = aq_cis_common_args(h, b);
+  a.Yo = b.Yo.get();
+  a.nb = 1;
+  a.snp = b.snp.get(); a.trait = b.trait.get(); a.r = b.r.get(); a.cap = (long long)b.cap;
+  a.n_pairs = b.counter.get(); a.n_undef = b.undef.get();
+  a.part_r = b.part_r.get(); a.part_s = b.part_s.get();
+  return a;
+}
+
+// the plain scan's tile kernel over the W work items (the conditional scan runs it where no trait has a list)
+template <bool MASKED>
+static void aq_cis_launch_tile(unsigned W, const aq_cis_args &a) {
+  aq_screen_a16(a.n, [&](auto a16) { hipLaunchKernelGGL((aq_k_cis_tile<MASKED, decltype(a16)::value>), dim3(W), dim3(256), 0, 0, a); });
+}
+
+// what every scan returns, after its kernels: the number of selected pairs and their table, each trait's best predictor and
+// its undefined pairs
+static int aq_cis_copy_scan(aq_prep *h, AqCisBuf &b, int32_t *snp, int32_t *trait, double *r, int64_t *n_pairs, int32_t *best_snp,
+                            double *best_r, int64_t *n_undef) {
+  const size_t q = (size_t)h->q;
+  unsigned long long cnt = 0;
+  AQ_HIP(hipMemcpy(&cnt, b.counter.get(), sizeof(cnt), hipMemcpyDeviceToHost));
+  if (n_pairs) *n_pairs = (int64_t)cnt;
+  AQ_TRY(aq_screen_copy_pairs(cnt, b.cap, b.snp, b.trait, b.r, snp, trait, r));
+  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
+  if (best_snp) AQ_HIP(hipMemcpy(best_snp, b.best_s.get(), q * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (best_r) AQ_HIP(hipMemcpy(best_r, b.best_r.get(), q * sizeof(double), hipMemcpyDeviceToHost));
+  if (n_undef) AQ_HIP(hipMemcpy(n_undef, b.undef.get(), q * sizeof(int64_t), hipMemcpyDeviceToHost));
+  return AQ_OK;
 }
 
 // Sx and Sxx of every column for the complete instances.  Asynchronous.

@@ -27,19 +27,17 @@
 // the 1 + KC trait-side panels unchanged.  A trait with k_t = 0, or with k_eff = 0, is a plain copy of y: no arithmetic on y,
 // and S~yy_t is the Syy_t of aq_k_ms_traitstats that the plain scan uses, so that its r is the plain scan's to the bit.
 //
-// aq_k_cc_tile<KC, A16>, KC in {1, 2, 4}, grid W, 256 threads, over the work items of aq_cis_plan.h.  The loop is that of
-// aq_k_cis_tile<false, A16> with 1 + KC trait-side LDS panels (rows of AQ_MSCREEN_STR doubles: the bank argument of
-// aq_mscreen_kernels.h holds for each) and 1 + KC accumulator sets fed from the same x[jj] registers: acc_y += Y~ X and
-// acc_j += Q_j X, 1 + KC streams of f64 matrix instructions from one operand read of X.  tile_k[k] is the largest k_eff of
-// trait tile k: a workgroup neither loads, stages nor multiplies a basis panel j >= tile_k (all zeros), which is uniform over
-// the workgroup and leaves its accumulators at 0.0, the value the products of zeros would have given.  32 accumulator
-// registers per set, 160 at KC = 4; LDS (2 + KC) 64 18 8 bytes plus the per-trait arrays (aq_ciscond_lds_bytes).
-// The epilogue is that of aq_k_cis_tile with Vx as above, the squares added in the order j = 1 ... KC: the selected-pair table
-// through one 64-bit counter, per-trait undefined counts, the item's best predictor per trait with ties to the lowest index;
-// aq_k_cis_best then reduces over a tile's items.
+// aq_k_cc_tile<KC, A16>, KC in {1, 2, 4}, grid W, 256 threads, over the work items of aq_cis_plan.h: the loop of aq_screen_tile.h
+// with 1 + KC trait-side panels, the residual traits of Yo and the KC basis panels of Qo, and as many accumulator sets fed
+// from the same operand read of X: acc_0 += Y~ X and acc_j += Q_j X.  tile_k[k] is the largest k_eff of trait tile k: a
+// workgroup neither loads, stages nor multiplies a basis panel j >= tile_k (all zeros), which is uniform over the workgroup
+// and leaves its accumulators at 0.0, the value the products of zeros would have given.  32 accumulator registers per set,
+// 160 at KC = 4; LDS (2 + KC) 64 18 8 bytes plus the per-trait arrays (aq_ciscond_lds_bytes).
+// The epilogue is aq_cis_scan_epilogue of aq_cis_kernels.h with `lost` = a_1^2 + ... + a_KC^2 handed to aq_ms_pair, its
+// roundings spelled out in the kernel; aq_k_cis_best then reduces over a tile's items.
 #pragma once
 #include "aq_ciscond_plan.h"
-#include "aq_cis_kernels.h"       // aq_cis_args; aq_mscreen_kernels.h: aq_ms_d4, AqMsShape, aq_ms_load, aq_ms_store; aq_block_sum
+#include "aq_cis_kernels.h"       // aq_cis_args, AqCisWin, aq_cis_scan_epilogue; aq_screen_tile.h
 
 struct aq_cc_args {
   aq_cis_args c;                  // Yo: the residual traits; syy: S~yy_t; mt is not read (complete Y: m_t = n)
@@ -131,179 +129,49 @@ __global__ __launch_bounds__(256, 2) void aq_k_cc_tile(const aq_cc_args ca) {
   static_assert(aq_ciscond_instance(KC), "an instance of the plan");
   constexpr int T = AQ_CIS_TILE;
   typedef AqMsShape<T> SH;
-  constexpr int NI = SH::NI;
-  constexpr int PAN = T * SH::STR;                         // doubles of a panel
-  __shared__ __attribute__((aligned(16))) double PX[PAN];
-  __shared__ __attribute__((aligned(16))) double PT[(1 + KC) * PAN];   // the residual traits, then the KC basis panels
+  __shared__ __attribute__((aligned(16))) double PX[SH::PAN];
+  __shared__ __attribute__((aligned(16))) double PT[(1 + KC) * SH::PAN];   // the residual traits, then the KC basis panels
   __shared__ double cand_r[2][T];
   __shared__ int cand_s[2][T];
-  __shared__ double ts_syy[T], ts_cut[T];                  // S~yy_t and the cutoff; not testable and an empty window for a trait >= qa
-  __shared__ int ts_ok[T], ts_lo[T], ts_hi[T], ts_orig[T];
-  static_assert(sizeof(double) * ((2 + KC) * PAN) + 2 * T * 12 + T * 32 == aq_ciscond_lds_bytes(KC), "plan and kernel");
-  static_assert(aq_ciscond_lds_bytes(KC) <= 65536, "64 KB of static LDS");
+  __shared__ double ts_syy[T], ts_cut[T];                  // S~yy_t and the cutoff; not testable for a trait >= qa
+  __shared__ int ts_ok[T];
+  __shared__ AqCisWin win;
+  static_assert(sizeof(double) * ((2 + KC) * SH::PAN) + 2 * T * 12 + T * 32 == aq_ciscond_lds_bytes(KC), "plan and kernel");
+  static_assert(sizeof(AqCisWin) == T * 12 && aq_ciscond_lds_bytes(KC) <= 65536, "64 KB of static LDS");
   const aq_cis_args &a = ca.c;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, l = lane & 15;
-  const int wr = w >> 1, wc = w & 1;
+  const AqMsLane ln;
   const int p0 = a.item_p0[blockIdx.x], kt = a.item_tile[blockIdx.x], q0 = T * kt;
   const int nq = ca.tile_k[kt];                            // basis panels of this trait tile that hold anything: <= KC
   const int n = a.n;
   const size_t qpanel = (size_t)a.qa * (size_t)n;
-  aq_ms_d4 axy[NI][NI], aq[KC][NI][NI];
-#pragma unroll
-  for (int i = 0; i < NI; i++)
-#pragma unroll
-    for (int jj = 0; jj < NI; jj++) {
-      axy[i][jj] = aq_ms_d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int c = 0; c < KC; c++) aq[c][i][jj] = aq_ms_d4{0.0, 0.0, 0.0, 0.0};
-    }
-  const int toff = (wr * SH::WT + l) * SH::STR + g;        // the lane's first operand within a trait-side panel
-  const double *px = PX + (wc * SH::WT + l) * SH::STR + g;
-  if ((int)threadIdx.x < T) {                      // read after the loop's barriers
+  if ((int)threadIdx.x < T) {
+    aq_ms_trait_fill(ts_syy, a.syy, q0, a.qa);
+    aq_ms_trait_fill(ts_cut, a.cut, q0, a.qa);
+    win.fill(a, q0);
     const int j = q0 + (int)threadIdx.x;
-    const bool tv = j < a.qa;
-    const double st = tv ? a.syy[j] : 0.0;
-    ts_syy[threadIdx.x] = st;
-    ts_cut[threadIdx.x] = tv ? a.cut[j] : 0.0;
-    ts_ok[threadIdx.x] = tv && n - 2 - a.n_cov - ca.keff[j] >= 1 && st > 1e-10 * ca.syy0[j];
-    ts_lo[threadIdx.x] = tv ? a.lo[j] : 0;
-    ts_hi[threadIdx.x] = tv ? a.hi[j] : 0;
-    ts_orig[threadIdx.x] = tv ? a.orig[j] : 0;
+    ts_ok[threadIdx.x] = j < a.qa && n - 2 - a.n_cov - ca.keff[j] >= 1 && a.syy[j] > 1e-10 * ca.syy0[j];
   }
-  double2 vx[SH::NV], vt[1 + KC][SH::NV];
-  aq_ms_load<T, A16>(a.Xs, n, a.p1, p0, 0, vx);
-  aq_ms_load<T, A16>(a.Yo, n, a.qa, q0, 0, vt[0]);
-#pragma unroll
-  for (int c = 0; c < KC; c++)
-    if (c < nq) aq_ms_load<T, A16>(ca.Qo + (size_t)c * qpanel, n, a.qa, q0, 0, vt[1 + c]);
-  for (int i0 = 0; i0 < n; i0 += AQ_MSCREEN_NC) {
-    __syncthreads();                             // the panels of the previous chunk have been read
-    aq_ms_store<T>(vx, PX);
-    aq_ms_store<T>(vt[0], PT);
-#pragma unroll
-    for (int c = 0; c < KC; c++)
-      if (c < nq) aq_ms_store<T>(vt[1 + c], PT + (1 + c) * PAN);
-    __syncthreads();
-    if (i0 + AQ_MSCREEN_NC < n) {
-      aq_ms_load<T, A16>(a.Xs, n, a.p1, p0, i0 + AQ_MSCREEN_NC, vx);
-      aq_ms_load<T, A16>(a.Yo, n, a.qa, q0, i0 + AQ_MSCREEN_NC, vt[0]);
-#pragma unroll
-      for (int c = 0; c < KC; c++)
-        if (c < nq) aq_ms_load<T, A16>(ca.Qo + (size_t)c * qpanel, n, a.qa, q0, i0 + AQ_MSCREEN_NC, vt[1 + c]);
-    }
-#pragma unroll
-    for (int kk = 0; kk < AQ_MSCREEN_NC; kk += 4) {
-      double x[NI], y[NI];
-#pragma unroll
-      for (int i = 0; i < NI; i++) {
-        x[i] = px[16 * i * SH::STR + kk];
-        y[i] = PT[toff + 16 * i * SH::STR + kk];
-      }
-#pragma unroll
-      for (int i = 0; i < NI; i++)
-#pragma unroll
-        for (int jj = 0; jj < NI; jj++) axy[i][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(y[i], x[jj], axy[i][jj], 0, 0, 0);
-#pragma unroll
-      for (int c = 0; c < KC; c++)
-        if (c < nq) {
-          double qv[NI];
-#pragma unroll
-          for (int i = 0; i < NI; i++) qv[i] = PT[(1 + c) * PAN + toff + 16 * i * SH::STR + kk];
-#pragma unroll
-          for (int i = 0; i < NI; i++)
-#pragma unroll
-            for (int jj = 0; jj < NI; jj++) aq[c][i][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(qv[i], x[jj], aq[c][i][jj], 0, 0, 0);
-        }
-    }
-  }
-
-  // ---- epilogue: r of the wave's 32 x 32 pairs, four traits (g + 4 reg) x one predictor (l) per accumulator and lane ----
+  aq_ms_acc<T, 1 + KC> acc;                                // [0]: x_s' y~_t; [j]: a_j = q_tj' x_s
+  aq_ms_acc_m<T, false, 1 + KC> unused_x, unused_xx;
+  // GUARD = 1: the residual traits (panel 0) are always live, the basis panels k >= 1 are tested against 1 + nq
+  aq_ms_tile_loop<T, false, A16, 1 + KC, 1, AQ_MS_STEP_PLAIN>(a.Xs, n, a.p1, p0, a.qa, q0, 1 + nq,
+                                               [&](int k) { return k == 0 ? a.Yo : ca.Qo + (size_t)(k - 1) * qpanel; }, PX, PT, acc,
+                                               unused_x, unused_xx);
   const double nd = (double)n;
-  double csx[NI], csxx[NI];                        // Sx and Sxx of the lane's predictors
+  double csx[SH::NI], csxx[SH::NI];
+  aq_ms_col_sums<SH::NI, true>(a.sx, a.sxx, p0 + ln.wc * SH::WT + ln.l, a.p1, csx, csxx);
+  const auto trait = [&](int tl) { return AqCisTrait{ts_ok[tl] != 0, ts_syy[tl], nd}; };
+  aq_cis_scan_epilogue(a, p0, q0, ts_cut, win, cand_r, cand_s, trait, [&](int i, int jj, int reg, const AqCisTrait &tr, double *r) {
+    // The variance of x_s that the conditioning takes, a_1^2 + ... + a_KC^2.  Which product of a sum of products the compiler
+    // folds into a fused multiply-add is its choice and moves the last bit of r, so the choice is spelled out here: a_2^2 is
+    // rounded, a_1^2 is folded onto it, then a_3^2 and a_4^2 in this order (what the first build of this kernel computed).
+    // Not pinned: at KC = 1 `lost` is one product, and whether Vx0 - a_1^2 inside aq_ms_pair becomes one fused operation is
+    // still the compiler's choice (HIP's default contraction); the other kernels pass 0.0 and have nothing to contract.
+    constexpr int C2 = KC > 1 ? 2 : 1;
+    const double a1 = acc[1][i][jj][reg], a2 = acc[C2][i][jj][reg];
+    double lost = KC > 1 ? __builtin_fma(a1, a1, a2 * a2) : a1 * a1;
 #pragma unroll
-  for (int jj = 0; jj < NI; jj++) {
-    const int s = p0 + wc * SH::WT + 16 * jj + l;
-    csx[jj] = s < a.p1 ? a.sx[s] : 0.0;
-    csxx[jj] = s < a.p1 ? a.sxx[s] : 0.0;
-  }
-#pragma unroll
-  for (int i = 0; i < NI; i++)
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) {
-      const int tl = wr * SH::WT + 16 * i + g + 4 * reg;
-      const double syy = ts_syy[tl], cut = ts_cut[tl];
-      const int lo = ts_lo[tl], hi = ts_hi[tl], t = ts_orig[tl];
-      const bool t_ok = ts_ok[tl] != 0;
-      double br2 = -1.0, br = __builtin_nan("");
-      int bs = 0x7fffffff;
-      unsigned int undef = 0;
-#pragma unroll
-      for (int jj = 0; jj < NI; jj++) {
-        const int s = p0 + wc * SH::WT + 16 * jj + l;
-        if (s >= lo && s < hi) {                   // hi <= p1, and lo = hi = 0 for a trait >= qa: the pair exists
-          double r = __builtin_nan("");
-          bool ok = false;
-          if (t_ok) {
-            const double sxy = axy[i][jj][reg];
-            double lost = 0.0;                     // the variance of x_s that the conditioning takes
-#pragma unroll
-            for (int c = 0; c < KC; c++) lost += aq[c][i][jj][reg] * aq[c][i][jj][reg];
-            const double sxx = csxx[jj];
-            const double vx0 = sxx - csx[jj] * csx[jj] / nd;
-            const double vx = vx0 - lost;
-            ok = vx > 1e-10 * sxx;
-            if (ok) r = sxy / sqrt(vx * syy);
-          }
-          if (ok) {
-            const double r2 = r * r;
-            if (r2 >= cut) {
-              const unsigned long long slot = atomicAdd(a.n_pairs, 1ull);
-              if ((long long)slot < a.cap) {
-                a.snp[slot] = s;
-                a.trait[slot] = t;
-                a.r[slot] = r;
-              }
-            }
-            if (r2 > br2) {                        // ascending s: the first of equal r^2 stays
-              br2 = r2;
-              br = r;
-              bs = s;
-            }
-          } else {
-            undef++;
-          }
-        }
-      }
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) {     // across the sixteen predictors of the lane group
-        const double o2 = __shfl_xor(br2, off), orr = __shfl_xor(br, off);
-        const int os = __shfl_xor(bs, off);
-        undef += __shfl_xor(undef, off);
-        if (o2 > br2 || (o2 == br2 && os < bs)) {
-          br2 = o2;
-          br = orr;
-          bs = os;
-        }
-      }
-      if (l == 0) {
-        cand_r[wc][tl] = br;
-        cand_s[wc][tl] = bs;
-        if (undef > 0) atomicAdd(a.n_undef + t, (unsigned long long)undef);   // undef > 0: a pair exists, so the trait is one < qa
-      }
-    }
-  __syncthreads();
-  if ((int)threadIdx.x < T && q0 + (int)threadIdx.x < a.qa) {   // the two waves of a tile row: the lower predictors win a tie
-    const int tl = threadIdx.x;
-    double r = cand_r[0][tl];
-    int s = cand_s[0][tl];
-    const double r1 = cand_r[1][tl];
-    const int s1 = cand_s[1][tl];
-    if (s1 != 0x7fffffff && (s == 0x7fffffff || r1 * r1 > r * r)) {
-      r = r1;
-      s = s1;
-    }
-    const size_t o = (size_t)blockIdx.x * (size_t)T + (size_t)tl;
-    a.part_r[o] = r;
-    a.part_s[o] = s == 0x7fffffff ? -1 : s;
-  }
+    for (int c = 3; c <= KC; c++) lost = __builtin_fma(acc[c][i][jj][reg], acc[c][i][jj][reg], lost);
+    return aq_ms_pair(acc[0][i][jj][reg], csx[jj], csxx[jj], tr.m, tr.syy, lost, r);
+  });
 }

@@ -14,7 +14,7 @@
 #include "../../include/atlasqtl_hip.h"
 
 #define AQ_MSCREEN_NC 16            // samples staged in LDS per step
-#define AQ_MSCREEN_STR 18           // doubles per LDS row: AQ_MSCREEN_NC + 2 (aq_mscreen_kernels.h has the bank argument)
+#define AQ_MSCREEN_STR 18           // doubles per LDS row: AQ_MSCREEN_NC + 2 (aq_screen_tile.h has the bank argument)
 #define AQ_MSCREEN_TILE_MASKED 64   // three accumulator sets: 96 of the 512 registers of a lane; 128 x 128 would need 384
 
 #if defined(__HIPCC__)

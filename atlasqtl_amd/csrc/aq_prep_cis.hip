@@ -4,15 +4,8 @@
 // same statistic on permuted responses and returns each trait's largest in-window r^2 per permutation; aq_prep_cis_time times
 // the kernels alone, aq_cis_plan_query runs the planner on the host.  The kernels are plain HIP that issues no hand-written
 // load: the ISA proof of the look-ahead sweep units does not cover them and need not.
-#include <hip/hip_runtime.h>
-#include <cmath>
-#include <cstdlib>
-#include <limits>
-#include <stdint.h>
-#include <string>
-#include <vector>
-#include "aq_cis_host.h"      // AqCisBuf, aq_cis_setup, aq_cis_common_args, aq_cis_colstats, aq_cis_need_windows; aq_prep.h,
-                              // aq_cis_kernels.h
+#include "aq_cis_host.h"      // AqCisBuf, aq_cis_setup, aq_cis_*_args, aq_cis_colstats, aq_cis_launch_tile, aq_cis_copy_scan,
+                              // aq_cis_need_windows; aq_screen_host.h, aq_prep.h, aq_cis_kernels.h
 #include "aq_msperm_plan.h"   // aq_msperm_check_rows (the plan header alone: aq_msperm_kernels.h defines a non-static kernel)
 
 extern "C" int aq_cis_plan_query(int32_t n, int32_t p1, int32_t q, int32_t masked, int32_t ncu, const int32_t *s_lo, const int32_t *s_hi,
@@ -33,26 +26,13 @@ static int aq_cis_launch_scan(aq_prep *h, AqCisBuf &b) {
   AQ_HIP(hipMemsetAsync(b.undef.get(), 0, (size_t)q * sizeof(unsigned long long), 0));
   AQ_TRY(aq_cis_colstats(h, b));
   if (W > 0) {
-    hipLaunchKernelGGL(aq_k_cis_gather, dim3((unsigned)(qa < (1 << 20) ? qa : (1 << 20))), dim3(256), 0, 0, h->Yc.get(), b.order.get(),
-                       (const int32_t *)nullptr, h->n, qa, 1, b.Yo.get());
-    aq_cis_args a = aq_cis_common_args(h, b);
-    a.Yo = b.Yo.get();
-    a.nb = 1;
-    a.snp = b.snp.get(); a.trait = b.trait.get(); a.r = b.r.get(); a.cap = (long long)b.cap;
-    a.n_pairs = b.counter.get(); a.n_undef = b.undef.get();
-    a.part_r = b.part_r.get(); a.part_s = b.part_s.get();
-    const bool a16 = (h->n & 1) == 0;            // even n: every column starts at a multiple of 16 bytes
-    if (b.pl.masked) {
-      if (a16)
-        hipLaunchKernelGGL((aq_k_cis_tile<true, true>), dim3(W), dim3(256), 0, 0, a);
-      else
-        hipLaunchKernelGGL((aq_k_cis_tile<true, false>), dim3(W), dim3(256), 0, 0, a);
-    } else {
-      if (a16)
-        hipLaunchKernelGGL((aq_k_cis_tile<false, true>), dim3(W), dim3(256), 0, 0, a);
-      else
-        hipLaunchKernelGGL((aq_k_cis_tile<false, false>), dim3(W), dim3(256), 0, 0, a);
-    }
+    hipLaunchKernelGGL(aq_k_ms_gather, dim3((unsigned)(qa < (1 << 20) ? qa : (1 << 20))), dim3(256), 0, 0, h->Yc.get(),
+                       (const int32_t *)b.order.get(), (const int32_t *)nullptr, h->n, qa, 1, b.Yo.get());
+    const aq_cis_args a = aq_cis_scan_args(h, b);
+    if (b.pl.masked)
+      aq_cis_launch_tile<true>(W, a);
+    else
+      aq_cis_launch_tile<false>(W, a);
   }
   hipLaunchKernelGGL(aq_k_cis_best, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, b.part_r.get(), b.part_s.get(), b.first_item.get(),
                      b.order.get(), qa, q, b.best_s.get(), b.best_r.get());
@@ -61,11 +41,10 @@ static int aq_cis_launch_scan(aq_prep *h, AqCisBuf &b) {
 }
 
 template <bool MASKED, int PB>
-static void aq_cis_launch_perm_tile(bool a16, unsigned grid, const aq_cis_args &a) {
-  if (a16)
-    hipLaunchKernelGGL((aq_k_cis_perm_tile<MASKED, true, PB>), dim3(grid), dim3(256), 0, 0, a);
-  else
-    hipLaunchKernelGGL((aq_k_cis_perm_tile<MASKED, false, PB>), dim3(grid), dim3(256), 0, 0, a);
+static void aq_cis_launch_perm_tile(unsigned grid, const aq_cis_args &a) {
+  aq_screen_a16(a.n, [&](auto a16) {
+    hipLaunchKernelGGL((aq_k_cis_perm_tile<MASKED, decltype(a16)::value, PB>), dim3(grid), dim3(256), 0, 0, a);
+  });
 }
 
 // the kernels of one launch over the nb <= batch permutations whose rows lie in b.perm; Sx and Sxx have been formed.
@@ -76,25 +55,24 @@ static int aq_cis_launch_perm(aq_prep *h, AqCisBuf &b, int nb) {
   AQ_HIP(hipMemsetAsync(b.key.get(), 0, (size_t)nb * (size_t)q * sizeof(unsigned long long), 0));
   if (W > 0) {
     const long long cols = (long long)nb * (long long)qa;
-    hipLaunchKernelGGL(aq_k_cis_gather, dim3((unsigned)(cols < (1ll << 20) ? cols : (1ll << 20))), dim3(256), 0, 0, h->Yc.get(),
-                       b.order.get(), (const int32_t *)b.perm.get(), h->n, qa, nb, b.Yp.get());
+    hipLaunchKernelGGL(aq_k_ms_gather, dim3((unsigned)(cols < (1ll << 20) ? cols : (1ll << 20))), dim3(256), 0, 0, h->Yc.get(),
+                       (const int32_t *)b.order.get(), (const int32_t *)b.perm.get(), h->n, qa, nb, b.Yp.get());
     aq_cis_args a = aq_cis_common_args(h, b);
     a.Yo = b.Yp.get();
     a.nb = nb;
     a.key = b.key.get();
-    const bool a16 = (h->n & 1) == 0;
     const unsigned grid = (unsigned)(W * ((nb + pb - 1) / pb));   // < 2^31: the plan
     if (b.pl.masked) {
       if (pb == 2)
-        aq_cis_launch_perm_tile<true, 2>(a16, grid, a);
+        aq_cis_launch_perm_tile<true, 2>(grid, a);
       else
-        aq_cis_launch_perm_tile<true, 1>(a16, grid, a);
+        aq_cis_launch_perm_tile<true, 1>(grid, a);
     } else if (pb == 4) {
-      aq_cis_launch_perm_tile<false, 4>(a16, grid, a);
+      aq_cis_launch_perm_tile<false, 4>(grid, a);
     } else if (pb == 2) {
-      aq_cis_launch_perm_tile<false, 2>(a16, grid, a);
+      aq_cis_launch_perm_tile<false, 2>(grid, a);
     } else {
-      aq_cis_launch_perm_tile<false, 1>(a16, grid, a);
+      aq_cis_launch_perm_tile<false, 1>(grid, a);
     }
   }
   const long long count = (long long)nb * (long long)q;
@@ -111,29 +89,14 @@ extern "C" int aq_prep_cis(aq_prep_handle h, const int32_t *s_lo, const int32_t 
   if (cap < 0) return aq_fail(AQ_ERR_ARG, "aq_prep_cis: cap >= 0 required, " + std::to_string(cap) + " given");
   if (!h) return aq_fail(AQ_ERR_ARG, "aq_prep_cis: NULL handle");
   AQ_TRY(aq_cis_need_windows(h, s_lo, s_hi, "aq_prep_cis"));
-  for (int t = 0; t < h->q; t++)
-    if (std::isnan(r2_cut[t])) return aq_fail(AQ_ERR_ARG, "aq_prep_cis: r2_cut[" + std::to_string(t) + "] is NaN");
+  AQ_TRY(aq_screen_need_cut(r2_cut, h->q, "aq_prep_cis"));
   AQ_TRY(aq_need_device(h->device));
   AQ_TRY(aq_need_acc_layout("aq_prep_cis"));
-  const size_t q = (size_t)h->q;
   AqCisBuf b;
   AQ_TRY(aq_cis_setup(h, s_lo, s_hi, r2_cut, cap, true, 0, "aq_prep_cis", &b));
   if (plan_out) *plan_out = b.pl;
   AQ_TRY(aq_cis_launch_scan(h, b));
-  unsigned long long cnt = 0;
-  AQ_HIP(hipMemcpy(&cnt, b.counter.get(), sizeof(cnt), hipMemcpyDeviceToHost));
-  if (n_pairs) *n_pairs = (int64_t)cnt;
-  const size_t rows = cnt < (unsigned long long)cap ? (size_t)cnt : (size_t)cap;
-  if (rows > 0) {
-    if (snp) AQ_HIP(hipMemcpy(snp, b.snp.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (trait) AQ_HIP(hipMemcpy(trait, b.trait.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (r) AQ_HIP(hipMemcpy(r, b.r.get(), rows * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
-  if (best_snp) AQ_HIP(hipMemcpy(best_snp, b.best_s.get(), q * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (best_r) AQ_HIP(hipMemcpy(best_r, b.best_r.get(), q * sizeof(double), hipMemcpyDeviceToHost));
-  if (n_undef) AQ_HIP(hipMemcpy(n_undef, b.undef.get(), q * sizeof(int64_t), hipMemcpyDeviceToHost));
-  return AQ_OK;
+  return aq_cis_copy_scan(h, b, snp, trait, r, n_pairs, best_snp, best_r, n_undef);
 }
 
 extern "C" int aq_prep_cis_perm(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, int32_t n_perm, const int32_t *perm,
@@ -163,9 +126,9 @@ extern "C" int aq_prep_cis_perm(aq_prep_handle h, const int32_t *s_lo, const int
   return AQ_OK;
 }
 
-// Timing hook: the scan's kernels `reps` times between two events, counting only (cap = 0), with the cutoff t^2 = 40 of
-// aq_prep_marginal_time, r2_cut = 40 / (40 + df_t), +inf where df_t < 1; then, with n_perm >= 1, the gather, tile and reduce
-// kernels of n_perm permutations launch by launch, on one batch of rows generated as in aq_prep_marginal_perm_time.
+// Timing hook: the scan's kernels `reps` times between two events, counting only (cap = 0), with the cutoff of
+// aq_prep_marginal_time (aq_screen_time_cut); then, with n_perm >= 1, the gather, tile and reduce kernels of n_perm
+// permutations launch by launch, on one batch of the rows of aq_prep_marginal_perm_time (aq_screen_time_perms).
 extern "C" int aq_prep_cis_time(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, int32_t n_perm, int32_t reps, double *ms_scan,
                                 double *ms_per_perm, aq_cis_plan *plan_out) {
   if (!s_lo || !s_hi || !ms_scan || !ms_per_perm) return aq_fail(AQ_ERR_ARG, "aq_prep_cis_time: NULL argument");
@@ -181,29 +144,13 @@ extern "C" int aq_prep_cis_time(aq_prep_handle h, const int32_t *s_lo, const int
   {
     const size_t qa = (size_t)b.wk.q_active;
     std::vector<double> cut(qa);
-    for (size_t j = 0; j < qa; j++) {
-      const int df = b.mt_host[j] - 2 - h->n_cov;
-      cut[j] = df >= 1 ? 40.0 / (40.0 + (double)df) : std::numeric_limits<double>::infinity();
-    }
+    for (size_t j = 0; j < qa; j++) cut[j] = aq_screen_time_cut(b.mt_host[j] - 2 - h->n_cov);
     if (qa > 0) AQ_HIP(hipMemcpy(b.cut.get(), cut.data(), qa * sizeof(double), hipMemcpyHostToDevice));
   }
   AQ_TRY(aq_time_launches(reps, ms_scan, [&] { return aq_cis_launch_scan(h, b); }));
   *ms_per_perm = 0.0;
   if (n_perm > 0) {
-    const size_t rows = (size_t)b.pl.batch;
-    std::vector<int32_t> perm(rows * n);
-    uint64_t state = 0x9e3779b97f4a7c15ull;
-    for (size_t r = 0; r < rows; r++) {
-      int32_t *row = perm.data() + r * n;
-      for (size_t i = 0; i < n; i++) row[i] = (int32_t)i;
-      for (size_t i = n; i > 1; i--) {
-        state = state * 6364136223846793005ull + 1442695040888963407ull;
-        const size_t j = (size_t)((state >> 33) % i);
-        const int32_t tmp = row[i - 1];
-        row[i - 1] = row[j];
-        row[j] = tmp;
-      }
-    }
+    const std::vector<int32_t> perm = aq_screen_time_perms((size_t)b.pl.batch, n);
     AQ_HIP(hipMemcpy(b.perm.get(), perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     double ms = 0.0;
     AQ_TRY(aq_time_launches(reps, &ms, [&] {

@@ -3,13 +3,8 @@
 // out of both (aq_ciscond_kernels.h; plan by aq_ciscond_plan.h on top of aq_cis_plan.h) and returns what aq_prep_cis returns,
 // and k_eff; aq_prep_cis_cond_time times the kernels alone, aq_ciscond_plan_query runs the planner on the host.  The kernels
 // are plain HIP that issues no hand-written load: the ISA proof of the look-ahead sweep units does not cover them and need not.
-#include <hip/hip_runtime.h>
-#include <cmath>
-#include <limits>
-#include <stdint.h>
-#include <string>
-#include <vector>
-#include "aq_cis_host.h"          // AqCisBuf, aq_cis_setup, aq_cis_common_args, aq_cis_colstats, aq_cis_need_windows
+#include "aq_cis_host.h"          // AqCisBuf, aq_cis_setup, aq_cis_scan_args, aq_cis_colstats, aq_cis_launch_tile, aq_cis_copy_scan,
+                                  // aq_cis_need_windows; aq_screen_host.h
 #include "aq_ciscond_kernels.h"   // aq_k_cc_basis, aq_k_cc_tile; aq_ciscond_make_plan, aq_ciscond_check_lists
 
 extern "C" int aq_ciscond_plan_query(int32_t n, int32_t p1, int32_t q, int32_t ncu, const int32_t *s_lo, const int32_t *s_hi,
@@ -49,11 +44,9 @@ static int aq_cc_setup(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, con
   AQ_TRY(aq_cis_setup(h, s_lo, s_hi, r2_cut, cap, true, 0, who, &b));
   if (b.pl.masked)
     return aq_fail(AQ_ERR_UNSUPPORTED, std::string(who) + ": Y has missing values; the conditional scan takes complete Y only");
-  int ncu = 0;
-  AQ_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
   std::string err;
   // the cis plan inside is the same pure function of the same arguments as b.pl, and its order and work list are b.wk
-  const int rc = aq_ciscond_make_plan(h->n, h->p_kept, h->q, ncu > 0 ? ncu : 256, s_lo, s_hi, cond_ptr, cond_idx, who, &cb->pl, nullptr, &err);
+  const int rc = aq_ciscond_make_plan(h->n, h->p_kept, h->q, b.ncu, s_lo, s_hi, cond_ptr, cond_idx, who, &cb->pl, nullptr, &err);
   if (rc != AQ_OK) return aq_fail(rc, err);
   const size_t qa = (size_t)b.wk.q_active, n = (size_t)h->n, q = (size_t)h->q;
   const int kc = cb->pl.kc;
@@ -101,11 +94,8 @@ static int aq_cc_tile_k(AqCcBuf &cb) {
 }
 
 template <int KC>
-static void aq_cc_launch_tile(bool a16, unsigned grid, const aq_cc_args &a) {
-  if (a16)
-    hipLaunchKernelGGL((aq_k_cc_tile<KC, true>), dim3(grid), dim3(256), 0, 0, a);
-  else
-    hipLaunchKernelGGL((aq_k_cc_tile<KC, false>), dim3(grid), dim3(256), 0, 0, a);
+static void aq_cc_launch_tile(unsigned grid, const aq_cc_args &ca) {
+  aq_screen_a16(ca.c.n, [&](auto a16) { hipLaunchKernelGGL((aq_k_cc_tile<KC, decltype(a16)::value>), dim3(grid), dim3(256), 0, 0, ca); });
 }
 
 // the kernels of one scan after the basis: the column sums, the tile kernel of the plan's KC (the plain scan's for KC = 0,
@@ -119,25 +109,13 @@ static int aq_cc_launch_scan(aq_prep *h, AqCcBuf &cb) {
   AQ_TRY(aq_cis_colstats(h, b));
   if (W > 0) {
     aq_cc_args ca{};
-    ca.c = aq_cis_common_args(h, b);
-    aq_cis_args &a = ca.c;
-    a.Yo = b.Yo.get();
-    a.nb = 1;
-    a.snp = b.snp.get(); a.trait = b.trait.get(); a.r = b.r.get(); a.cap = (long long)b.cap;
-    a.n_pairs = b.counter.get(); a.n_undef = b.undef.get();
-    a.part_r = b.part_r.get(); a.part_s = b.part_s.get();
+    ca.c = aq_cis_scan_args(h, b);
     ca.Qo = cb.Qo.get(); ca.syy0 = cb.syy0.get(); ca.keff = cb.keff_o.get(); ca.tile_k = cb.tile_k.get();
-    const bool a16 = (h->n & 1) == 0;            // even n: every column starts at a multiple of 16 bytes
     switch (cb.pl.kc) {
-      case 0:                                    // no list: S~yy = Syy and k_eff = 0 everywhere, the plain scan's kernel
-        if (a16)
-          hipLaunchKernelGGL((aq_k_cis_tile<false, true>), dim3(W), dim3(256), 0, 0, a);
-        else
-          hipLaunchKernelGGL((aq_k_cis_tile<false, false>), dim3(W), dim3(256), 0, 0, a);
-        break;
-      case 1: aq_cc_launch_tile<1>(a16, W, ca); break;
-      case 2: aq_cc_launch_tile<2>(a16, W, ca); break;
-      default: aq_cc_launch_tile<4>(a16, W, ca); break;
+      case 0: aq_cis_launch_tile<false>(W, ca.c); break;   // no list: S~yy = Syy and k_eff = 0 everywhere, the plain scan's kernel
+      case 1: aq_cc_launch_tile<1>(W, ca); break;
+      case 2: aq_cc_launch_tile<2>(W, ca); break;
+      default: aq_cc_launch_tile<4>(W, ca); break;
     }
   }
   hipLaunchKernelGGL(aq_k_cis_best, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, b.part_r.get(), b.part_s.get(), b.first_item.get(),
@@ -152,8 +130,7 @@ extern "C" int aq_prep_cis_cond(aq_prep_handle h, const int32_t *s_lo, const int
   if (!r2_cut) return aq_fail(AQ_ERR_ARG, "aq_prep_cis_cond: NULL r2_cut");
   if (cap < 0) return aq_fail(AQ_ERR_ARG, "aq_prep_cis_cond: cap >= 0 required, " + std::to_string(cap) + " given");
   AQ_TRY(aq_cc_check(h, s_lo, s_hi, cond_ptr, cond_idx, "aq_prep_cis_cond"));
-  for (int t = 0; t < h->q; t++)
-    if (std::isnan(r2_cut[t])) return aq_fail(AQ_ERR_ARG, "aq_prep_cis_cond: r2_cut[" + std::to_string(t) + "] is NaN");
+  AQ_TRY(aq_screen_need_cut(r2_cut, h->q, "aq_prep_cis_cond"));
   AQ_TRY(aq_need_device(h->device));
   AQ_TRY(aq_need_acc_layout("aq_prep_cis_cond"));
   const size_t q = (size_t)h->q;
@@ -163,27 +140,14 @@ extern "C" int aq_prep_cis_cond(aq_prep_handle h, const int32_t *s_lo, const int
   AQ_TRY(aq_cc_launch_basis(h, cb));
   AQ_TRY(aq_cc_tile_k(cb));
   AQ_TRY(aq_cc_launch_scan(h, cb));
-  AqCisBuf &b = cb.b;
-  unsigned long long cnt = 0;
-  AQ_HIP(hipMemcpy(&cnt, b.counter.get(), sizeof(cnt), hipMemcpyDeviceToHost));
-  if (n_pairs) *n_pairs = (int64_t)cnt;
-  const size_t rows = cnt < (unsigned long long)cap ? (size_t)cnt : (size_t)cap;
-  if (rows > 0) {
-    if (snp) AQ_HIP(hipMemcpy(snp, b.snp.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (trait) AQ_HIP(hipMemcpy(trait, b.trait.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (r) AQ_HIP(hipMemcpy(r, b.r.get(), rows * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
-  if (best_snp) AQ_HIP(hipMemcpy(best_snp, b.best_s.get(), q * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (best_r) AQ_HIP(hipMemcpy(best_r, b.best_r.get(), q * sizeof(double), hipMemcpyDeviceToHost));
-  if (n_undef) AQ_HIP(hipMemcpy(n_undef, b.undef.get(), q * sizeof(int64_t), hipMemcpyDeviceToHost));
+  AQ_TRY(aq_cis_copy_scan(h, cb.b, snp, trait, r, n_pairs, best_snp, best_r, n_undef));
   if (k_eff) AQ_HIP(hipMemcpy(k_eff, cb.keff_t.get(), q * sizeof(int32_t), hipMemcpyDeviceToHost));
   return AQ_OK;
 }
 
 // Timing hook, after aq_prep_cis_time: the basis kernel `reps` times between two events, then the scan's kernels (column
-// sums, tile kernel of the plan's KC, reduction of the bests), counting only (cap = 0), with the cutoff t^2 = 40 at
-// df_t = n - 2 - n_cov - k_eff[t], r2_cut = 40 / (40 + df_t), +inf where df_t < 1.
+// sums, tile kernel of the plan's KC, reduction of the bests), counting only (cap = 0), with the cutoff aq_screen_time_cut at
+// df_t = n - 2 - n_cov - k_eff[t].
 extern "C" int aq_prep_cis_cond_time(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, const int32_t *cond_ptr,
                                      const int32_t *cond_idx, int32_t reps, double *ms_basis, double *ms_scan, aq_ciscond_plan *plan_out) {
   if (!ms_basis || !ms_scan) return aq_fail(AQ_ERR_ARG, "aq_prep_cis_cond_time: NULL argument");
@@ -202,10 +166,7 @@ extern "C" int aq_prep_cis_cond_time(aq_prep_handle h, const int32_t *s_lo, cons
     std::vector<int32_t> keff(qa);
     std::vector<double> cut(qa);
     if (qa > 0) AQ_HIP(hipMemcpy(keff.data(), cb.keff_o.get(), qa * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (size_t j = 0; j < qa; j++) {
-      const int df = h->n - 2 - h->n_cov - keff[j];
-      cut[j] = df >= 1 ? 40.0 / (40.0 + (double)df) : std::numeric_limits<double>::infinity();
-    }
+    for (size_t j = 0; j < qa; j++) cut[j] = aq_screen_time_cut(h->n - 2 - h->n_cov - keff[j]);
     if (qa > 0) AQ_HIP(hipMemcpy(b.cut.get(), cut.data(), qa * sizeof(double), hipMemcpyHostToDevice));
   }
   AQ_TRY(aq_time_launches(reps, ms_scan, [&] { return aq_cc_launch_scan(h, cb); }));

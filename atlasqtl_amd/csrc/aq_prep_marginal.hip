@@ -3,15 +3,8 @@
 // aq_mscreen_plan.h) and returns the selected pairs, the per-predictor counts and each trait's best predictor;
 // aq_prep_marginal_time times the kernels alone, aq_mscreen_plan_query runs the planner on the host.  The kernels are plain HIP
 // that issues no hand-written load: the ISA proof of the look-ahead sweep units does not cover them and need not.
-#include <hip/hip_runtime.h>
-#include <cmath>
-#include <cstdlib>
-#include <limits>
-#include <stdint.h>
-#include <string>
-#include <vector>
-#include "aq_prep.h"             // aq_prep, aq_time_launches; aq_internal.h: aq_fail, AQ_HIP, aq_need_device, aq_need_acc_layout, AqDev
-#include "aq_mscreen_kernels.h"  // aq_k_ms_traitstats, aq_k_ms_colstats, aq_k_ms_tile, aq_k_ms_best; aq_mscreen_make_plan
+#include "aq_screen_host.h"      // aq_screen_*; aq_prep.h, aq_internal.h; aq_screen_tile.h: aq_k_ms_traitstats, aq_k_ms_colstats
+#include "aq_mscreen_kernels.h"  // aq_k_ms_tile, aq_k_ms_best; aq_mscreen_make_plan
 
 extern "C" int aq_mscreen_plan_query(int32_t n, int32_t p1, int32_t q, int32_t masked, int32_t ncu, aq_mscreen_plan *out) {
   if (!out) return aq_fail(AQ_ERR_ARG, "aq_mscreen_plan_query: NULL argument");
@@ -27,6 +20,7 @@ struct AqMsBuf {
   AqDev<int> mt;
   AqDev<int32_t> part_s, best_s, snp, trait;
   AqDev<unsigned long long> counters, rs;    // counters: n_pairs, n_undefined
+  std::vector<int> mt_host;
   aq_mscreen_plan pl{};
   int64_t cap = 0;
   bool want_dense = false;
@@ -35,23 +29,10 @@ struct AqMsBuf {
 // Syy_t and m_t of the handle's traits, whether any value is missing, and from that the plan; then every buffer
 static int aq_ms_setup(aq_prep *h, int64_t cap, bool want_dense, const char *who, AqMsBuf *b) {
   const size_t p1 = (size_t)h->p_kept, q = (size_t)h->q;
-  AQ_TRY(b->syy.alloc(q));
-  AQ_TRY(b->mt.alloc(q));
-  hipLaunchKernelGGL(aq_k_ms_traitstats, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, h->Yc.get(), h->n, h->q, b->syy.get(),
-                     b->mt.get());
-  AQ_HIP(hipGetLastError());
-  std::vector<int> mt(q);
-  AQ_HIP(hipMemcpy(mt.data(), b->mt.get(), q * sizeof(int), hipMemcpyDeviceToHost));
-  int masked = 0;
-  for (size_t t = 0; t < q; t++) masked |= mt[t] < h->n;
-  int ncu = 0, force = 0;
-  AQ_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
-  if (const char *e = getenv("AQ_MSCREEN_TILE")) {
-    force = atoi(e);
-    if (force < 1) force = -1;               // not a number: the planner's message
-  }
+  int masked = 0, ncu = 0;
+  AQ_TRY(aq_screen_trait_stats(h, &b->syy, &b->mt, &b->mt_host, &masked, &ncu));
   std::string err;
-  const int rc = aq_mscreen_make_plan(h->n, h->p_kept, h->q, masked, ncu > 0 ? ncu : 256, force, who, &b->pl, &err);
+  const int rc = aq_mscreen_make_plan(h->n, h->p_kept, h->q, masked, ncu, aq_screen_env("AQ_MSCREEN_TILE"), who, &b->pl, &err);
   if (rc != AQ_OK) return aq_fail(rc, err);
   b->cap = cap;
   b->want_dense = want_dense;
@@ -76,11 +57,8 @@ static int aq_ms_setup(aq_prep *h, int64_t cap, bool want_dense, const char *who
 }
 
 template <int T, bool MASKED>
-static void aq_ms_launch_tile(bool a16, unsigned grid, const aq_ms_args &a) {
-  if (a16)
-    hipLaunchKernelGGL((aq_k_ms_tile<T, MASKED, true>), dim3(grid), dim3(256), 0, 0, a);
-  else
-    hipLaunchKernelGGL((aq_k_ms_tile<T, MASKED, false>), dim3(grid), dim3(256), 0, 0, a);
+static void aq_ms_launch_tile(unsigned grid, const aq_ms_args &a) {
+  aq_screen_a16(a.n, [&](auto a16) { hipLaunchKernelGGL((aq_k_ms_tile<T, MASKED, decltype(a16)::value>), dim3(grid), dim3(256), 0, 0, a); });
 }
 
 // every kernel of one screen after aq_ms_setup, with b->cut holding the cutoffs.  Asynchronous.
@@ -97,14 +75,13 @@ static int aq_ms_launch(aq_prep *h, AqMsBuf &b) {
   a.n_pairs = b.counters.get(); a.n_undef = b.counters.get() + 1; a.rs = b.rs.get();
   a.part_r = b.part_r.get(); a.part_s = b.part_s.get();
   a.r_dense = b.want_dense ? b.dense.get() : nullptr;
-  const bool a16 = (h->n & 1) == 0;            // even n: every column starts at a multiple of 16 bytes
   const unsigned grid = (unsigned)b.pl.n_tiles;
   if (b.pl.masked)
-    aq_ms_launch_tile<AQ_MSCREEN_TILE_MASKED, true>(a16, grid, a);
+    aq_ms_launch_tile<AQ_MSCREEN_TILE_MASKED, true>(grid, a);
   else if (b.pl.tile == 128)
-    aq_ms_launch_tile<128, false>(a16, grid, a);
+    aq_ms_launch_tile<128, false>(grid, a);
   else
-    aq_ms_launch_tile<64, false>(a16, grid, a);
+    aq_ms_launch_tile<64, false>(grid, a);
   hipLaunchKernelGGL(aq_k_ms_best, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, b.part_r.get(), b.part_s.get(), b.pl.tiles_p, q,
                      b.best_s.get(), b.best_r.get());
   AQ_HIP(hipGetLastError());
@@ -116,8 +93,7 @@ extern "C" int aq_prep_marginal(aq_prep_handle h, const double *r2_cut, int64_t 
   if (!r2_cut) return aq_fail(AQ_ERR_ARG, "aq_prep_marginal: NULL r2_cut");
   if (cap < 0) return aq_fail(AQ_ERR_ARG, "aq_prep_marginal: cap >= 0 required, " + std::to_string(cap) + " given");
   if (!h) return aq_fail(AQ_ERR_ARG, "aq_prep_marginal: NULL handle");
-  for (int t = 0; t < h->q; t++)
-    if (std::isnan(r2_cut[t])) return aq_fail(AQ_ERR_ARG, "aq_prep_marginal: r2_cut[" + std::to_string(t) + "] is NaN");
+  AQ_TRY(aq_screen_need_cut(r2_cut, h->q, "aq_prep_marginal"));
   AQ_TRY(aq_need_device(h->device));
   AQ_TRY(aq_need_acc_layout("aq_prep_marginal"));
   const size_t p1 = (size_t)h->p_kept, q = (size_t)h->q;
@@ -129,12 +105,7 @@ extern "C" int aq_prep_marginal(aq_prep_handle h, const double *r2_cut, int64_t 
   AQ_HIP(hipMemcpy(cnt, b.counters.get(), sizeof(cnt), hipMemcpyDeviceToHost));
   if (n_pairs) *n_pairs = (int64_t)cnt[0];
   if (n_undefined) *n_undefined = (int64_t)cnt[1];
-  const size_t rows = cnt[0] < (unsigned long long)cap ? (size_t)cnt[0] : (size_t)cap;
-  if (rows > 0) {
-    if (snp) AQ_HIP(hipMemcpy(snp, b.snp.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (trait) AQ_HIP(hipMemcpy(trait, b.trait.get(), rows * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (r) AQ_HIP(hipMemcpy(r, b.r.get(), rows * sizeof(double), hipMemcpyDeviceToHost));
-  }
+  AQ_TRY(aq_screen_copy_pairs(cnt[0], cap, b.snp, b.trait, b.r, snp, trait, r));
   static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
   if (rs) AQ_HIP(hipMemcpy(rs, b.rs.get(), p1 * sizeof(int64_t), hipMemcpyDeviceToHost));
   if (best_snp) AQ_HIP(hipMemcpy(best_snp, b.best_s.get(), q * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -144,7 +115,7 @@ extern "C" int aq_prep_marginal(aq_prep_handle h, const double *r2_cut, int64_t 
 }
 
 // Timing hook of aq_prep_marginal: every kernel of one screen, `reps` times between two events, counting only, without the
-// copies.  The cutoff is t^2 = 40 for every trait (p about 1e-9 at large df): r2_cut = 40 / (40 + df_t), +inf where df_t < 1.
+// copies.  The cutoff is aq_screen_time_cut at df_t = m_t - 2 - n_cov.
 extern "C" int aq_prep_marginal_time(aq_prep_handle h, int32_t reps, double *ms_per_call, aq_mscreen_plan *plan_out) {
   if (!h || !ms_per_call) return aq_fail(AQ_ERR_ARG, "aq_prep_marginal_time: NULL argument");
   if (reps < 1) return aq_fail(AQ_ERR_ARG, "aq_prep_marginal_time: reps >= 1 required");
@@ -154,15 +125,8 @@ extern "C" int aq_prep_marginal_time(aq_prep_handle h, int32_t reps, double *ms_
   AqMsBuf b;
   AQ_TRY(aq_ms_setup(h, 0, false, "aq_prep_marginal_time", &b));
   if (plan_out) *plan_out = b.pl;
-  {
-    std::vector<int> mt(q);
-    std::vector<double> cut(q);
-    AQ_HIP(hipMemcpy(mt.data(), b.mt.get(), q * sizeof(int), hipMemcpyDeviceToHost));
-    for (size_t t = 0; t < q; t++) {
-      const int df = mt[t] - 2 - h->n_cov;
-      cut[t] = df >= 1 ? 40.0 / (40.0 + (double)df) : std::numeric_limits<double>::infinity();
-    }
-    AQ_HIP(hipMemcpy(b.cut.get(), cut.data(), q * sizeof(double), hipMemcpyHostToDevice));
-  }
+  std::vector<double> cut(q);
+  for (size_t t = 0; t < q; t++) cut[t] = aq_screen_time_cut(b.mt_host[t] - 2 - h->n_cov);
+  AQ_HIP(hipMemcpy(b.cut.get(), cut.data(), q * sizeof(double), hipMemcpyHostToDevice));
   return aq_time_launches(reps, ms_per_call, [&] { return aq_ms_launch(h, b); });
 }

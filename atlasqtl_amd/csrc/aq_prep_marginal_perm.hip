@@ -5,15 +5,8 @@
 // undefined ones; aq_prep_marginal_perm_time times the kernels alone, aq_msperm_plan_query runs the planner on the host.  The
 // kernels are plain HIP that issues no hand-written load: the ISA proof of the look-ahead sweep units does not cover them and
 // need not.
-#include <hip/hip_runtime.h>
-#include <cmath>
-#include <cstdlib>
-#include <limits>
-#include <stdint.h>
-#include <string>
-#include <vector>
-#include "aq_prep.h"             // aq_prep, aq_time_launches; aq_internal.h: aq_fail, AQ_HIP, aq_need_device, aq_need_acc_layout, AqDev
-#include "aq_msperm_kernels.h"   // aq_k_msperm_gather, aq_k_msperm_tile, aq_k_msperm_reduce; aq_k_ms_traitstats, aq_k_ms_colstats
+#include "aq_screen_host.h"      // aq_screen_*; aq_prep.h, aq_internal.h; aq_screen_tile.h: aq_k_ms_gather, aq_k_ms_traitstats, aq_k_ms_colstats
+#include "aq_msperm_kernels.h"   // aq_k_msperm_tile, aq_k_msperm_reduce; aq_msperm_make_plan, aq_msperm_check_rows
 
 extern "C" int aq_msperm_plan_query(int32_t n, int32_t p1, int32_t q, int32_t masked, int32_t ncu, int32_t n_perm, aq_msperm_plan *out) {
   if (!out) return aq_fail(AQ_ERR_ARG, "aq_msperm_plan_query: NULL argument");
@@ -31,35 +24,19 @@ struct AqMspBuf {
   AqDev<unsigned long long> key, undef;
   AqDev<unsigned int> count;
   AqDev<long long> hs, nsel;
+  std::vector<int> mt_host;
   aq_msperm_plan pl{};
 };
-
-// an environment variable that forces a plan field: 0 when it is not set, -1 when it is no number >= 1 (the planner's message)
-static int aq_msp_env(const char *name) {
-  const char *e = getenv(name);
-  if (!e) return 0;
-  const int v = atoi(e);
-  return v < 1 ? -1 : v;
-}
 
 // Syy_t and m_t of the handle's traits (permutation-invariant), whether any value is missing, the plan, every buffer, and the
 // complete instance's Sx and Sxx
 static int aq_msp_setup(aq_prep *h, int n_perm, const char *who, AqMspBuf *b) {
   const size_t p1 = (size_t)h->p_kept, q = (size_t)h->q, n = (size_t)h->n;
-  AQ_TRY(b->syy.alloc(q));
-  AQ_TRY(b->mt.alloc(q));
-  hipLaunchKernelGGL(aq_k_ms_traitstats, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, h->Yc.get(), h->n, h->q, b->syy.get(),
-                     b->mt.get());
-  AQ_HIP(hipGetLastError());
-  std::vector<int> mt(q);
-  AQ_HIP(hipMemcpy(mt.data(), b->mt.get(), q * sizeof(int), hipMemcpyDeviceToHost));
-  int masked = 0;
-  for (size_t t = 0; t < q; t++) masked |= mt[t] < h->n;
-  int ncu = 0;
-  AQ_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
+  int masked = 0, ncu = 0;
+  AQ_TRY(aq_screen_trait_stats(h, &b->syy, &b->mt, &b->mt_host, &masked, &ncu));
   std::string err;
-  const int rc = aq_msperm_make_plan(h->n, h->p_kept, h->q, masked, ncu > 0 ? ncu : 256, n_perm, aq_msp_env("AQ_MSCREEN_TILE"),
-                                     aq_msp_env("AQ_MSPERM_PB"), aq_msp_env("AQ_MSPERM_BATCH"), who, &b->pl, &err);
+  const int rc = aq_msperm_make_plan(h->n, h->p_kept, h->q, masked, ncu, n_perm, aq_screen_env("AQ_MSCREEN_TILE"),
+                                     aq_screen_env("AQ_MSPERM_PB"), aq_screen_env("AQ_MSPERM_BATCH"), who, &b->pl, &err);
   if (rc != AQ_OK) return aq_fail(rc, err);
   const size_t batch = (size_t)b->pl.batch;
   AQ_TRY(b->cut.alloc(q));
@@ -81,11 +58,10 @@ static int aq_msp_setup(aq_prep *h, int n_perm, const char *who, AqMspBuf *b) {
 }
 
 template <int T, bool MASKED, int PB>
-static void aq_msp_launch_tile(bool a16, unsigned grid, const aq_msp_args &a) {
-  if (a16)
-    hipLaunchKernelGGL((aq_k_msperm_tile<T, MASKED, true, PB>), dim3(grid), dim3(256), 0, 0, a);
-  else
-    hipLaunchKernelGGL((aq_k_msperm_tile<T, MASKED, false, PB>), dim3(grid), dim3(256), 0, 0, a);
+static void aq_msp_launch_tile(unsigned grid, const aq_msp_args &a) {
+  aq_screen_a16(a.n, [&](auto a16) {   // even n: every column of Xs and of Yp starts at a multiple of 16 bytes
+    hipLaunchKernelGGL((aq_k_msperm_tile<T, MASKED, decltype(a16)::value, PB>), dim3(grid), dim3(256), 0, 0, a);
+  });
 }
 
 // the kernels of one launch over the nb <= batch permutations whose rows lie in b.perm, with b.cut holding the cutoffs.
@@ -96,8 +72,8 @@ static int aq_msp_launch(aq_prep *h, AqMspBuf &b, int nb) {
   AQ_HIP(hipMemsetAsync(b.count.get(), 0, (size_t)nb * (size_t)p1 * sizeof(unsigned int), 0));
   AQ_HIP(hipMemsetAsync(b.undef.get(), 0, (size_t)nb * sizeof(unsigned long long), 0));
   const long long cols = (long long)nb * (long long)q;
-  hipLaunchKernelGGL(aq_k_msperm_gather, dim3((unsigned)(cols < (1ll << 20) ? cols : (1ll << 20))), dim3(256), 0, 0, h->Yc.get(),
-                     b.perm.get(), n, q, nb, b.Yp.get());
+  hipLaunchKernelGGL(aq_k_ms_gather, dim3((unsigned)(cols < (1ll << 20) ? cols : (1ll << 20))), dim3(256), 0, 0, h->Yc.get(),
+                     (const int32_t *)nullptr, (const int32_t *)b.perm.get(), n, q, nb, b.Yp.get());
   aq_msp_args a{};
   a.Xs = h->Xs.get(); a.Yp = b.Yp.get();
   a.n = n; a.p1 = p1; a.q = q; a.n_cov = h->n_cov; a.tiles_p = b.pl.tiles_p;
@@ -105,21 +81,20 @@ static int aq_msp_launch(aq_prep *h, AqMspBuf &b, int nb) {
   a.nb = nb;
   a.sx = b.sx.get(); a.sxx = b.sxx.get(); a.syy = b.syy.get(); a.mt = b.mt.get(); a.cut = b.cut.get();
   a.key = b.key.get(); a.count = b.count.get(); a.n_undef = b.undef.get();
-  const bool a16 = (n & 1) == 0;                   // even n: every column of Xs and of Yp starts at a multiple of 16 bytes
   const unsigned grid = (unsigned)((long long)a.n_tiles * ((nb + pb - 1) / pb));
   if (b.pl.masked) {
     if (pb == 2)
-      aq_msp_launch_tile<AQ_MSCREEN_TILE_MASKED, true, 2>(a16, grid, a);
+      aq_msp_launch_tile<AQ_MSCREEN_TILE_MASKED, true, 2>(grid, a);
     else
-      aq_msp_launch_tile<AQ_MSCREEN_TILE_MASKED, true, 1>(a16, grid, a);
+      aq_msp_launch_tile<AQ_MSCREEN_TILE_MASKED, true, 1>(grid, a);
   } else if (b.pl.tile == 128) {
-    aq_msp_launch_tile<128, false, 1>(a16, grid, a);
+    aq_msp_launch_tile<128, false, 1>(grid, a);
   } else if (pb == 4) {
-    aq_msp_launch_tile<64, false, 4>(a16, grid, a);
+    aq_msp_launch_tile<64, false, 4>(grid, a);
   } else if (pb == 2) {
-    aq_msp_launch_tile<64, false, 2>(a16, grid, a);
+    aq_msp_launch_tile<64, false, 2>(grid, a);
   } else {
-    aq_msp_launch_tile<64, false, 1>(a16, grid, a);
+    aq_msp_launch_tile<64, false, 1>(grid, a);
   }
   hipLaunchKernelGGL(aq_k_msperm_reduce, dim3((unsigned)nb), dim3(256), 0, 0, b.count.get(), b.key.get(), p1, q, b.hs.get(), b.nsel.get(),
                      b.max_r2.get());
@@ -132,8 +107,7 @@ extern "C" int aq_prep_marginal_perm(aq_prep_handle h, const double *r2_cut, int
   if (n_perm < 1) return aq_fail(AQ_ERR_ARG, "aq_prep_marginal_perm: n_perm >= 1 required, " + std::to_string(n_perm) + " given");
   if (!r2_cut || !perm) return aq_fail(AQ_ERR_ARG, "aq_prep_marginal_perm: NULL r2_cut or perm");
   if (!h) return aq_fail(AQ_ERR_ARG, "aq_prep_marginal_perm: NULL handle");
-  for (int t = 0; t < h->q; t++)
-    if (std::isnan(r2_cut[t])) return aq_fail(AQ_ERR_ARG, "aq_prep_marginal_perm: r2_cut[" + std::to_string(t) + "] is NaN");
+  AQ_TRY(aq_screen_need_cut(r2_cut, h->q, "aq_prep_marginal_perm"));
   {
     std::string err;                             // an index out of range never reaches the gather kernel
     const int rc = aq_msperm_check_rows(perm, n_perm, h->n, "aq_prep_marginal_perm", &err);
@@ -160,9 +134,8 @@ extern "C" int aq_prep_marginal_perm(aq_prep_handle h, const double *r2_cut, int
 }
 
 // Timing hook of aq_prep_marginal_perm: the gather, tile and reduce kernels of n_perm permutations, launch by launch, `reps`
-// times between two events, without the copies.  The rows are pseudo-random permutations made here (a Fisher-Yates shuffle
-// driven by a 64-bit LCG), one batch of them, used again by every launch; the cutoff is that of aq_prep_marginal_time,
-// r2_cut = 40 / (40 + df_t), +inf where df_t < 1.
+// times between two events, without the copies.  The rows are one batch of aq_screen_time_perms, used again by every launch;
+// the cutoff is that of aq_prep_marginal_time.
 extern "C" int aq_prep_marginal_perm_time(aq_prep_handle h, int32_t n_perm, int32_t reps, double *ms_per_perm, aq_msperm_plan *plan_out) {
   if (!h || !ms_per_perm) return aq_fail(AQ_ERR_ARG, "aq_prep_marginal_perm_time: NULL argument");
   if (n_perm < 1 || reps < 1) return aq_fail(AQ_ERR_ARG, "aq_prep_marginal_perm_time: n_perm >= 1 and reps >= 1 required");
@@ -172,31 +145,11 @@ extern "C" int aq_prep_marginal_perm_time(aq_prep_handle h, int32_t n_perm, int3
   AqMspBuf b;
   AQ_TRY(aq_msp_setup(h, n_perm, "aq_prep_marginal_perm_time", &b));
   if (plan_out) *plan_out = b.pl;
-  {
-    std::vector<int> mt(q);
-    std::vector<double> cut(q);
-    AQ_HIP(hipMemcpy(mt.data(), b.mt.get(), q * sizeof(int), hipMemcpyDeviceToHost));
-    for (size_t t = 0; t < q; t++) {
-      const int df = mt[t] - 2 - h->n_cov;
-      cut[t] = df >= 1 ? 40.0 / (40.0 + (double)df) : std::numeric_limits<double>::infinity();
-    }
-    AQ_HIP(hipMemcpy(b.cut.get(), cut.data(), q * sizeof(double), hipMemcpyHostToDevice));
-    const size_t rows = (size_t)b.pl.batch;
-    std::vector<int32_t> perm(rows * n);
-    uint64_t state = 0x9e3779b97f4a7c15ull;
-    for (size_t r = 0; r < rows; r++) {
-      int32_t *row = perm.data() + r * n;
-      for (size_t i = 0; i < n; i++) row[i] = (int32_t)i;
-      for (size_t i = n; i > 1; i--) {
-        state = state * 6364136223846793005ull + 1442695040888963407ull;
-        const size_t j = (size_t)((state >> 33) % i);
-        const int32_t tmp = row[i - 1];
-        row[i - 1] = row[j];
-        row[j] = tmp;
-      }
-    }
-    AQ_HIP(hipMemcpy(b.perm.get(), perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
+  std::vector<double> cut(q);
+  for (size_t t = 0; t < q; t++) cut[t] = aq_screen_time_cut(b.mt_host[t] - 2 - h->n_cov);
+  AQ_HIP(hipMemcpy(b.cut.get(), cut.data(), q * sizeof(double), hipMemcpyHostToDevice));
+  const std::vector<int32_t> perm = aq_screen_time_perms((size_t)b.pl.batch, n);
+  AQ_HIP(hipMemcpy(b.perm.get(), perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   double ms = 0.0;
   AQ_TRY(aq_time_launches(reps, &ms, [&] {
     for (int done = 0; done < n_perm; done += b.pl.batch)

@@ -1,4 +1,4 @@
-"""GPU: the cis scan (aq_prep_cis, aq_prep_cis_perm, csrc/aq_cis_kernels.h) against the long-double restatement of
+"""GPU: the cis scan (aq_prep_cis, aq_prep_cis_perm, csrc/aq_cis_kernels.h, csrc/aq_screen_tile.h) against the long-double restatement of
 tests/mscreen_util.py run on the handle's own matrices and restricted to the windows, and against the device's own dense r of
 aq_prep_marginal on the same handle, which every in-window r must equal to the bit.
 

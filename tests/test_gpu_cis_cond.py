@@ -1,4 +1,4 @@
-"""GPU: the conditional cis scan (aq_prep_cis_cond, csrc/aq_ciscond_kernels.h) against the long-double restatement of
+"""GPU: the conditional cis scan (aq_prep_cis_cond, csrc/aq_ciscond_kernels.h, csrc/aq_screen_tile.h) against the long-double restatement of
 tests/ciscond_util.py run on the handle's own matrices, against the plain scan of the same handle, which every trait with an
 empty list must equal to the bit, and cis_independent() against the same loop run on the reference scan.
 

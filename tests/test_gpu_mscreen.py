@@ -1,4 +1,4 @@
-"""GPU: the marginal screen of a prepared handle (aq_prep_marginal, csrc/aq_mscreen_kernels.h) against the long-double
+"""GPU: the marginal screen of a prepared handle (aq_prep_marginal, csrc/aq_mscreen_kernels.h, csrc/aq_screen_tile.h) against the long-double
 restatement of tests/mscreen_util.py run on the handle's own matrices, at shapes chosen for the kernels' edges: below one tile
 (20, 3, 1), (50, 17, 5); odd n with p and q off every multiple of 16 and of 4 (333, 257, 33); one element past 128 and 64 in
 every dimension (257, 130, 130); many sample chunks (1000, 300, 70); many predictor tiles (130, 1000, 20).  Every shape runs

@@ -1,4 +1,4 @@
-"""GPU: permutation nulls of the marginal screen (aq_prep_marginal_perm, csrc/aq_msperm_kernels.h) against the long-double
+"""GPU: permutation nulls of the marginal screen (aq_prep_marginal_perm, csrc/aq_msperm_kernels.h, csrc/aq_screen_tile.h) against the long-double
 restatement of tests/mscreen_util.py run on the handle's own matrices with the rows of Y permuted on the host.  Shapes:
 (37, 70, 5): odd n, q below a tile, two predictor tiles; (50, 130, 67): n no multiple of 16, both dimensions ragged, two trait
 tiles; (96, 200, 150).  Each with complete Y and with the missing kinds "random" and "few", B = 5 permutations, and every

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the cis scan (aq_prep_cis_time: csrc/aq_cis_kernels.h) on the inputs of tools/time_marginal.py, n = 1000,
+"""Times the cis scan (aq_prep_cis_time: csrc/aq_cis_kernels.h, the tile loop in csrc/aq_screen_tile.h) on the inputs of tools/time_marginal.py, n = 1000,
 p = 50 000, q = 10 000, random int8 dosages and Gaussian traits, complete Y and Y with 5 % of its values missing.  The
 predictors sit evenly on 22 "chromosomes", 1000 base pairs apart, and the traits at random positions; the windows reach
 `--half` predictors to either side of the trait, cut at the ends of its chromosome (a chromosome holds p / 22 predictors, so

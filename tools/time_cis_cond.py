@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the conditional cis scan (aq_prep_cis_cond_time: csrc/aq_ciscond_kernels.h) on the inputs of tools/time_cis.py,
+"""Times the conditional cis scan (aq_prep_cis_cond_time: csrc/aq_ciscond_kernels.h, the tile loop in csrc/aq_screen_tile.h) on the inputs of tools/time_cis.py,
 n = 1000, p = 50 000, q = 10 000, random int8 dosages and complete Gaussian traits, windows reaching `--half` predictors to
 either side of the trait (about 600 predictors with the default 300).  On one handle and in one process, `--repeats` times:
 the plain scan (aq_prep_cis_time: max k = 0), then the conditional scan with every trait conditioned on k = 1, 2 and 4

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times aq_prep_marginal, the marginal screen of a prepared handle (csrc/aq_mscreen_kernels.h), at bench.py's shape
+"""Times aq_prep_marginal, the marginal screen of a prepared handle (csrc/aq_mscreen_kernels.h, the tile loop in csrc/aq_screen_tile.h), at bench.py's shape
 (n = 1000, p = 50 000, q = 10 000) on random int8 dosages and Gaussian traits: complete Y, and Y with 5 % of its values missing.
 Per case: all kernels of one screen alone (aq_prep_marginal_time: events around `--reps` launches after a warm-up, counting
 only), and the whole entry as marginal_screen() calls it, with its allocations and copies (wall clock, one warm-up).  TFLOP/s

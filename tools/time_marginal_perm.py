@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times aq_prep_marginal_perm, the permutation nulls of the marginal screen (csrc/aq_msperm_kernels.h), at bench.py's shape
+"""Times aq_prep_marginal_perm, the permutation nulls of the marginal screen (csrc/aq_msperm_kernels.h, the tile loop in csrc/aq_screen_tile.h), at bench.py's shape
 (n = 1000, p = 50 000, q = 10 000) on random int8 dosages and Gaussian traits: complete Y, and Y with 5 % of its values missing.
 Per case and per instance of the tile kernel (complete: tile 128 with PB 1 and tile 64 with PB 1, 2, 4; masked: PB 1, 2;
 forced through AQ_MSCREEN_TILE and AQ_MSPERM_PB) the kernels of one full batch of permutations -- gather, tile, reduce -- per
