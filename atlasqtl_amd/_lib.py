@@ -195,6 +195,7 @@ SYMBOLS = {
     "aq_q_approx_vec": (C.c_int, [dp, dp, C.c_int64, ip]),
     "aq_vb_debug_raise_errflag": (C.c_int, [C.c_void_p]),
     "aq_debug_live_device_bytes": (C.c_int64, []),
+    "aq_vb_debug_get_setup": (C.c_int64, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),
     "aq_prepare_data_bed": (C.c_int, [C.POINTER(AqPrepBedInput), C.POINTER(C.c_void_p)]),
     "aq_prep_genotype_counts": (C.c_int, [C.c_void_p, ip]),
     "aq_prepare_data_cov": (C.c_int, [C.POINTER(AqPrepInput), C.POINTER(AqPrepCov), C.POINTER(C.c_void_p)]),

@@ -240,6 +240,45 @@ extern "C" int aq_vb_debug_raise_errflag(aq_vb_handle s) {
 }
 extern "C" int64_t aq_debug_live_device_bytes(void) { return aq_live_device_bytes.load(); }
 
+// What aq_vb_create built once for this handle, read back as it lies in device memory: copies only, no kernel, no lifetime
+// changed (a buffer the handle has already released reads as length 0).
+extern "C" int64_t aq_vb_debug_get_setup(aq_vb_handle s, int32_t which, void *buf, int64_t cap_bytes) {
+  if (!s) return -(int64_t)aq_fail(AQ_ERR_ARG, "aq_vb_debug_get_setup: NULL handle");
+  if (which < 0 || which >= AQ_SETUP_COUNT) return -(int64_t)aq_fail(AQ_ERR_ARG, "aq_vb_debug_get_setup: which out of range");
+  if (cap_bytes < 0 || (cap_bytes > 0 && !buf)) return -(int64_t)aq_fail(AQ_ERR_ARG, "aq_vb_debug_get_setup: NULL buffer or negative capacity");
+  const int32_t geo[AQ_SETUP_GEOMETRY_LEN] = {s->nb, s->ntile, s->n_pad, s->p_pad, s->q_pad, s->NR, s->Mmax, s->dmode, s->use_la ? 1 : 0,
+                                              s->la_mask ? 1 : 0, s->la_wide ? 1 : 0, s->use_mis ? 1 : 0, s->use_tw ? 1 : 0};
+  if (which == AQ_SETUP_GEOMETRY) {
+    if (cap_bytes >= (int64_t)sizeof(geo)) std::memcpy(buf, geo, sizeof(geo));
+    return (int64_t)sizeof(geo);
+  }
+  const size_t xpanel = (size_t)s->nb * (s->n_pad / 16) * 128 * sizeof(double2), tile16 = (size_t)s->ntile * 16;
+  const void *src = nullptr;
+  size_t bytes = 0;
+  switch (which) {
+    case AQ_SETUP_XA: src = s->use_tw ? nullptr : s->XA.get(); bytes = xpanel; break;
+    case AQ_SETUP_XU: src = s->use_tw ? nullptr : s->XU.get(); bytes = xpanel; break;
+    case AQ_SETUP_XR: src = s->XR.get(); bytes = (size_t)s->nb * s->NR * 16 * sizeof(double); break;
+    case AQ_SETUP_G: src = s->use_tw ? nullptr : s->G.get(); bytes = (size_t)s->nb * 256 * sizeof(double); break;
+    case AQ_SETUP_GX: src = s->use_tw ? nullptr : s->Gx.get(); bytes = (size_t)s->nb * 256 * sizeof(double); break;
+    case AQ_SETUP_GK: src = s->GK.get(); bytes = (size_t)s->ntile * s->nb * AQ_GK_STRIDE * sizeof(double); break;
+    case AQ_SETUP_MIDX: src = s->midx.get(); bytes = tile16 * s->Mmax * sizeof(int); break;
+    case AQ_SETUP_MCNT4: src = s->mcnt4.get(); bytes = tile16 * sizeof(int); break;
+    case AQ_SETUP_MOBS: src = s->mobs.get(); bytes = tile16 * sizeof(int); break;
+    case AQ_SETUP_MIS: src = s->mis.get(); bytes = tile16 * s->n_pad * sizeof(double); break;
+    case AQ_SETUP_R: src = s->R.get(); bytes = tile16 * s->n_pad * sizeof(double); break;
+    case AQ_SETUP_GAM: src = s->gam.get(); bytes = tile16 * s->p_pad * sizeof(double); break;
+    case AQ_SETUP_MU: src = s->mu.get(); bytes = tile16 * s->p_pad * sizeof(double); break;
+  }
+  if (!src) return 0;
+  if (cap_bytes >= (int64_t)bytes) {
+    hipError_t e = hipSetDevice(s->device);
+    if (e == hipSuccess) e = hipMemcpy(buf, src, bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return -(int64_t)aq_fail(AQ_ERR_DEVICE, std::string("aq_vb_debug_get_setup: ") + hipGetErrorString(e));
+  }
+  return (int64_t)bytes;
+}
+
 // one element of the test hook, compiled for host and device from the same header the kernels use
 __host__ __device__ static inline bool aq_special_one(int which, double x, double x2, double *out) {
   double a_, b_, c_, d_;

@@ -408,6 +408,21 @@ int aq_vb_debug_raise_errflag(aq_vb_handle h);
  * prepared data, buffers of entries in flight).  0 in a fresh process; back at its earlier value once everything that was
  * created since has been destroyed. */
 int64_t aq_debug_live_device_bytes(void);
+/* Test hook: one of the buffers aq_vb_create builds once per handle, as it lies in device memory (the layouts are described in
+ * atlasqtl_amd/csrc/aq_core_sweep.h and aq_vb.h).  Returns the buffer's length in bytes and copies it to buf when cap_bytes
+ * suffices (buf may be NULL with cap_bytes = 0: the length alone); 0 for a buffer this handle does not hold -- GK without the
+ * MASK instances, XR once a MASK handle has released it, the operand panels and Gram blocks under the generic kernel; and
+ * -AQ_ERR_ARG / -AQ_ERR_DEVICE with aq_last_error() set (NULL handle, which out of range, cap_bytes < 0, NULL buf with
+ * cap_bytes > 0; a failed copy).  Copies only: launches nothing, allocates nothing, keeps nothing alive.
+ * AQ_SETUP_GEOMETRY: AQ_SETUP_GEOMETRY_LEN int32 -- nb, ntile, n_pad, p_pad, q_pad, NR, Mmax, dmode, then 0 / 1 each for
+ * use_la, la_mask, la_wide, use_mis, use_tw (the planner's fields, atlasqtl_amd/csrc/aq_plan.h).  XA, XU: double2; midx,
+ * mcnt4, mobs: int32; everything else: double. */
+enum {
+  AQ_SETUP_GEOMETRY = 0, AQ_SETUP_XA, AQ_SETUP_XU, AQ_SETUP_XR, AQ_SETUP_G, AQ_SETUP_GX, AQ_SETUP_GK, AQ_SETUP_MIDX,
+  AQ_SETUP_MCNT4, AQ_SETUP_MOBS, AQ_SETUP_MIS, AQ_SETUP_R, AQ_SETUP_GAM, AQ_SETUP_MU, AQ_SETUP_COUNT
+};
+#define AQ_SETUP_GEOMETRY_LEN 13
+int64_t aq_vb_debug_get_setup(aq_vb_handle h, int32_t which, void *buf, int64_t cap_bytes);
 /* exp(x) E1(x) for a vector with the reference's shared Lentz stopping rule (R/utils.R:380-423);
  * host evaluation; writes the shared iteration count to *iters. */
 int aq_q_approx_vec(const double *x, double *out, int64_t len, int32_t *iters);
