@@ -100,6 +100,11 @@ class AqCiscondPlan(C.Structure):
                 ("qo_bytes", C.c_int64), ("yo_bytes", C.c_int64)]
 
 
+class AqCisintPlan(C.Structure):
+    _fields_ = [("cis", AqCisPlan), ("streams", C.c_int32), ("n_basis", C.c_int32), ("lds_bytes", C.c_int32), ("mult_pad", C.c_int32),
+                ("yo_bytes", C.c_int64), ("pred_bytes", C.c_int64), ("basis_bytes", C.c_int64)]
+
+
 class AqPredictPlan(C.Structure):
     _fields_ = [("sample_tiles", C.c_int32), ("trait_tiles", C.c_int32), ("sample_blocks", C.c_int32), ("trait_groups", C.c_int32),
                 ("splits", C.c_int32), ("chunk", C.c_int32), ("chunks_per_split", C.c_int32), ("n_pad", C.c_int32),
@@ -233,6 +238,10 @@ SYMBOLS = {
     "aq_prep_cis_cond": (C.c_int, [C.c_void_p, ip, ip, ip, ip, dp, C.c_int64, ip, ip, dp, C.POINTER(C.c_int64), ip, dp,
                                    C.POINTER(C.c_int64), ip, C.POINTER(AqCiscondPlan)]),
     "aq_prep_cis_cond_time": (C.c_int, [C.c_void_p, ip, ip, ip, ip, C.c_int32, dp, dp, C.POINTER(AqCiscondPlan)]),
+    "aq_cisint_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, ip, C.c_int32, C.POINTER(AqCisintPlan)]),
+    "aq_prep_cis_int": (C.c_int, [C.c_void_p, ip, ip, dp, C.c_int32, dp, dp, C.c_int64, ip, ip, dp, C.POINTER(C.c_int64), ip, dp,
+                                  C.POINTER(C.c_int64), dp, C.POINTER(AqCisintPlan)]),
+    "aq_prep_cis_int_time": (C.c_int, [C.c_void_p, ip, ip, dp, C.c_int32, dp, C.c_int32, dp, dp, C.POINTER(AqCisintPlan)]),
     "aq_predict_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AqPredictPlan)]),
     "aq_vb_predict": (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int8), C.c_int32, dp, dp, dp]),
     "aq_vb_fitted": (C.c_int, [C.c_void_p, C.c_void_p, dp]),

@@ -16,6 +16,10 @@ condition_on= turns the scan into the conditional one (aq_prep_cis_cond, csrc/aq
 correlation given the trait's own conditioning variants, df_t = n - 2 - n_cov - k_eff[t].  cis_independent() runs the
 forward-backward conditional pass of QTLtools and tensorQTL's map_independent on top of it: the loop itself is
 independent_signals_, which takes the scan as a callable.
+
+interaction= turns the scan into the genotype x environment one (aq_prep_cis_int, csrc/aq_prep_cis_int.hip; tensorQTL's
+map_cis(interaction_df=)): r becomes the partial correlation of g o e with the trait given the intercept, the covariates, e
+and g, df = n - 4 - n_cov.  The basis of [1, Z, e] the library takes is built here, on the host (interaction_basis).
 """
 from __future__ import annotations
 
@@ -197,13 +201,96 @@ def _refuse_with_condition(permutations, Y):
         raise AtlasqtlError("cis_screen: condition_on= needs complete Y; Y has missing values.")
 
 
-def cis_handle(prep, names_x, names_y, s_lo, s_hi, p_value=None, fdr=None, max_pairs=None, permutations=None, condition_on=None):
+COV_TOL = 1e-10                                        # AQ_COV_TOL of csrc/aq_cov_kernels.h: the rule of aq_cov_basis
+
+
+def _interaction_vector(e, n=None):
+    """The interaction variable as one finite, non-constant float64 vector (of n values, where n is given)."""
+    try:
+        ev = np.asarray(e, dtype=np.float64)
+    except (TypeError, ValueError):
+        ev = None
+    if ev is None or ev.ndim != 1 or ev.size < 1 or (n is not None and ev.shape[0] != int(n)):
+        want = "one value per sample" if n is None else f"one value per sample ({int(n)})"
+        raise AtlasqtlError(f"cis_screen: interaction must be one numeric vector with {want}, not "
+                            f"{'that' if ev is None else ev.shape}. One interaction term per call.")
+    if not np.all(np.isfinite(ev)):
+        raise AtlasqtlError("cis_screen: interaction must be finite without missing value.")
+    if ev.max() == ev.min():
+        raise AtlasqtlError("cis_screen: interaction is constant: it cannot be told from the intercept.")
+    return ev
+
+
+def interaction_basis(e, covariates, n, n_cov):
+    """(B, m) for the interaction scan, on the host: m = e centred (n values) and B, nb x n with nb = n_cov + 2, the orthonormal
+    rows spanning [1, Z, e] in this order, by Gram-Schmidt with one re-orthogonalisation and long-double dot products.  A
+    column is dropped when what is left of it after the columns before it has a squared norm <= 1e-10 times its own (the
+    rule of aq_cov_basis).  Refused with AtlasqtlError, before anything is computed on a device: an e of the wrong length, a
+    non-finite e, a constant e, an e inside span[1, Z], and covariates whose rank (the columns not dropped) is not n_cov, the
+    number the handle was prepared with."""
+    n, n_cov = int(n), int(n_cov)
+    ev = _interaction_vector(e, n)
+    if covariates is None:
+        Z = np.zeros((n, 0))
+    else:
+        try:
+            Z = np.asarray(covariates, dtype=np.float64)
+        except (TypeError, ValueError):
+            Z = None
+        if Z is None or Z.ndim != 2 or Z.shape[0] != n or not np.all(np.isfinite(Z)):
+            raise AtlasqtlError(f"cis_screen: covariates must be a finite numeric matrix with one row per sample ({n}).")
+    LD = np.longdouble
+    rows = [np.full(n, 1.0 / np.sqrt(n))]
+
+    def remainder(col):
+        v = np.array(col, dtype=np.float64)
+        own = float(np.dot(v.astype(LD), v.astype(LD)))
+        for _ in range(2):
+            for b in rows:
+                v = v - b * float(np.dot(b.astype(LD), v.astype(LD)))
+        rem = float(np.dot(v.astype(LD), v.astype(LD)))
+        return v, rem, own
+
+    for l in range(Z.shape[1]):
+        v, rem, own = remainder(Z[:, l])
+        if rem > COV_TOL * own:
+            rows.append(v / np.sqrt(rem))
+    rank = len(rows) - 1
+    if rank != n_cov:
+        raise AtlasqtlError(f"cis_screen: the covariates given with interaction= have rank {rank}, but the data were prepared with "
+                            f"{n_cov} covariates. Pass the covariates the data were prepared with.")
+    m = ev - ev.mean()
+    v, rem, own = remainder(m)
+    if not rem > COV_TOL * own:
+        raise AtlasqtlError("cis_screen: interaction lies in the span of the intercept and the covariates: its effect cannot be "
+                            "told from theirs.")
+    rows.append(v / np.sqrt(rem))
+    return np.ascontiguousarray(np.stack(rows, axis=0)), m
+
+
+def _refuse_with_interaction(permutations, condition_on, Y):
+    if permutations is not None:
+        raise AtlasqtlError("cis_screen: interaction= together with permutations= is not supported: permutation nulls are "
+                            "computed for the plain scan only. best_pvalue_bonferroni corrects each trait's best interaction.")
+    if condition_on is not None:
+        raise AtlasqtlError("cis_screen: interaction= together with condition_on= is not supported. Run the two separately.")
+    if Y is not None and np.isnan(np.asarray(Y, dtype=np.float64)).any():
+        raise AtlasqtlError("cis_screen: interaction= needs complete Y; Y has missing values.")
+
+
+def cis_handle(prep, names_x, names_y, s_lo, s_hi, p_value=None, fdr=None, max_pairs=None, permutations=None, condition_on=None,
+               interaction=None, covariates=None):
     """The cis scan on a PreparedData as it stands, with the windows given as index ranges over its columns: cis_screen()
     without the preparation and without cis_windows.  condition_on: as for cis_screen(), by index into names_x / names_y or by
-    name; None takes the unconditional path unchanged.  Returns the result without the rmvd_* fields."""
+    name; None takes the unconditional path unchanged.  interaction: as for cis_screen(), with covariates the matrix the data
+    were prepared with (None: none); None changes nothing.  Returns the result without the rmvd_* fields."""
     from .api import AtlasqtlResult
     p, q = int(prep.p), int(prep.q)
     o = cis_options(p_value, fdr, max_pairs)
+    inter = None
+    if interaction is not None:
+        _refuse_with_interaction(permutations, condition_on, prep.Y)
+        inter = interaction_basis(interaction, covariates, int(prep.n), int(prep.n_cov))
     cond = None
     if condition_on is not None:
         cond = condition_lists(condition_on, names_x, names_y)
@@ -216,7 +303,11 @@ def cis_handle(prep, names_x, names_y, s_lo, s_hi, p_value=None, fdr=None, max_p
     n_obs = np.sum(~np.isnan(prep.Y), axis=0).astype(np.int64)
     df = n_obs - 2 - int(prep.n_cov)
     cap = int(min(M, INITIAL_CAP))
-    if cond is None:
+    if inter is not None:
+        def scan(cut, cap):
+            return prep.cis_interaction(s_lo, s_hi, inter[0], inter[1], cut, cap)
+        df = df - 2                                           # e and g: n - 4 - n_cov
+    elif cond is None:
         def scan(cut, cap):
             return prep.cis(s_lo, s_hi, cut, cap)
     else:
@@ -259,6 +350,10 @@ def cis_handle(prep, names_x, names_y, s_lo, s_hi, p_value=None, fdr=None, max_p
     if cond is not None:
         res["condition_on"] = cond
         res["k_eff"] = out["k_eff"]
+    if inter is not None:
+        res["interaction"] = inter[1]
+        res["int_tol"] = out["int_tol"]
+        res["best_pvalue_bonferroni"] = np.minimum(1.0, best_p * n_tests_t)
     if po is not None:
         max_r2 = prep.cis_permute(s_lo, s_hi, po["perms"])
         res["permutation"] = dict(n=po["n"], seed=po["seed"], max_r2=max_r2,
@@ -275,7 +370,7 @@ def _per_predictor(values, p_given, name):
 
 def cis_screen(Y, X, trait_chrom, trait_start, trait_end=None, window=1_000_000, snp_chrom=None, snp_pos=None, p_value=None,
                fdr=None, max_pairs=None, permutations=None, covariates=None, ld_prune=None, transform_y=None, device=0,
-               condition_on=None):
+               condition_on=None, interaction=None):
     """Every trait of Y tested against the predictors of X within `window` base pairs of it, on the GPU: cis-QTL mapping.
 
     X and Y are prepared exactly as marginal_screen() prepares them.  trait_chrom, trait_start, trait_end (default:
@@ -318,12 +413,32 @@ def cis_screen(Y, X, trait_chrom, trait_start, trait_end=None, window=1_000_000,
     listed variant itself is) or the list explains the whole trait.  The result then also carries condition_on (the q index
     lists) and k_eff (per trait, the listed variants not collinear with the earlier ones; 0 where the window is empty).
     Complete Y only, and not together with permutations=: both are refused before anything is computed.  A window of
-    [0, p) for every trait is the conditional trans scan.  Without the argument the call is the unconditional scan above."""
+    [0, p) for every trait is the conditional trans scan.  Without the argument the call is the unconditional scan above.
+
+    interaction (None, or one vector e of n values: cell-type fraction, sex, age, treatment; one term per call, as in
+    tensorQTL's map_cis(interaction_df=)) makes the scan the genotype x environment one (aq_prep_cis_int): every in-window pair
+    is tested for the coefficient of g o e in y ~ 1 + covariates + e + g + g o e, g the prepared predictor.  r in assoc is then
+    the partial correlation of g o e with the trait given the other four, t = r sqrt(df / (1 - r^2)) that coefficient's OLS t,
+    and df = n - 4 - d.  A pair is undefined when g is collinear with [1, covariates, e] (a variant that equals e), when g o e
+    is collinear with [1, covariates, e, g] (a variant that is zero outside one level of a binary e), or when these explain
+    the whole trait.  The result then also carries interaction (e centred), int_tol (per kept predictor, the share of g o e
+    that [1, covariates, e, g] leave; NaN where the predictor is undefined) and best_pvalue_bonferroni = min(1, best_pvalue
+    n_tests), the correction of each trait's best interaction over its window.  e must be finite, not constant, and outside
+    span[1, covariates].  Complete Y only, and not together with permutations= or condition_on=: all refused before anything
+    is computed.  A window of [0, p) for every trait is the genome-wide interaction scan.  Without the argument the call is
+    the scan above, unchanged."""
     from .plink import PlinkBed
     cis_options(p_value, fdr, max_pairs)                       # before the first device call
     permutation_options(permutations)
     if condition_on is not None:
         _refuse_with_condition(permutations, None if isinstance(Y, str) else Y)
+    if interaction is not None:
+        Yh = None if isinstance(Y, str) else Y
+        _refuse_with_interaction(permutations, condition_on, Yh)
+        if Yh is not None and np.ndim(Yh) == 2 and (covariates is None or np.ndim(covariates) == 2):
+            interaction_basis(interaction, covariates, np.shape(Yh)[0], 0 if covariates is None else np.shape(covariates)[1])
+        else:
+            _interaction_vector(interaction)
     if not _is_whole(window) or int(window) < 0:
         raise AtlasqtlError(f"cis_screen: window must be a whole number >= 0, not {window!r}.")
     if isinstance(X, PlinkBed):
@@ -342,7 +457,8 @@ def cis_screen(Y, X, trait_chrom, trait_start, trait_end=None, window=1_000_000,
         if len(np.atleast_1d(trait_start)) != int(prep.q):
             raise AtlasqtlError(f"cis_screen: trait_chrom, trait_start and trait_end must hold one value per trait ({int(prep.q)}).")
         s_lo, s_hi = cis_windows(snp_chrom[kept], snp_pos[kept], trait_chrom, trait_start, trait_end, window)
-        res = cis_handle(prep, dat["names_x"], dat["names_y"], s_lo, s_hi, p_value, fdr, max_pairs, permutations, condition_on)
+        res = cis_handle(prep, dat["names_x"], dat["names_y"], s_lo, s_hi, p_value, fdr, max_pairs, permutations, condition_on,
+                         interaction, covariates if interaction is not None else None)
     finally:
         prep.close()
     for key in ("rmvd_cst_x", "rmvd_coll_x", "rmvd_cov_x", "rmvd_ld_x"):

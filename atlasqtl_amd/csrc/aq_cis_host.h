@@ -1,8 +1,8 @@
 // aq_cis_host.h -- the host side that the entries of the cis scan share (aq_prep_cis.hip: the plain scan and its permutation
-// nulls; aq_prep_cis_cond.hip: the conditional scan): the device buffers of one call, the set-up that runs the planner of
+// nulls; aq_prep_cis_cond.hip: the conditional scan; aq_prep_cis_int.hip: the interaction scan): the device buffers of one call, the set-up that runs the planner of
 // aq_cis_plan.h and uploads the order, the work list and the per-trait arrays, the arguments every tile kernel takes, and
 // the column sums, the launch of the plain scan's tile kernel and the copy-back of a scan's outputs.  What the marginal screen's
-// entries need as well lies beneath, in aq_screen_host.h.  Static functions: each of the two units has its own copy.
+// entries need as well lies beneath, in aq_screen_host.h.  Static functions: each of the three units has its own copy.
 #pragma once
 #include "aq_screen_host.h"   // aq_screen_*; aq_prep.h, aq_internal.h
 #include "aq_cis_kernels.h"   // aq_k_cis_*; aq_screen_tile.h: aq_k_ms_gather, aq_k_ms_colstats; aq_cis_make_plan

@@ -1,7 +1,7 @@
 // aq_cis_kernels.h -- the cis scan of a finished prepare handle: the statistic of aq_mscreen_kernels.h
 // evaluated only for the pairs (predictor s, trait t) with s_lo[t] <= s < s_hi[t], a band of the p1 x q matrix, and the
-// permutation null of each trait's best in-window predictor.  Included through aq_cis_host.h by aq_prep_cis.hip and
-// aq_prep_cis_cond.hip, so its kernels that are no templates are static; the launch plan, the order of the traits and the list
+// permutation null of each trait's best in-window predictor.  Included through aq_cis_host.h by aq_prep_cis.hip,
+// aq_prep_cis_cond.hip and aq_prep_cis_int.hip, so its kernels that are no templates are static; the launch plan, the order of the traits and the list
 // of work items are aq_cis_plan.h; the tile loop, the pair statistic, the reductions and the kernels aq_k_ms_gather,
 // aq_k_ms_traitstats and aq_k_ms_colstats are those of aq_screen_tile.h.  Every kernel is a plain grid: no workgroup waits for
 // another one, nothing spins, and no floating-point atomic is used (the integer atomics are counters and a maximum over bit

@@ -1,5 +1,5 @@
 // aq_screen_host.h -- the host side that the entries of the screen family share (aq_prep_marginal.hip,
-// aq_prep_marginal_perm.hip and, beneath aq_cis_host.h, aq_prep_cis.hip and aq_prep_cis_cond.hip): the reader of the
+// aq_prep_marginal_perm.hip and, beneath aq_cis_host.h, aq_prep_cis.hip, aq_prep_cis_cond.hip and aq_prep_cis_int.hip): the reader of the
 // environment hooks, the per-trait sums with the decision whether any value is missing, the cutoff and the permutation rows of
 // the timing hooks, the check of r2_cut, the copy-back of the capped pair table, and the step from the runtime parity of n to
 // the kernels' A16 template argument.  Static functions: each unit has its own copy.  The including unit includes its kernel

@@ -1,6 +1,6 @@
 // aq_screen_tile.h -- what the f64-MFMA tile kernels of the screen family share: aq_k_ms_tile
-// (aq_mscreen_kernels.h), aq_k_msperm_tile (aq_msperm_kernels.h), aq_k_cis_tile and aq_k_cis_perm_tile (aq_cis_kernels.h) and
-// aq_k_cc_tile (aq_ciscond_kernels.h).  The tile geometry and the panel movers, the staged main loop, the pair statistic, the
+// (aq_mscreen_kernels.h), aq_k_msperm_tile (aq_msperm_kernels.h), aq_k_cis_tile and aq_k_cis_perm_tile (aq_cis_kernels.h),
+// aq_k_cc_tile (aq_ciscond_kernels.h) and aq_k_ci_tile (aq_cisint_kernels.h, on the sibling loop aq_ms_tile_loop_x2).  The tile geometry and the panel movers, the staged main loop, the pair statistic, the
 // lane and wave reductions and the three small kernels every entry runs around its tile kernel exist here and nowhere else, so
 // that "r of a pair is the same bits in every kernel of the family", which the GPU tests require, is a property of one text.
 // A kernel header keeps its argument block, its LDS declarations, its work-item decoding and the parts of the epilogue that
@@ -271,6 +271,70 @@ __device__ __forceinline__ void aq_ms_tile_loop(const double *Xs, int n, int p1,
             }
         }
       if (STEP == AQ_MS_STEP_FENCED) __builtin_amdgcn_sched_barrier(0);   // nothing of the next step is scheduled into this one
+    }
+  }
+}
+
+// The sibling of aq_ms_tile_loop for the interaction scan (aq_k_ci_tile, aq_cisint_kernels.h): complete Y, ONE trait-side
+// panel and TWO predictor-side streams fed from the one staged panel of X, acc0 += Y X and acc1 += Y (X o mult), the second
+// operand x * mult[sample] formed in registers with one rounding, as the masked instances above form x^2: no second LDS panel
+// and no p1 x n matrix of products.  The movers, the shapes, the lane struct, the staging and the order of accumulation (one
+// MFMA per step of 4 samples, samples ascending) are those of aq_ms_tile_loop, so acc0 of a pair is axy of the plain scan on
+// the same panel to the bit; the operands of the one panel are read together with X's (STEP = PAIRED there).  A lane's operand
+// of step kk holds sample i0 + kk + g, so its multiplier is mpad[i0 + kk + g]: mpad is the multiplier padded with zeros to
+// whole chunks of AQ_MSCREEN_NC samples (aq_cisint_mult_pad), read without a guard, the four of a chunk together with the
+// chunk's panels one chunk ahead.  aq_ms_tile_loop's text is not touched: its five kernels compile to the ISA they had.
+template <int T, bool A16>
+__device__ __forceinline__ void aq_ms_tile_loop_x2(const double *Xs, int n, int p1, int p0, const double *Yo, int ncols, int c0,
+                                                   const double *__restrict__ mpad, double *PX, double *PT, aq_ms_acc<T, 1> &acc0,
+                                                   aq_ms_acc<T, 1> &acc1) {
+  typedef AqMsShape<T> SH;
+  constexpr int NI = SH::NI, NK = AQ_MSCREEN_NC / 4;
+  const AqMsLane ln;
+#pragma unroll
+  for (int i = 0; i < NI; i++)
+#pragma unroll
+    for (int jj = 0; jj < NI; jj++) {
+      acc0[0][i][jj] = aq_ms_d4{0.0, 0.0, 0.0, 0.0};
+      acc1[0][i][jj] = aq_ms_d4{0.0, 0.0, 0.0, 0.0};
+    }
+  const double *pt = PT + (ln.wr * SH::WT + ln.l) * SH::STR + ln.g;
+  const double *px = PX + (ln.wc * SH::WT + ln.l) * SH::STR + ln.g;
+  double2 vx[SH::NV], vt[SH::NV];
+  double mnext[NK], mk[NK];
+  aq_ms_load<T, A16>(Xs, n, p1, p0, 0, vx);
+  aq_ms_load<T, A16>(Yo, n, ncols, c0, 0, vt);
+#pragma unroll
+  for (int s = 0; s < NK; s++) mnext[s] = mpad[4 * s + ln.g];
+  for (int i0 = 0; i0 < n; i0 += AQ_MSCREEN_NC) {
+    __syncthreads();                             // the panels of the previous chunk have been read
+    aq_ms_store<T>(vx, PX);
+    aq_ms_store<T>(vt, PT);
+#pragma unroll
+    for (int s = 0; s < NK; s++) mk[s] = mnext[s];
+    __syncthreads();
+    if (i0 + AQ_MSCREEN_NC < n) {                // then i0 + 2 AQ_MSCREEN_NC <= the length of mpad
+      aq_ms_load<T, A16>(Xs, n, p1, p0, i0 + AQ_MSCREEN_NC, vx);
+      aq_ms_load<T, A16>(Yo, n, ncols, c0, i0 + AQ_MSCREEN_NC, vt);
+#pragma unroll
+      for (int s = 0; s < NK; s++) mnext[s] = mpad[i0 + AQ_MSCREEN_NC + 4 * s + ln.g];
+    }
+#pragma unroll
+    for (int kk = 0; kk < AQ_MSCREEN_NC; kk += 4) {
+      double x[NI], xm[NI], y[NI];
+#pragma unroll
+      for (int i = 0; i < NI; i++) {
+        y[i] = pt[16 * i * SH::STR + kk];
+        x[i] = px[16 * i * SH::STR + kk];
+        xm[i] = x[i] * mk[kk / 4];               // one rounding
+      }
+#pragma unroll
+      for (int i = 0; i < NI; i++)
+#pragma unroll
+        for (int jj = 0; jj < NI; jj++) {
+          acc0[0][i][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(y[i], x[jj], acc0[0][i][jj], 0, 0, 0);
+          acc1[0][i][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(y[i], xm[jj], acc1[0][i][jj], 0, 0, 0);
+        }
     }
   }
 }

@@ -333,6 +333,41 @@ class PreparedData:
         return dict(snp=snp[:k], trait=trait[:k], r=r[:k], n_pairs=int(n_pairs.value), best_snp=best_snp, best_r=best_r,
                     n_undef=n_undef, k_eff=k_eff, plan=pd)
 
+    def cis_interaction(self, s_lo, s_hi, basis, mult, r2_cut, cap):
+        """The interaction cis scan of the matrix as it stands: aq_prep_cis_int.  s_lo, s_hi, r2_cut, cap: as for cis().
+        basis: nb x n, orthonormal rows spanning the intercept, the covariates the matrix was prepared with and the interaction
+        variable e (cis.interaction_basis); mult: n, e centred.  Complete Y only.  Returns the dict of cis() with r the partial
+        correlation of the interaction term g o e given [1, Z, e, g] (df = n - nb - 2), and int_tol: per column, the share of
+        g o e that [1, Z, e, g] leave (NaN where the column is undefined for every trait); plan: the dict of aq_cisint_plan,
+        the fields of its aq_cis_plan alongside."""
+        import ctypes as C
+        lo, hi = self._cis_windows_arg(s_lo, s_hi, "cis_interaction")
+        cut = np.ascontiguousarray(r2_cut, dtype=np.float64)
+        if cut.shape != (self.q,):
+            raise AtlasqtlError(f"cis_interaction: r2_cut must hold one cutoff per trait ({self.q}), not {cut.shape}.")
+        B = np.ascontiguousarray(basis, dtype=np.float64)
+        m = np.ascontiguousarray(mult, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] < 1 or B.shape[1] != self.n or m.shape != (self.n,):
+            raise AtlasqtlError(f"cis_interaction: basis must be nb x n and mult must hold n = {self.n} values, not {B.shape} and "
+                                f"{m.shape}.")
+        if np.isnan(self.Y).any():
+            raise AtlasqtlError("cis_interaction: Y has missing values; the interaction scan takes complete Y only.")
+        cap = int(cap)
+        rows = max(cap, 0)
+        snp = np.empty(rows, dtype=np.int32); trait = np.empty(rows, dtype=np.int32); r = np.empty(rows)
+        best_snp = np.empty(self.q, dtype=np.int32); best_r = np.empty(self.q); n_undef = np.zeros(self.q, dtype=np.int64)
+        int_tol = np.empty(self.p)
+        n_pairs, plan = C.c_int64(0), _lib.AqCisintPlan()
+        _lib.check(_lib.lib().aq_prep_cis_int(self.handle, _lib.as_ip(lo), _lib.as_ip(hi), _lib.as_dp(B), B.shape[0], _lib.as_dp(m),
+                                              _lib.as_dp(cut), cap, _lib.as_ip(snp), _lib.as_ip(trait), _lib.as_dp(r), C.byref(n_pairs),
+                                              _lib.as_ip(best_snp), _lib.as_dp(best_r), n_undef.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              _lib.as_dp(int_tol), C.byref(plan)), "aq_prep_cis_int")
+        k = min(int(n_pairs.value), rows)
+        pd = {name: int(getattr(plan.cis, name)) for name, _ in _lib.AqCisPlan._fields_}
+        pd.update({name: int(getattr(plan, name)) for name, _ in _lib.AqCisintPlan._fields_ if name != "cis"})
+        return dict(snp=snp[:k], trait=trait[:k], r=r[:k], n_pairs=int(n_pairs.value), best_snp=best_snp, best_r=best_r,
+                    n_undef=n_undef, int_tol=int_tol, plan=pd)
+
     def close(self):
         if self.handle is not None:
             _lib.lib().aq_prep_destroy(self.handle)

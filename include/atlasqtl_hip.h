@@ -878,6 +878,62 @@ int aq_prep_cis_cond_time(aq_prep_handle h, const int32_t *s_lo, const int32_t *
                           int32_t reps, double *ms_basis, double *ms_scan, aq_ciscond_plan *plan_out);
 
 /* ------------------------------------------------------------------------------------------
+ * Interaction cis scan of a finished handle: for every in-window pair, whether the effect of the predictor on the trait
+ * depends on a sample-level variable e (cell-type fraction, sex, age, treatment): the genotype x environment pass of an eQTL
+ * pipeline, tensorQTL's map_cis(interaction_df=).  The windows, the order of the traits and the work items are those of
+ * aq_prep_cis.
+ * The statistic.  Complete Y only.  Xs [p1][n] and Yc [q][n] are the handle's prepared matrices.  B is nb orthonormal
+ * n-vectors spanning [1, Z, e], Z the covariates the handle was prepared with, nb = n_cov + 2: basis[k n + i] is entry i of
+ * b_k.  m is the per-sample multiplier: e centred, n doubles (mult).
+ *   Per trait t:      y' = y_t - sum_k b_k (b_k'y_t), in the order of B;  S'yy_t = sum y'^2;  S0yy_t is the Syy_t of the
+ *                     plain scan.
+ *   Per predictor s,  with g = Xs[:, s] and w = g o m, every product rounded once:
+ *                     a_k = b_k'g;  c_k = b_k'w;  Sxx = g'g;  Sww = w'w;
+ *                     Vg = Sxx - sum a_k^2;  Cgw = g'w - sum a_k c_k;  Vw = Sww - sum c_k^2 - Cgw^2 / Vg.
+ *   Per in-window pair (s_lo[t] <= s < s_hi[t]):  Sgy = g'y' and Swy = w'y', the two matrix-instruction streams, both fed
+ *                     from one staged panel of Xs, w formed in registers;
+ *                     num = Swy - (Cgw / Vg) Sgy;  S'' = S'yy - Sgy^2 / Vg;  r = num / sqrt(Vw S'').
+ *   df = n - nb - 2 and t = r sqrt(df / (1 - r^2)).
+ * r is the partial correlation of the interaction term g o e with the trait given the intercept, Z, e and g, so this t is the
+ * OLS t of the coefficient of g o e in y ~ 1 + Z + e + g + g o e.
+ *   Undefined pairs.  A pair is undefined when Vg <= 1e-10 Sxx, Vw <= 1e-10 Sww, S'' <= 1e-10 S0yy_t, or df < 1.  Its r is
+ *   NaN; it is counted in n_undef and never selected.  Two realistic cases: a variant that is zero outside one level of a
+ *   binary e, where g o m is collinear with [g, e]; a variant that equals e.
+ * No floating-point atomics: two calls give the same set of rows and the same bits in every other output.
+ *   aq_prep_cis_int        r2_cut, cap, snp, trait, r, n_pairs, best_snp, best_r, n_undef: as for aq_prep_cis.  int_tol:
+ *                          double[p1], Vw / Sww, the share of the interaction term that [1, Z, e, g] leave; NaN where the
+ *                          predictor itself is undefined (one of the first two rules).  plan_out: the plan used.  Any output
+ *                          may be NULL.  The handle is not changed.
+ *   aq_cisint_plan_query   the plan without a device, a pure function of its arguments.  What aq_cis_plan_query refuses,
+ *                          and residual traits above 4 GiB, are refused here.
+ *   aq_prep_cis_int_time   measurement, after aq_prep_cis_cond_time: ms_stats, the per-predictor kernel and the trait
+ *                          residuals; ms_scan, the rest of one scan (the tile kernel, the reduction of the bests), counting
+ *                          only, with the cutoff t^2 = 40 at df.  Each `reps` times between two events after a warm-up.
+ * AQ_ERR_ARG, in this order, before any device call: a NULL s_lo, s_hi, basis, mult or r2_cut (ms_stats, ms_scan) or a NULL
+ * handle; cap < 0 (reps < 1); n_basis < 1 (n_basis > 256 is AQ_ERR_UNSUPPORTED at this place, and the message says that at
+ * most 256 basis vectors are supported); a non-finite entry of basis or of mult; max |B'B - I| > 1e-8; mult outside
+ * span(B), |m - B B'm|^2 > 1e-10 |m|^2; mult all zero; the window errors of aq_prep_cis; a NaN cutoff.  A handle whose Y has
+ * missing values is AQ_ERR_UNSUPPORTED, and the message says so.  No index out of range reaches a kernel.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_cisint_plan {
+  aq_cis_plan cis;            /* the plan of the windows: complete Y, no permutations             */
+  int32_t streams;            /* 2 matrix-instruction streams per staged panel of Xs              */
+  int32_t n_basis;            /* nb                                                               */
+  int32_t lds_bytes;          /* static LDS of a workgroup of the tile kernel, <= 64 KiB          */
+  int32_t mult_pad;           /* doubles of the zero-padded multiplier: n up to whole chunks      */
+  int64_t yo_bytes;           /* the residual traits: 8 max(q_active, 1) n                        */
+  int64_t pred_bytes;         /* per predictor Vg, Cgw / Vg, Vw, int_tol and the flag: 36 p1      */
+  int64_t basis_bytes;        /* the basis and the padded multiplier: 8 (nb n + mult_pad)         */
+} aq_cisint_plan;
+int aq_cisint_plan_query(int32_t n, int32_t p1, int32_t q, int32_t ncu, const int32_t *s_lo, const int32_t *s_hi, int32_t n_basis,
+                         aq_cisint_plan *out);
+int aq_prep_cis_int(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, const double *basis, int32_t n_basis, const double *mult,
+                    const double *r2_cut, int64_t cap, int32_t *snp, int32_t *trait, double *r, int64_t *n_pairs, int32_t *best_snp,
+                    double *best_r, int64_t *n_undef, double *int_tol, aq_cisint_plan *plan_out);
+int aq_prep_cis_int_time(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, const double *basis, int32_t n_basis,
+                         const double *mult, int32_t reps, double *ms_stats, double *ms_scan, aq_cisint_plan *plan_out);
+
+/* ------------------------------------------------------------------------------------------
  * Prediction: the fitted model applied to genotypes,
  *   Yhat = Xt B,   B = beta_vb = gam_vb * mu_beta_vb (p x q, R/update_vb.R:17),   Xt = (X_new - center) / scale per column,
  * n_new x q: the genetic component of the traits on the scale of the prepared Y, in-sample (the X_beta_vb that the reference's
