@@ -9,7 +9,8 @@ from .api import add_collinear_back_pairs_, atlasqtl, print_atlasqtl, summary  #
 from .core import (VbRun, assign_bFDR, associations, atlasqtl_global_core_, atlasqtl_global_local_core_,  # noqa: F401
                    coreDualLoop, coreDualMisLoop, hotspot_sizes, merge_pair_tables, value_summary)
 from .hyper_init import set_hyper, set_init  # noqa: F401
-from .prepare import AtlasqtlError, genotype_grm, genotype_pcs, rank_normalize  # noqa: F401
+from .checks import AtlasqtlError  # noqa: F401
+from .prepare import genotype_grm, genotype_pcs, rank_normalize  # noqa: F401
 from .plink import PlinkBed  # noqa: F401
 from .marginal import marginal_screen  # noqa: F401
 from .cis import cis_independent, cis_screen, cis_windows, independent_signals_  # noqa: F401

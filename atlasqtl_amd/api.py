@@ -1,7 +1,7 @@
 """User-level entry point: ``atlasqtl()`` with the reference's argument surface
 (R/atlasqtl.R:179-184) and return fields (R/atlasqtl.R:293-316,
 R/atlasqtl_global_local_core.R:426-428).  Pre-processing and hyper-parameter /
-initialisation handling run on the host (prepare.py, hyper_init.py); the
+initialisation handling run on the host (checks.py, prepare.py, hyper_init.py); the
 variational loop runs on the GPU through core.atlasqtl_global_local_core_.
 """
 from __future__ import annotations
@@ -16,8 +16,8 @@ from .core import atlasqtl_global_local_core_
 from .postproc import hotspot_sizes, six_numbers_host_, sparse_output_options, value_summary
 from .hyper_init import prepare_list_hyper_, prepare_list_init_
 from .marginal import screen_arg, screen_handle
-from .prepare import (check_annealing_, check_positive_, check_vector_, check_verbose_, covariates_with_genotype_pcs,
-                      prepare_data_, transform_y_options)
+from .checks import check_annealing_, check_positive_, check_vector_, check_verbose_
+from .prepare import covariates_with_genotype_pcs, prepare_data_, transform_y_options
 
 
 class AtlasqtlResult(dict):

@@ -25,8 +25,11 @@ from __future__ import annotations
 
 import numpy as np
 
-from .marginal import INITIAL_CAP, bh_qvalues, permutation_options, r2_cutoff, screen_options, t_and_pvalue, table_order
-from .prepare import AtlasqtlError, _is_whole, prepare_data_
+from .checks import AtlasqtlError, _is_real, _is_whole
+from .marginal import (INITIAL_CAP, association_table_, bh_qvalues, on_prepared_, permutation_options, permutation_trait_pvalue,
+                       r2_cutoff, screen_options, t_and_pvalue)
+from .plink import PlinkBed
+from .prepare import prepare_data_
 
 
 def cis_windows(snp_chrom, snp_pos, trait_chrom, trait_start, trait_end=None, window=1_000_000):
@@ -118,13 +121,8 @@ def cis_permutation_summary(max_r2, best_snp, best_r, best_pvalue, df):
       beta_shape1, beta_shape2, trait_pvalue_beta: beta_approximation;
       trait_qvalue: Benjamini-Hochberg of trait_pvalue_beta over the traits with a defined pair (NaN elsewhere, and where the
         beta approximation is NaN: those traits are not among the tests)."""
-    max_r2 = np.asarray(max_r2, dtype=np.float64)
-    B = max_r2.shape[0]
-    best_r = np.asarray(best_r, dtype=np.float64)
+    trait_p = permutation_trait_pvalue(max_r2, best_snp, best_r)
     has = np.asarray(best_snp) >= 0
-    obs = np.where(has, best_r * best_r, np.inf)
-    trait_p = (1.0 + np.sum(max_r2 >= obs[None, :], axis=0)) / (B + 1.0)
-    trait_p[~has] = np.nan
     s1, s2, pbeta = beta_approximation(max_r2, df, np.where(has, best_pvalue, np.nan))
     qv = np.full(trait_p.shape, np.nan)
     tested = np.nonzero(has & ~np.isnan(pbeta))[0]
@@ -323,26 +321,10 @@ def cis_handle(prep, names_x, names_y, s_lo, s_hi, p_value=None, fdr=None, max_p
         out = scan(cut, cap)
     if out["n_pairs"] > cap:                                  # the complete set, whatever order the first call filled its rows in
         out = scan(cut, out["n_pairs"])
-    snp, trait, r = out["snp"], out["trait"], out["r"]
-    dfr = df[trait].astype(np.float64)
-    t, pv = t_and_pvalue(r, dfr)
-    order = table_order(pv, t, snp, trait, p)
-    snp, trait, r, t, pv, dfr = snp[order], trait[order], r[order], t[order], pv[order], dfr[order]
     n_tests_t = n_cis - out["n_undef"]
     n_tests = int(n_tests_t.sum())
-    qv = bh_qvalues(pv, n_tests)
-    if o["mode"] == "fdr":                                    # the device selected p <= alpha, a superset of the BH set
-        keep = int(np.sum(qv <= level))                       # q is non-decreasing along the table
-        snp, trait, r, t, pv, dfr, qv = (a[:keep] for a in (snp, trait, r, t, pv, dfr, qv))
-    n_pairs = int(snp.size)
-    m = n_pairs if o["max_pairs"] is None else min(n_pairs, o["max_pairs"])
-    assoc = dict(snp=snp[:m], trait=trait[:m], r=r[:m], t=t[:m], df=dfr[:m].astype(np.int64), pvalue=pv[:m], qvalue=qv[:m],
-                 snp_name=np.asarray(names_x, dtype=object)[snp[:m]], trait_name=np.asarray(names_y, dtype=object)[trait[:m]],
-                 n_pairs=n_pairs)
+    assoc, best_p, _, _ = association_table_(out, df, n_tests, o["mode"], level, o["max_pairs"], names_x, names_y, p)
     best_snp, best_r = out["best_snp"], out["best_r"]
-    best_p = np.full(q, np.nan)
-    has = best_snp >= 0
-    best_p[has] = t_and_pvalue(best_r[has], df[has])[1]
     res = AtlasqtlResult(assoc=assoc, window=(s_lo, s_hi), n_cis=n_cis, n_tests=n_tests_t, best_snp=best_snp, best_r=best_r,
                          best_pvalue=best_p, n_obs=n_obs, df=df, n_undefined=out["n_undef"], n=int(prep.n), p=p, q=q,
                          threshold=dict(mode=o["mode"], level=level, r2_cut=cut, n_tests=n_tests), plan=out["plan"],
@@ -361,11 +343,34 @@ def cis_handle(prep, names_x, names_y, s_lo, s_hi, p_value=None, fdr=None, max_p
     return res
 
 
-def _per_predictor(values, p_given, name):
-    a = np.asarray(values)
-    if a.ndim != 1 or a.shape[0] != int(p_given):
-        raise AtlasqtlError(f"cis_screen: {name} must hold one value per predictor given ({int(p_given)}), not {a.shape}.")
-    return a
+def _snp_coordinates(X, snp_chrom, snp_pos, who):
+    """snp_chrom and snp_pos as given, or the chrom and pos of a PlinkBed X where they are not."""
+    if isinstance(X, PlinkBed):
+        snp_chrom = X.chrom if snp_chrom is None else snp_chrom
+        snp_pos = X.pos if snp_pos is None else snp_pos
+    if snp_chrom is None or snp_pos is None:
+        raise AtlasqtlError(f"{who}: snp_chrom and snp_pos are required unless X is a PlinkBed.")
+    return snp_chrom, snp_pos
+
+
+def _per_predictor(X, snp_chrom, snp_pos):
+    """snp_chrom and snp_pos as arrays with one value per predictor given."""
+    p_given = X.shape[1] if hasattr(X, "shape") else np.asarray(X).shape[1]
+    out = []
+    for name, values in (("snp_chrom", snp_chrom), ("snp_pos", snp_pos)):
+        a = np.asarray(values)
+        if a.ndim != 1 or a.shape[0] != int(p_given):
+            raise AtlasqtlError(f"cis_screen: {name} must hold one value per predictor given ({int(p_given)}), not {a.shape}.")
+        out.append(a)
+    return out
+
+
+def _windows_of_kept(prep, dat, snp_chrom, snp_pos, trait_chrom, trait_start, trait_end, window, who):
+    """cis_windows over the columns the preparation kept, once the traits are known to be as many as the prepared ones."""
+    kept = ~np.asarray(dat["bool_rmvd_x"], dtype=bool)
+    if len(np.atleast_1d(trait_start)) != int(prep.q):
+        raise AtlasqtlError(f"{who}: trait_chrom, trait_start and trait_end must hold one value per trait ({int(prep.q)}).")
+    return cis_windows(snp_chrom[kept], snp_pos[kept], trait_chrom, trait_start, trait_end, window)
 
 
 def cis_screen(Y, X, trait_chrom, trait_start, trait_end=None, window=1_000_000, snp_chrom=None, snp_pos=None, p_value=None,
@@ -427,7 +432,6 @@ def cis_screen(Y, X, trait_chrom, trait_start, trait_end=None, window=1_000_000,
     span[1, covariates].  Complete Y only, and not together with permutations= or condition_on=: all refused before anything
     is computed.  A window of [0, p) for every trait is the genome-wide interaction scan.  Without the argument the call is
     the scan above, unchanged."""
-    from .plink import PlinkBed
     cis_options(p_value, fdr, max_pairs)                       # before the first device call
     permutation_options(permutations)
     if condition_on is not None:
@@ -441,33 +445,21 @@ def cis_screen(Y, X, trait_chrom, trait_start, trait_end=None, window=1_000_000,
             _interaction_vector(interaction)
     if not _is_whole(window) or int(window) < 0:
         raise AtlasqtlError(f"cis_screen: window must be a whole number >= 0, not {window!r}.")
-    if isinstance(X, PlinkBed):
-        snp_chrom = X.chrom if snp_chrom is None else snp_chrom
-        snp_pos = X.pos if snp_pos is None else snp_pos
-    if snp_chrom is None or snp_pos is None:
-        raise AtlasqtlError("cis_screen: snp_chrom and snp_pos are required unless X is a PlinkBed.")
-    p_given = X.shape[1] if hasattr(X, "shape") else np.asarray(X).shape[1]
-    snp_chrom = _per_predictor(snp_chrom, p_given, "snp_chrom")
-    snp_pos = _per_predictor(snp_pos, p_given, "snp_pos")
-    dat = prepare_data_(Y, X, 0.1, 1, None, 0, None, None, device=device, covariates=covariates, ld_prune=ld_prune,
-                        transform_y=transform_y)
-    prep = dat["X"]
-    try:
-        kept = ~np.asarray(dat["bool_rmvd_x"], dtype=bool)
-        if len(np.atleast_1d(trait_start)) != int(prep.q):
-            raise AtlasqtlError(f"cis_screen: trait_chrom, trait_start and trait_end must hold one value per trait ({int(prep.q)}).")
-        s_lo, s_hi = cis_windows(snp_chrom[kept], snp_pos[kept], trait_chrom, trait_start, trait_end, window)
-        res = cis_handle(prep, dat["names_x"], dat["names_y"], s_lo, s_hi, p_value, fdr, max_pairs, permutations, condition_on,
-                         interaction, covariates if interaction is not None else None)
-    finally:
-        prep.close()
-    for key in ("rmvd_cst_x", "rmvd_coll_x", "rmvd_cov_x", "rmvd_ld_x"):
-        res[key] = dat[key]
-    res["n_covariates"] = dat["n_covariates"]
-    return res
+    snp_chrom, snp_pos = _per_predictor(X, *_snp_coordinates(X, snp_chrom, snp_pos, "cis_screen"))
+
+    def body(prep, dat):
+        s_lo, s_hi = _windows_of_kept(prep, dat, snp_chrom, snp_pos, trait_chrom, trait_start, trait_end, window, "cis_screen")
+        return cis_handle(prep, dat["names_x"], dat["names_y"], s_lo, s_hi, p_value, fdr, max_pairs, permutations, condition_on,
+                          interaction, covariates if interaction is not None else None)
+    return on_prepared_(prepare_data_, body, Y, X, device, covariates, ld_prune, transform_y)
 
 
 MAX_SIGNALS = 5                                        # one more than the variants a trait can be conditioned on
+
+
+def _check_max_signals(max_signals):
+    if not _is_whole(max_signals) or not 1 <= int(max_signals) <= MAX_SIGNALS:
+        raise AtlasqtlError(f"cis_independent: max_signals must be a whole number from 1 to {MAX_SIGNALS}, not {max_signals!r}.")
 
 
 def independent_signals_(scan, best_snp, best_pvalue, threshold, max_signals=MAX_SIGNALS, best_r=None, df=None):
@@ -488,8 +480,7 @@ def independent_signals_(scan, best_snp, best_pvalue, threshold, max_signals=MAX
     keeps it as it is.
     Returns dict(forward: per trait the forward variants; signals: per trait a list of dict(rank [1-based position in the
     forward set], snp, forward_snp, pvalue, r, df [NaN / -1 where the scan does not give them]); n_signals)."""
-    if not _is_whole(max_signals) or not 1 <= int(max_signals) <= MAX_SIGNALS:
-        raise AtlasqtlError(f"cis_independent: max_signals must be a whole number from 1 to {MAX_SIGNALS}, not {max_signals!r}.")
+    _check_max_signals(max_signals)
     best_snp = np.asarray(best_snp)
     best_pvalue = np.asarray(best_pvalue, dtype=np.float64)
     threshold = np.asarray(threshold, dtype=np.float64)
@@ -530,12 +521,11 @@ def cis_independent_handle(prep, names_x, names_y, s_lo, s_hi, fdr=0.05, permuta
     the result without the rmvd_* fields."""
     from scipy.stats import beta
     from .api import AtlasqtlResult
-    if isinstance(fdr, (bool, np.bool_)) or not isinstance(fdr, (int, float, np.integer, np.floating)) or not 0 < float(fdr) <= 1:
+    if not _is_real(fdr, 0.0, 1.0, lo_open=True):
         raise AtlasqtlError(f"cis_independent: fdr must be a number in (0, 1], not {fdr!r}.")
     if permutations is None:
         raise AtlasqtlError("cis_independent: permutations are required: they decide the eGenes and each gene's threshold.")
-    if not _is_whole(max_signals) or not 1 <= int(max_signals) <= MAX_SIGNALS:
-        raise AtlasqtlError(f"cis_independent: max_signals must be a whole number from 1 to {MAX_SIGNALS}, not {max_signals!r}.")
+    _check_max_signals(max_signals)
     if np.isnan(prep.Y).any():
         raise AtlasqtlError("cis_independent: the conditional scans need complete Y; Y has missing values.")
     primary = cis_handle(prep, names_x, names_y, s_lo, s_hi, permutations=permutations)
@@ -594,32 +584,14 @@ def cis_independent(Y, X, trait_chrom, trait_start, trait_end=None, window=1_000
         trait's other forward variants; unconditional for a trait with one signal), snp_name, trait_name;
       n_signals: per trait; forward: per trait the forward variants; threshold: per trait (NaN where the beta approximation
       is NaN, or there is no eGene); egene; primary: the result of (a); names_x, names_y, n, p, q, n_covariates, rmvd_*."""
-    from .plink import PlinkBed
-    if isinstance(X, PlinkBed):
-        snp_chrom = X.chrom if snp_chrom is None else snp_chrom
-        snp_pos = X.pos if snp_pos is None else snp_pos
-    if snp_chrom is None or snp_pos is None:
-        raise AtlasqtlError("cis_independent: snp_chrom and snp_pos are required unless X is a PlinkBed.")
-    if not _is_whole(max_signals) or not 1 <= int(max_signals) <= MAX_SIGNALS:
-        raise AtlasqtlError(f"cis_independent: max_signals must be a whole number from 1 to {MAX_SIGNALS}, not {max_signals!r}.")
+    snp_chrom, snp_pos = _snp_coordinates(X, snp_chrom, snp_pos, "cis_independent")
+    _check_max_signals(max_signals)
     if permutations is None:
         raise AtlasqtlError("cis_independent: permutations are required: they decide the eGenes and each gene's threshold.")
     permutation_options(permutations)
-    p_given = X.shape[1] if hasattr(X, "shape") else np.asarray(X).shape[1]
-    snp_chrom = _per_predictor(snp_chrom, p_given, "snp_chrom")
-    snp_pos = _per_predictor(snp_pos, p_given, "snp_pos")
-    dat = prepare_data_(Y, X, 0.1, 1, None, 0, None, None, device=device, covariates=covariates, ld_prune=ld_prune,
-                        transform_y=transform_y)
-    prep = dat["X"]
-    try:
-        kept = ~np.asarray(dat["bool_rmvd_x"], dtype=bool)
-        if len(np.atleast_1d(trait_start)) != int(prep.q):
-            raise AtlasqtlError(f"cis_independent: trait_chrom, trait_start and trait_end must hold one value per trait ({int(prep.q)}).")
-        s_lo, s_hi = cis_windows(snp_chrom[kept], snp_pos[kept], trait_chrom, trait_start, trait_end, window)
-        res = cis_independent_handle(prep, dat["names_x"], dat["names_y"], s_lo, s_hi, fdr, permutations, max_signals)
-    finally:
-        prep.close()
-    for key in ("rmvd_cst_x", "rmvd_coll_x", "rmvd_cov_x", "rmvd_ld_x"):
-        res[key] = dat[key]
-    res["n_covariates"] = dat["n_covariates"]
-    return res
+    snp_chrom, snp_pos = _per_predictor(X, snp_chrom, snp_pos)
+
+    def body(prep, dat):
+        s_lo, s_hi = _windows_of_kept(prep, dat, snp_chrom, snp_pos, trait_chrom, trait_start, trait_end, window, "cis_independent")
+        return cis_independent_handle(prep, dat["names_x"], dat["names_y"], s_lo, s_hi, fdr, permutations, max_signals)
+    return on_prepared_(prepare_data_, body, Y, X, device, covariates, ld_prune, transform_y)

@@ -116,7 +116,7 @@ class VbRun:
     def __init__(self, Y, X, list_hyper, list_init, anneal, tol, maxit, thinned_elbo_eval=True, debug=True,
                  device=0, q_total=None, process_group=None, trait_offset=0, scheme="global_local", df=1):
         L = lib()
-        prep = X if hasattr(X, "x_ptr") else None       # prepare.PreparedData: standardised X and centred Y already on the GPU
+        prep = X if hasattr(X, "x_ptr") else None       # prepared.PreparedData: standardised X and centred Y already on the GPU
         Y = np.asfortranarray(Y, dtype=np.float64)
         if prep is None:
             X = np.asfortranarray(X, dtype=np.float64)
@@ -364,7 +364,7 @@ class VbRun:
         return prediction.apply_in_batches(call, X, self.q, center, scale)
 
     def fitted(self, prep):
-        """X beta_vb (n x q), the reference's X_beta_vb, on the standardised X of the fit: a prepare.PreparedData (its matrix
+        """X beta_vb (n x q), the reference's X_beta_vb, on the standardised X of the fit: a prepared.PreparedData (its matrix
         is used where it lies on the device, aq_vb_fitted) or the host matrix the run was given."""
         if not hasattr(prep, "x_ptr"):
             return self.predict(prep)

@@ -1,8 +1,9 @@
 // aq_cis_host.h -- the host side that the entries of the cis scan share (aq_prep_cis.hip: the plain scan and its permutation
 // nulls; aq_prep_cis_cond.hip: the conditional scan; aq_prep_cis_int.hip: the interaction scan): the device buffers of one call, the set-up that runs the planner of
 // aq_cis_plan.h and uploads the order, the work list and the per-trait arrays, the arguments every tile kernel takes, and
-// the column sums, the launch of the plain scan's tile kernel and the copy-back of a scan's outputs.  What the marginal screen's
-// entries need as well lies beneath, in aq_screen_host.h.  Static functions: each of the three units has its own copy.
+// the column sums, the launch of the plain scan's tile kernel and the copy-back of a scan's outputs.  Moved here from the three
+// units, which each had a copy: aq_cis_launch_scan, aq_cis_upload_time_cut, aq_cis_setup_complete and aq_cis_keep_syy.  What the
+// marginal screen's entries need as well lies beneath, in aq_screen_host.h.  Static functions: each unit has its own copy.
 #pragma once
 #include "aq_screen_host.h"   // aq_screen_*; aq_prep.h, aq_internal.h
 #include "aq_cis_kernels.h"   // aq_k_cis_*; aq_screen_tile.h: aq_k_ms_gather, aq_k_ms_colstats; aq_cis_make_plan
@@ -101,6 +102,33 @@ static int aq_cis_setup(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, co
   return AQ_OK;
 }
 
+// aq_cis_setup for a scan that takes complete Y only: missing values are refused under the entry's name, `scan` naming the scan
+static int aq_cis_setup_complete(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, const double *r2_cut, int64_t cap, const char *who,
+                                 const char *scan, AqCisBuf *b) {
+  AQ_TRY(aq_cis_setup(h, s_lo, s_hi, r2_cut, cap, true, 0, who, b));
+  if (b->pl.masked)
+    return aq_fail(AQ_ERR_UNSUPPORTED, std::string(who) + ": Y has missing values; the " + scan + " scan takes complete Y only");
+  return AQ_OK;
+}
+
+// b.syy holds Syy_t per ordered trait; a scan whose first kernel overwrites it keeps the trait's own in syy0 first
+static int aq_cis_keep_syy(AqCisBuf &b, AqDev<double> *syy0) {
+  const size_t qa = (size_t)b.wk.q_active;
+  AQ_TRY(syy0->alloc(qa > 0 ? qa : 1));
+  if (qa > 0) AQ_HIP(hipMemcpy(syy0->get(), b.syy.get(), qa * sizeof(double), hipMemcpyDeviceToDevice));
+  return AQ_OK;
+}
+
+// the timing hooks' cutoff per ordered trait j: aq_screen_time_cut at df(j) degrees of freedom, in the place of r2_cut
+template <typename Df>
+static int aq_cis_upload_time_cut(AqCisBuf &b, Df &&df) {
+  const size_t qa = (size_t)b.wk.q_active;
+  std::vector<double> cut(qa);
+  for (size_t j = 0; j < qa; j++) cut[j] = aq_screen_time_cut(df(j));
+  if (qa > 0) AQ_HIP(hipMemcpy(b.cut.get(), cut.data(), qa * sizeof(double), hipMemcpyHostToDevice));
+  return AQ_OK;
+}
+
 static aq_cis_args aq_cis_common_args(aq_prep *h, AqCisBuf &b) {
   aq_cis_args a{};
   a.Xs = h->Xs.get();
@@ -150,6 +178,22 @@ static int aq_cis_colstats(aq_prep *h, AqCisBuf &b) {
     hipLaunchKernelGGL(aq_k_ms_colstats, dim3((unsigned)h->p_kept), dim3(256), 0, 0, h->Xs.get(), h->n, b.sx.get(), b.sxx.get());
     AQ_HIP(hipGetLastError());
   }
+  return AQ_OK;
+}
+
+// every kernel of one scan after its set-up, on the null stream: the counter and the undefined counts zeroed, the column sums
+// (colstats), then, if the plan has work items, the unit's tile(W, the scan's arguments), then the bests.  Asynchronous.
+template <typename Tile>
+static int aq_cis_launch_scan(aq_prep *h, AqCisBuf &b, bool colstats, Tile &&tile) {
+  const int q = h->q, qa = b.wk.q_active;
+  const unsigned W = (unsigned)b.pl.n_items;
+  AQ_HIP(hipMemsetAsync(b.counter.get(), 0, sizeof(unsigned long long), 0));
+  AQ_HIP(hipMemsetAsync(b.undef.get(), 0, (size_t)q * sizeof(unsigned long long), 0));
+  if (colstats) AQ_TRY(aq_cis_colstats(h, b));
+  if (W > 0) tile(W, aq_cis_scan_args(h, b));
+  hipLaunchKernelGGL(aq_k_cis_best, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, b.part_r.get(), b.part_s.get(), b.first_item.get(),
+                     b.order.get(), qa, q, b.best_s.get(), b.best_r.get());
+  AQ_HIP(hipGetLastError());
   return AQ_OK;
 }
 

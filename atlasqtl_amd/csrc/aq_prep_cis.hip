@@ -4,8 +4,9 @@
 // same statistic on permuted responses and returns each trait's largest in-window r^2 per permutation; aq_prep_cis_time times
 // the kernels alone, aq_cis_plan_query runs the planner on the host.  The kernels are plain HIP that issues no hand-written
 // load: the ISA proof of the look-ahead sweep units does not cover them and need not.
-#include "aq_cis_host.h"      // AqCisBuf, aq_cis_setup, aq_cis_*_args, aq_cis_colstats, aq_cis_launch_tile, aq_cis_copy_scan,
-                              // aq_cis_need_windows; aq_screen_host.h, aq_prep.h, aq_cis_kernels.h
+#include "aq_cis_host.h"      // AqCisBuf, aq_cis_setup, aq_cis_*_args, aq_cis_colstats, aq_cis_launch_scan, aq_cis_launch_tile,
+                              // aq_cis_upload_time_cut, aq_cis_copy_scan, aq_cis_need_windows; aq_screen_host.h, aq_prep.h,
+                              // aq_cis_kernels.h
 #include "aq_msperm_plan.h"   // aq_msperm_check_rows (the plan header alone: aq_msperm_kernels.h defines a non-static kernel)
 
 extern "C" int aq_cis_plan_query(int32_t n, int32_t p1, int32_t q, int32_t masked, int32_t ncu, const int32_t *s_lo, const int32_t *s_hi,
@@ -18,26 +19,18 @@ extern "C" int aq_cis_plan_query(int32_t n, int32_t p1, int32_t q, int32_t maske
   return rc == AQ_OK ? AQ_OK : aq_fail(rc, err);
 }
 
-// every kernel of one scan after aq_cis_setup.  Asynchronous.
-static int aq_cis_launch_scan(aq_prep *h, AqCisBuf &b) {
-  const int q = h->q, qa = b.wk.q_active;
-  const unsigned W = (unsigned)b.pl.n_items;
-  AQ_HIP(hipMemsetAsync(b.counter.get(), 0, sizeof(unsigned long long), 0));
-  AQ_HIP(hipMemsetAsync(b.undef.get(), 0, (size_t)q * sizeof(unsigned long long), 0));
-  AQ_TRY(aq_cis_colstats(h, b));
-  if (W > 0) {
+// every kernel of one scan after aq_cis_setup: the launch sequence of aq_cis_host.h around the gather of the ordered copy of
+// Y and the plain tile kernel.  Asynchronous.
+static int aq_cis_launch_plain(aq_prep *h, AqCisBuf &b) {
+  return aq_cis_launch_scan(h, b, true, [&](unsigned W, const aq_cis_args &a) {
+    const int qa = b.wk.q_active;
     hipLaunchKernelGGL(aq_k_ms_gather, dim3((unsigned)(qa < (1 << 20) ? qa : (1 << 20))), dim3(256), 0, 0, h->Yc.get(),
                        (const int32_t *)b.order.get(), (const int32_t *)nullptr, h->n, qa, 1, b.Yo.get());
-    const aq_cis_args a = aq_cis_scan_args(h, b);
     if (b.pl.masked)
       aq_cis_launch_tile<true>(W, a);
     else
       aq_cis_launch_tile<false>(W, a);
-  }
-  hipLaunchKernelGGL(aq_k_cis_best, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, b.part_r.get(), b.part_s.get(), b.first_item.get(),
-                     b.order.get(), qa, q, b.best_s.get(), b.best_r.get());
-  AQ_HIP(hipGetLastError());
-  return AQ_OK;
+  });
 }
 
 template <bool MASKED, int PB>
@@ -95,7 +88,7 @@ extern "C" int aq_prep_cis(aq_prep_handle h, const int32_t *s_lo, const int32_t 
   AqCisBuf b;
   AQ_TRY(aq_cis_setup(h, s_lo, s_hi, r2_cut, cap, true, 0, "aq_prep_cis", &b));
   if (plan_out) *plan_out = b.pl;
-  AQ_TRY(aq_cis_launch_scan(h, b));
+  AQ_TRY(aq_cis_launch_plain(h, b));
   return aq_cis_copy_scan(h, b, snp, trait, r, n_pairs, best_snp, best_r, n_undef);
 }
 
@@ -141,13 +134,8 @@ extern "C" int aq_prep_cis_time(aq_prep_handle h, const int32_t *s_lo, const int
   AqCisBuf b;
   AQ_TRY(aq_cis_setup(h, s_lo, s_hi, nullptr, 0, true, n_perm, "aq_prep_cis_time", &b));
   if (plan_out) *plan_out = b.pl;
-  {
-    const size_t qa = (size_t)b.wk.q_active;
-    std::vector<double> cut(qa);
-    for (size_t j = 0; j < qa; j++) cut[j] = aq_screen_time_cut(b.mt_host[j] - 2 - h->n_cov);
-    if (qa > 0) AQ_HIP(hipMemcpy(b.cut.get(), cut.data(), qa * sizeof(double), hipMemcpyHostToDevice));
-  }
-  AQ_TRY(aq_time_launches(reps, ms_scan, [&] { return aq_cis_launch_scan(h, b); }));
+  AQ_TRY(aq_cis_upload_time_cut(b, [&](size_t j) { return b.mt_host[j] - 2 - h->n_cov; }));
+  AQ_TRY(aq_time_launches(reps, ms_scan, [&] { return aq_cis_launch_plain(h, b); }));
   *ms_per_perm = 0.0;
   if (n_perm > 0) {
     const std::vector<int32_t> perm = aq_screen_time_perms((size_t)b.pl.batch, n);

@@ -3,8 +3,8 @@
 // out of both (aq_ciscond_kernels.h; plan by aq_ciscond_plan.h on top of aq_cis_plan.h) and returns what aq_prep_cis returns,
 // and k_eff; aq_prep_cis_cond_time times the kernels alone, aq_ciscond_plan_query runs the planner on the host.  The kernels
 // are plain HIP that issues no hand-written load: the ISA proof of the look-ahead sweep units does not cover them and need not.
-#include "aq_cis_host.h"          // AqCisBuf, aq_cis_setup, aq_cis_scan_args, aq_cis_colstats, aq_cis_launch_tile, aq_cis_copy_scan,
-                                  // aq_cis_need_windows; aq_screen_host.h
+#include "aq_cis_host.h"          // AqCisBuf, aq_cis_setup_complete, aq_cis_keep_syy, aq_cis_launch_scan, aq_cis_launch_tile,
+                                  // aq_cis_upload_time_cut, aq_cis_copy_scan, aq_cis_need_windows; aq_screen_host.h
 #include "aq_ciscond_kernels.h"   // aq_k_cc_basis, aq_k_cc_tile; aq_ciscond_make_plan, aq_ciscond_check_lists
 
 extern "C" int aq_ciscond_plan_query(int32_t n, int32_t p1, int32_t q, int32_t ncu, const int32_t *s_lo, const int32_t *s_hi,
@@ -37,13 +37,11 @@ static int aq_cc_check(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, con
   return aq_cis_need_windows(h, s_lo, s_hi, who);
 }
 
-// the scan's set-up of aq_cis_host.h, the refusal of a handle with missing values, the plan, and the lists in the order
+// the complete-Y set-up of aq_cis_host.h, the plan, and the lists in the order
 static int aq_cc_setup(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, const int32_t *cond_ptr, const int32_t *cond_idx,
                        const double *r2_cut, int64_t cap, const char *who, AqCcBuf *cb) {
   AqCisBuf &b = cb->b;
-  AQ_TRY(aq_cis_setup(h, s_lo, s_hi, r2_cut, cap, true, 0, who, &b));
-  if (b.pl.masked)
-    return aq_fail(AQ_ERR_UNSUPPORTED, std::string(who) + ": Y has missing values; the conditional scan takes complete Y only");
+  AQ_TRY(aq_cis_setup_complete(h, s_lo, s_hi, r2_cut, cap, who, "conditional", &b));
   std::string err;
   // the cis plan inside is the same pure function of the same arguments as b.pl, and its order and work list are b.wk
   const int rc = aq_ciscond_make_plan(h->n, h->p_kept, h->q, b.ncu, s_lo, s_hi, cond_ptr, cond_idx, who, &cb->pl, nullptr, &err);
@@ -59,13 +57,10 @@ static int aq_cc_setup(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, con
   AQ_TRY(aq_cis_upload(&cb->ck, ck));
   AQ_TRY(aq_cis_upload(&cb->cidx, cidx));
   AQ_TRY(cb->Qo.alloc(kc > 0 && qa > 0 ? (size_t)kc * qa * n : 1));
-  AQ_TRY(cb->syy0.alloc(qa > 0 ? qa : 1));
   AQ_TRY(cb->keff_o.alloc(qa > 0 ? qa : 1));
   AQ_TRY(cb->keff_t.alloc(q));
   AQ_TRY(cb->tile_k.alloc(b.pl.trait_tiles > 0 ? (size_t)b.pl.trait_tiles : 1));
-  // b.syy holds Syy_t per ordered trait; the basis kernel overwrites it with S~yy_t, so the trait's own goes to syy0 first
-  if (qa > 0) AQ_HIP(hipMemcpy(cb->syy0.get(), b.syy.get(), qa * sizeof(double), hipMemcpyDeviceToDevice));
-  return AQ_OK;
+  return aq_cis_keep_syy(b, &cb->syy0);     // the basis kernel overwrites b.syy with S~yy_t
 }
 
 // the basis kernel, then the largest k_eff per trait tile: one small copy back, the tile kernel's grid does not depend on it
@@ -98,18 +93,13 @@ static void aq_cc_launch_tile(unsigned grid, const aq_cc_args &ca) {
   aq_screen_a16(ca.c.n, [&](auto a16) { hipLaunchKernelGGL((aq_k_cc_tile<KC, decltype(a16)::value>), dim3(grid), dim3(256), 0, 0, ca); });
 }
 
-// the kernels of one scan after the basis: the column sums, the tile kernel of the plan's KC (the plain scan's for KC = 0,
-// on the copies of y that the basis kernel made), the reduction of the bests.  Asynchronous.
+// the kernels of one scan after the basis, in the launch sequence of aq_cis_host.h: the column sums, the tile kernel of the
+// plan's KC (the plain scan's for KC = 0, on the copies of y that the basis kernel made), the reduction of the bests.
+// Asynchronous.
 static int aq_cc_launch_scan(aq_prep *h, AqCcBuf &cb) {
-  AqCisBuf &b = cb.b;
-  const int q = h->q, qa = b.wk.q_active;
-  const unsigned W = (unsigned)b.pl.n_items;
-  AQ_HIP(hipMemsetAsync(b.counter.get(), 0, sizeof(unsigned long long), 0));
-  AQ_HIP(hipMemsetAsync(b.undef.get(), 0, (size_t)q * sizeof(unsigned long long), 0));
-  AQ_TRY(aq_cis_colstats(h, b));
-  if (W > 0) {
+  return aq_cis_launch_scan(h, cb.b, true, [&](unsigned W, const aq_cis_args &a) {
     aq_cc_args ca{};
-    ca.c = aq_cis_scan_args(h, b);
+    ca.c = a;
     ca.Qo = cb.Qo.get(); ca.syy0 = cb.syy0.get(); ca.keff = cb.keff_o.get(); ca.tile_k = cb.tile_k.get();
     switch (cb.pl.kc) {
       case 0: aq_cis_launch_tile<false>(W, ca.c); break;   // no list: S~yy = Syy and k_eff = 0 everywhere, the plain scan's kernel
@@ -117,11 +107,7 @@ static int aq_cc_launch_scan(aq_prep *h, AqCcBuf &cb) {
       case 2: aq_cc_launch_tile<2>(W, ca); break;
       default: aq_cc_launch_tile<4>(W, ca); break;
     }
-  }
-  hipLaunchKernelGGL(aq_k_cis_best, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, b.part_r.get(), b.part_s.get(), b.first_item.get(),
-                     b.order.get(), qa, q, b.best_s.get(), b.best_r.get());
-  AQ_HIP(hipGetLastError());
-  return AQ_OK;
+  });
 }
 
 extern "C" int aq_prep_cis_cond(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, const int32_t *cond_ptr, const int32_t *cond_idx,
@@ -164,10 +150,8 @@ extern "C" int aq_prep_cis_cond_time(aq_prep_handle h, const int32_t *s_lo, cons
     AqCisBuf &b = cb.b;
     const size_t qa = (size_t)b.wk.q_active;
     std::vector<int32_t> keff(qa);
-    std::vector<double> cut(qa);
     if (qa > 0) AQ_HIP(hipMemcpy(keff.data(), cb.keff_o.get(), qa * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (size_t j = 0; j < qa; j++) cut[j] = aq_screen_time_cut(h->n - 2 - h->n_cov - keff[j]);
-    if (qa > 0) AQ_HIP(hipMemcpy(b.cut.get(), cut.data(), qa * sizeof(double), hipMemcpyHostToDevice));
+    AQ_TRY(aq_cis_upload_time_cut(b, [&](size_t j) { return h->n - 2 - h->n_cov - keff[j]; }));
   }
   AQ_TRY(aq_time_launches(reps, ms_scan, [&] { return aq_cc_launch_scan(h, cb); }));
   return AQ_OK;

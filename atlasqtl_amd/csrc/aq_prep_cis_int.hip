@@ -3,7 +3,8 @@
 // (aq_cisint_kernels.h; plan by aq_cisint_plan.h on top of aq_cis_plan.h) and returns what aq_prep_cis returns, and int_tol;
 // aq_prep_cis_int_time times the kernels alone, aq_cisint_plan_query runs the planner on the host.  The kernels are plain HIP
 // that issues no hand-written load: the ISA proof of the look-ahead sweep units does not cover them and need not.
-#include "aq_cis_host.h"          // AqCisBuf, aq_cis_setup, aq_cis_scan_args, aq_cis_copy_scan, aq_cis_need_windows; aq_screen_host.h
+#include "aq_cis_host.h"          // AqCisBuf, aq_cis_setup_complete, aq_cis_keep_syy, aq_cis_launch_scan, aq_cis_upload_time_cut,
+                                  // aq_cis_copy_scan, aq_cis_need_windows; aq_screen_host.h
 #include "aq_cisint_kernels.h"    // aq_k_ci_traits, aq_k_ci_predstats, aq_k_ci_tile; aq_cisint_make_plan, aq_cisint_check_basis
 
 extern "C" int aq_cisint_plan_query(int32_t n, int32_t p1, int32_t q, int32_t ncu, const int32_t *s_lo, const int32_t *s_hi, int32_t n_basis,
@@ -34,21 +35,18 @@ static int aq_ci_check(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, con
   return aq_cis_need_windows(h, s_lo, s_hi, who);
 }
 
-// the scan's set-up of aq_cis_host.h, the refusal of a handle with missing values, the plan, the basis and the multiplier
+// the complete-Y set-up of aq_cis_host.h, the plan, the basis and the multiplier
 static int aq_ci_setup(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, const double *basis, int n_basis, const double *mult,
                        const double *r2_cut, int64_t cap, const char *who, AqCiBuf *cb) {
   AqCisBuf &b = cb->b;
-  AQ_TRY(aq_cis_setup(h, s_lo, s_hi, r2_cut, cap, true, 0, who, &b));
-  if (b.pl.masked)
-    return aq_fail(AQ_ERR_UNSUPPORTED, std::string(who) + ": Y has missing values; the interaction scan takes complete Y only");
+  AQ_TRY(aq_cis_setup_complete(h, s_lo, s_hi, r2_cut, cap, who, "interaction", &b));
   std::string err;
   // the cis plan inside is the same pure function of the same arguments as b.pl, and its order and work list are b.wk
   const int rc = aq_cisint_make_plan(h->n, h->p_kept, h->q, b.ncu, s_lo, s_hi, n_basis, who, &cb->pl, nullptr, &err);
   if (rc != AQ_OK) return aq_fail(rc, err);
-  const size_t qa = (size_t)b.wk.q_active, n = (size_t)h->n, p1 = (size_t)h->p_kept, npad = (size_t)cb->pl.mult_pad;
+  const size_t n = (size_t)h->n, p1 = (size_t)h->p_kept, npad = (size_t)cb->pl.mult_pad;
   AQ_TRY(cb->B.alloc((size_t)n_basis * n));
   AQ_TRY(cb->mpad.alloc(npad));
-  AQ_TRY(cb->syy0.alloc(qa > 0 ? qa : 1));
   AQ_TRY(cb->vg.alloc(p1));
   AQ_TRY(cb->cgv.alloc(p1));
   AQ_TRY(cb->vw.alloc(p1));
@@ -57,9 +55,7 @@ static int aq_ci_setup(aq_prep *h, const int32_t *s_lo, const int32_t *s_hi, con
   AQ_HIP(hipMemcpy(cb->B.get(), basis, (size_t)n_basis * n * sizeof(double), hipMemcpyHostToDevice));
   AQ_HIP(hipMemset(cb->mpad.get(), 0, npad * sizeof(double)));
   AQ_HIP(hipMemcpy(cb->mpad.get(), mult, n * sizeof(double), hipMemcpyHostToDevice));
-  // b.syy holds Syy_t per ordered trait; the trait kernel overwrites it with S'yy_t, so the trait's own goes to syy0 first
-  if (qa > 0) AQ_HIP(hipMemcpy(cb->syy0.get(), b.syy.get(), qa * sizeof(double), hipMemcpyDeviceToDevice));
-  return AQ_OK;
+  return aq_cis_keep_syy(b, &cb->syy0);     // the trait kernel overwrites b.syy with S'yy_t
 }
 
 // the per-predictor statistics and the residual traits.  Asynchronous.
@@ -75,24 +71,16 @@ static int aq_ci_launch_stats(aq_prep *h, AqCiBuf &cb) {
   return AQ_OK;
 }
 
-// the kernels of one scan after the statistics: the tile kernel and the reduction of the bests.  Asynchronous.
+// the kernels of one scan after the statistics, in the launch sequence of aq_cis_host.h without the column sums: the tile
+// kernel and the reduction of the bests.  Asynchronous.
 static int aq_ci_launch_scan(aq_prep *h, AqCiBuf &cb) {
-  AqCisBuf &b = cb.b;
-  const int q = h->q, qa = b.wk.q_active;
-  const unsigned W = (unsigned)b.pl.n_items;
-  AQ_HIP(hipMemsetAsync(b.counter.get(), 0, sizeof(unsigned long long), 0));
-  AQ_HIP(hipMemsetAsync(b.undef.get(), 0, (size_t)q * sizeof(unsigned long long), 0));
-  if (W > 0) {
+  return aq_cis_launch_scan(h, cb.b, false, [&](unsigned W, const aq_cis_args &a) {
     aq_ci_args ca{};
-    ca.c = aq_cis_scan_args(h, b);
+    ca.c = a;
     ca.mpad = cb.mpad.get(); ca.syy0 = cb.syy0.get(); ca.vg = cb.vg.get(); ca.cgv = cb.cgv.get(); ca.vw = cb.vw.get();
     ca.pok = cb.pok.get(); ca.nb = cb.pl.n_basis;
     aq_screen_a16(h->n, [&](auto a16) { hipLaunchKernelGGL((aq_k_ci_tile<decltype(a16)::value>), dim3(W), dim3(256), 0, 0, ca); });
-  }
-  hipLaunchKernelGGL(aq_k_cis_best, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, 0, b.part_r.get(), b.part_s.get(), b.first_item.get(),
-                     b.order.get(), qa, q, b.best_s.get(), b.best_r.get());
-  AQ_HIP(hipGetLastError());
-  return AQ_OK;
+  });
 }
 
 extern "C" int aq_prep_cis_int(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, const double *basis, int32_t n_basis,
@@ -130,12 +118,7 @@ extern "C" int aq_prep_cis_int_time(aq_prep_handle h, const int32_t *s_lo, const
   AqCiBuf cb;
   AQ_TRY(aq_ci_setup(h, s_lo, s_hi, basis, n_basis, mult, nullptr, 0, "aq_prep_cis_int_time", &cb));
   if (plan_out) *plan_out = cb.pl;
-  {
-    AqCisBuf &b = cb.b;
-    const size_t qa = (size_t)b.wk.q_active;
-    const std::vector<double> cut(qa, aq_screen_time_cut(h->n - n_basis - 2));
-    if (qa > 0) AQ_HIP(hipMemcpy(b.cut.get(), cut.data(), qa * sizeof(double), hipMemcpyHostToDevice));
-  }
+  AQ_TRY(aq_cis_upload_time_cut(cb.b, [&](size_t) { return h->n - n_basis - 2; }));
   AQ_TRY(aq_time_launches(reps, ms_stats, [&] { return aq_ci_launch_stats(h, cb); }));
   AQ_TRY(aq_time_launches(reps, ms_scan, [&] { return aq_ci_launch_scan(h, cb); }));
   return AQ_OK;

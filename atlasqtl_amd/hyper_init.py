@@ -13,8 +13,7 @@ from __future__ import annotations
 import numpy as np
 from scipy import optimize, special, stats
 
-from .prepare import (AtlasqtlError, check_matrix_, check_natural_, check_positive_, check_vector_,
-                      check_zero_one_)
+from .checks import AtlasqtlError, check_matrix_, check_natural_, check_positive_, check_vector_, check_zero_one_
 
 
 class ListHyper(dict):

@@ -22,15 +22,12 @@ from __future__ import annotations
 
 import numpy as np
 
-from .prepare import AtlasqtlError, _is_whole, prepare_data_
+from .checks import AtlasqtlError, _is_real, _is_whole
+from .prepare import prepare_data_
 
 DENSE_MAX = 1 << 27           # entries of the dense r that dense=True returns (1 GiB of fp64)
 INITIAL_CAP = 1 << 16         # rows of the first call's table; a second call with cap = n_pairs follows when they do not suffice
 SCREEN_KEYS = ("p_value", "fdr", "max_pairs")
-
-
-def _is_level(x):
-    return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, np.bool_)) and 0.0 < float(x) <= 1.0
 
 
 def screen_options(p_value=None, fdr=None, max_pairs=None, dense=False, p=None, q=None):
@@ -41,7 +38,7 @@ def screen_options(p_value=None, fdr=None, max_pairs=None, dense=False, p=None, 
     if p_value is not None and fdr is not None:
         raise AtlasqtlError("marginal_screen: at most one of p_value and fdr may be given.")
     for name, v in (("p_value", p_value), ("fdr", fdr)):
-        if v is not None and not _is_level(v):
+        if v is not None and not _is_real(v, 0.0, 1.0, lo_open=True):
             raise AtlasqtlError(f"marginal_screen: {name} must be a number in (0, 1], not {v!r}.")
     if max_pairs is not None and (not _is_whole(max_pairs) or int(max_pairs) < 1):
         raise AtlasqtlError(f"marginal_screen: max_pairs must be None or a whole number >= 1, not {max_pairs!r}.")
@@ -167,6 +164,18 @@ def permutation_options(permutations, n=None):
     return dict(n=int(perms.shape[0]), seed=None, perms=perms)
 
 
+def permutation_trait_pvalue(max_r2, best_snp, best_r):
+    """(1 + #{b: max_r2[b][t] >= best_r[t]^2}) / (B + 1) per trait, from max_r2 (B x q) and the observed best_snp, best_r (q):
+    the permutation p-value of the trait's best predictor; NaN where the trait has no defined pair (best_snp[t] < 0)."""
+    max_r2 = np.asarray(max_r2, dtype=np.float64)
+    best_r = np.asarray(best_r, dtype=np.float64)
+    has = np.asarray(best_snp) >= 0
+    obs = np.where(has, best_r * best_r, np.inf)
+    trait_p = (1.0 + np.sum(max_r2 >= obs[None, :], axis=0)) / (max_r2.shape[0] + 1.0)
+    trait_p[~has] = np.nan
+    return trait_p
+
+
 def permutation_summary(max_r2, hs_max, n_sel, best_snp, best_r, rs_thres, nb_pairwise):
     """What the permutation nulls say about a screen, in numpy.  max_r2 (B x q), hs_max (B), n_sel (B): the outputs of
     PreparedData.marginal_permute; best_snp, best_r (q), rs_thres (p), nb_pairwise: of the screen.  Returns dict of
@@ -175,19 +184,39 @@ def permutation_summary(max_r2, hs_max, n_sel, best_snp, best_r, rs_thres, nb_pa
       hotspot_pvalue[s] = (1 + #{b: hs_max[b] >= rs_thres[s]}) / (B + 1): of a hotspot of that size anywhere among the
         predictors (1 for a predictor without a selected trait);
       expected_null_pairs = mean(n_sel); empirical_fdr = min(1, expected_null_pairs / max(1, nb_pairwise))."""
-    max_r2 = np.asarray(max_r2, dtype=np.float64)
     hs_max = np.asarray(hs_max, dtype=np.int64)
-    B = max_r2.shape[0]
-    best_r = np.asarray(best_r, dtype=np.float64)
-    has = np.asarray(best_snp) >= 0
-    obs = np.where(has, best_r * best_r, np.inf)
-    trait_p = (1.0 + np.sum(max_r2 >= obs[None, :], axis=0)) / (B + 1.0)
-    trait_p[~has] = np.nan
+    B = np.shape(max_r2)[0]
     rs = np.asarray(rs_thres, dtype=np.int64)
     hot_p = (1.0 + (B - np.searchsorted(np.sort(hs_max), rs, side="left"))) / (B + 1.0)      # #{b: hs_max[b] >= rs[s]}
     expected = float(np.mean(np.asarray(n_sel, dtype=np.float64)))
-    return dict(trait_pvalue=trait_p, hotspot_pvalue=hot_p, expected_null_pairs=expected,
+    return dict(trait_pvalue=permutation_trait_pvalue(max_r2, best_snp, best_r), hotspot_pvalue=hot_p, expected_null_pairs=expected,
                 empirical_fdr=min(1.0, expected / max(1, int(nb_pairwise))))
+
+
+def association_table_(out, df, n_tests, mode, level, max_pairs, names_x, names_y, p):
+    """What the host makes of the rows a scan returned (out: snp, trait, r, best_snp, best_r; df: per trait): t, p-value and
+    Benjamini-Hochberg q-value over n_tests tests per row, the rows in table_order, in the mode "fdr" cut to q <= level, and
+    `assoc`, the table cut to max_pairs rows with n_pairs the size of the complete one; best_pvalue per trait (NaN where
+    best_snp < 0).  Returns (assoc, best_pvalue, snp, pvalue), the last two of the complete table."""
+    snp, trait, r = out["snp"], out["trait"], out["r"]
+    dfr = df[trait].astype(np.float64)
+    t, pv = t_and_pvalue(r, dfr)
+    order = table_order(pv, t, snp, trait, p)
+    snp, trait, r, t, pv, dfr = snp[order], trait[order], r[order], t[order], pv[order], dfr[order]
+    qv = bh_qvalues(pv, n_tests)
+    if mode == "fdr":                                         # the device selected p <= alpha, a superset of the BH set
+        keep = int(np.sum(qv <= level))                       # q is non-decreasing along the table
+        snp, trait, r, t, pv, dfr, qv = (a[:keep] for a in (snp, trait, r, t, pv, dfr, qv))
+    n_pairs = int(snp.size)
+    m = n_pairs if max_pairs is None else min(n_pairs, max_pairs)
+    assoc = dict(snp=snp[:m], trait=trait[:m], r=r[:m], t=t[:m], df=dfr[:m].astype(np.int64), pvalue=pv[:m], qvalue=qv[:m],
+                 snp_name=np.asarray(names_x, dtype=object)[snp[:m]], trait_name=np.asarray(names_y, dtype=object)[trait[:m]],
+                 n_pairs=n_pairs)
+    best_snp, best_r = out["best_snp"], out["best_r"]
+    best_p = np.full(best_snp.shape[0], np.nan)
+    has = best_snp >= 0
+    best_p[has] = t_and_pvalue(best_r[has], df[has])[1]
+    return assoc, best_p, snp, pv
 
 
 def screen_handle(prep, names_x, names_y, p_value=None, fdr=None, max_pairs=None, dense=False, permutations=None):
@@ -204,27 +233,12 @@ def screen_handle(prep, names_x, names_y, p_value=None, fdr=None, max_pairs=None
     out = prep.marginal(cut, cap, dense=o["dense"])
     if out["n_pairs"] > cap:                                  # the complete set, whatever order the first call filled its rows in
         out = prep.marginal(cut, out["n_pairs"], dense=o["dense"])
-    snp, trait, r = out["snp"], out["trait"], out["r"]
-    dfr = df[trait].astype(np.float64)
-    t, pv = t_and_pvalue(r, dfr)
-    order = table_order(pv, t, snp, trait, p)
-    snp, trait, r, t, pv, dfr = snp[order], trait[order], r[order], t[order], pv[order], dfr[order]
     n_tests = p * q - int(out["n_undefined"])
-    qv = bh_qvalues(pv, n_tests)
+    assoc, best_p, snp, pv = association_table_(out, df, n_tests, o["mode"], o["level"], o["max_pairs"], names_x, names_y, p)
+    n_pairs, best_snp, best_r = assoc["n_pairs"], out["best_snp"], out["best_r"]
     rs = np.asarray(out["rs"], dtype=np.int64)
-    if o["mode"] == "fdr":                                    # the device selected p <= alpha, a superset of the BH set
-        keep = int(np.sum(qv <= o["level"]))                  # q is non-decreasing along the table
-        snp, trait, r, t, pv, dfr, qv = (a[:keep] for a in (snp, trait, r, t, pv, dfr, qv))
+    if o["mode"] == "fdr":                                    # the Benjamini-Hochberg cut dropped rows the device had counted
         rs = np.bincount(snp, minlength=p).astype(np.int64)
-    n_pairs = int(snp.size)
-    m = n_pairs if o["max_pairs"] is None else min(n_pairs, o["max_pairs"])
-    assoc = dict(snp=snp[:m], trait=trait[:m], r=r[:m], t=t[:m], df=dfr[:m].astype(np.int64), pvalue=pv[:m], qvalue=qv[:m],
-                 snp_name=np.asarray(names_x, dtype=object)[snp[:m]], trait_name=np.asarray(names_y, dtype=object)[trait[:m]],
-                 n_pairs=n_pairs)
-    best_snp, best_r = out["best_snp"], out["best_r"]
-    best_p = np.full(q, np.nan)
-    has = best_snp >= 0
-    best_p[has] = t_and_pvalue(best_r[has], df[has])[1]
     res = AtlasqtlResult(assoc=assoc, rs_thres=rs, nb_pairwise=n_pairs, best_snp=best_snp, best_r=best_r, best_pvalue=best_p,
                          n_obs=n_obs, df=df, n_undefined=int(out["n_undefined"]), n=int(prep.n), p=p, q=q,
                          threshold=dict(mode=o["mode"], level=o["level"], r2_cut=cut, n_tests=n_tests),
@@ -244,6 +258,22 @@ def screen_handle(prep, names_x, names_y, p_value=None, fdr=None, max_pairs=None
         res["permutation"] = dict(n=po["n"], seed=po["seed"], max_r2=nul["max_r2"], hotspot_max=nul["hs_max"], n_selected=nul["n_sel"],
                                   n_undefined=nul["n_undef"], r2_cut=null_cut,
                                   **permutation_summary(nul["max_r2"], nul["hs_max"], nul["n_sel"], best_snp, best_r, rs, n_pairs))
+    return res
+
+
+def on_prepared_(prepare, body, Y, X, device, covariates, ld_prune, transform_y):
+    """What marginal_screen(), cis_screen() and cis_independent() do around their scan: prepare (the caller's prepare_data_,
+    passed in so that the name in the caller's module is what runs: tests replace cis.prepare_data_), run body(prep, dat) on
+    the handle, close it whatever happens, attach the preparation's rmvd_* fields and n_covariates."""
+    dat = prepare(Y, X, 0.1, 1, None, 0, None, None, device=device, covariates=covariates, ld_prune=ld_prune, transform_y=transform_y)
+    prep = dat["X"]
+    try:
+        res = body(prep, dat)
+    finally:
+        prep.close()
+    for key in ("rmvd_cst_x", "rmvd_coll_x", "rmvd_cov_x", "rmvd_ld_x"):
+        res[key] = dat[key]
+    res["n_covariates"] = dat["n_covariates"]
     return res
 
 
@@ -292,14 +322,6 @@ def marginal_screen(Y, X, p_value=None, fdr=None, max_pairs=None, covariates=Non
     residualised on the unpermuted rows; df keeps its covariate count."""
     screen_options(p_value, fdr, max_pairs, dense)             # before the first device call
     permutation_options(permutations)
-    dat = prepare_data_(Y, X, 0.1, 1, None, 0, None, None, device=device, covariates=covariates, ld_prune=ld_prune,
-                        transform_y=transform_y)
-    prep = dat["X"]
-    try:
-        res = screen_handle(prep, dat["names_x"], dat["names_y"], p_value, fdr, max_pairs, dense, permutations)
-    finally:
-        prep.close()
-    for key in ("rmvd_cst_x", "rmvd_coll_x", "rmvd_cov_x", "rmvd_ld_x"):
-        res[key] = dat[key]
-    res["n_covariates"] = dat["n_covariates"]
-    return res
+    def body(prep, dat):
+        return screen_handle(prep, dat["names_x"], dat["names_y"], p_value, fdr, max_pairs, dense, permutations)
+    return on_prepared_(prepare_data_, body, Y, X, device, covariates, ld_prune, transform_y)

@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from .prepare import AtlasqtlError
+from .checks import AtlasqtlError
 
 BED_MAGIC = (0x6C, 0x1B)
 

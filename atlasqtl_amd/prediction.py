@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .prepare import AtlasqtlError
+from .checks import AtlasqtlError
 
 # most rows of one library call (aq_vb_predict, aq_predict: AQ_N_MAX); longer matrices are looped over in batches of this many
 PREDICT_MAX_ROWS = _lib.AQ_N_MAX

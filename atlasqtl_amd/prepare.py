@@ -1,383 +1,27 @@
-"""Host-side pre-processing, mirroring the reference's R checks and data preparation.
-
-Follows R/prepare_atlasqtl.R:8-124 (``prepare_data_``, ``check_verbose_``,
-``check_annealing_``) and R/utils.R:10-100, 276-343 (``check_*_``,
-``rm_constant_``, ``rm_collinear_``).  Error messages keep the reference's
-wording so tests read like the reference's own.  The argument checks run on the host;
-the O(n p) work itself -- scale(X), the removal of constant and duplicated columns,
-the centring of Y -- runs on the GPU (aq_prepare_data) and X stays there: one call of aq_prepare_data_opt, the
-five aq_prepare_data* entries in one, whose pipeline is csrc/aq_prepare.hip; the .bed decode, the covariates, the transform of
-Y, LD pruning and the relationship matrix are the csrc/aq_prep_*.hip units.  Covariates, which the reference
-does not take, are regressed out of X and Y there as well (aq_prepare_data_cov), and the compact matrix can be pruned for
-linkage disequilibrium there before the fit (aq_prep_ld_prune).  The genetic relationship matrix of the prepared matrix is
-formed there too (aq_prep_grm); its leading eigenvectors, the genotype principal components, are taken here on the host --
-or, with solver="subspace", by subspace iteration whose operator K Q = Xs (Xs' Q) / p1 runs there (aq_prep_grm_apply) without
-K ever being formed, for any n the fit takes.  The rank-based inverse normal transform of the traits (transform_y=, rank_normalize)
-runs there as well, before everything else that is done to Y (aq_prepare_data_opt, aq_rank_int).
+"""The preparation of the data, mirroring the reference's R/prepare_atlasqtl.R:8-87 (``prepare_data_``) and
+R/utils.R:276-343 (``rm_constant_``, ``rm_collinear_``).  The argument checks (checks.py) run on the host; the O(n p) work
+itself -- scale(X), the removal of constant and duplicated columns, the centring of Y -- runs on the GPU and X
+stays there: one call of aq_prepare_data_opt, the five aq_prepare_data* entries in one, whose pipeline is csrc/aq_prepare.hip;
+the .bed decode, the covariates, the transform of Y and LD pruning are the csrc/aq_prep_*.hip units.  Covariates, which the
+reference does not take, are regressed out of X and Y there as well, and the compact matrix can be pruned for linkage
+disequilibrium there before the fit (aq_prep_ld_prune).  The rank-based inverse normal transform of the traits (transform_y=,
+rank_normalize) runs there too, before everything else that is done to Y (aq_prepare_data_opt, aq_rank_int).  Here: the
+parsers of the options, rank_normalize, prepare_on_device and prepare_data_; the PreparedData they return is prepared.py, the
+genotype GRM / principal components taken from one (genotype_grm, genotype_pcs) stay here, below their rule: their names are
+what callers import from this module.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
+import warnings
 
 import numpy as np
 
 from . import _lib
-
-_EPS75 = np.finfo(np.float64).eps ** 0.75
-
-
-class AtlasqtlError(ValueError):
-    """Raised where the reference calls ``stop()``."""
-
-
-def check_natural_(x, name, eps=_EPS75):                      # R/utils.R:10-15
-    x = np.atleast_1d(np.asarray(x, dtype=np.float64))
-    if np.any((x < eps) | (np.abs(x - np.round(x)) > eps)):
-        raise AtlasqtlError(f"{name} must be natural.")
-
-
-def check_positive_(x, name, eps=_EPS75):                     # R/utils.R:17-24
-    x = np.atleast_1d(np.asarray(x, dtype=np.float64))
-    if np.any(x < eps):
-        msg = f"{name} must be positive, greater than {eps:.3g}."
-        if x.size > 1:
-            msg = "All entries of " + msg
-        raise AtlasqtlError(msg)
-
-
-def check_zero_one_(x, name):                                 # R/utils.R:26-32
-    x = np.asarray(x)
-    if np.any(x < 0) or np.any(x > 1):
-        msg = f"{name} must lie between 0 and 1."
-        if x.size > 1:
-            msg = "All entries of " + msg
-        raise AtlasqtlError(msg)
-
-
-def check_vector_(x, name, size=None, null_ok=False, na_ok=False):
-    """check_structure_(x, "vector", ...) of R/utils.R:34-100 for numeric vectors."""
-    if x is None:
-        if null_ok:
-            return None
-        raise AtlasqtlError(f"{name} must be a non-empty a numeric vector.")
-    a = np.atleast_1d(np.asarray(x, dtype=np.float64))
-    ok = a.ndim == 1 and a.size > 0
-    if size is not None:
-        sizes = size if isinstance(size, (tuple, list)) else (size,)
-        ok = ok and a.size in sizes
-    if not na_ok:
-        ok = ok and not np.any(np.isnan(a))
-    ok = ok and bool(np.all(np.isfinite(a[~np.isnan(a)])))
-    if not ok:
-        raise AtlasqtlError(f"{name} must be a non-empty a numeric vector"
-                            + (f" of length {size}" if size is not None else "")
-                            + ", finite" + ("" if na_ok else " without missing value")
-                            + (" or must be NULL" if null_ok else "") + ".")
-    return a
-
-
-def check_matrix_(x, name, shape=None, na_ok=False):
-    """check_structure_(x, "matrix", ...) of R/utils.R:34-100."""
-    a = np.asarray(x, dtype=np.float64)
-    ok = a.ndim == 2 and a.size > 0
-    if shape is not None:
-        ok = ok and tuple(a.shape) == tuple(shape)
-    if not na_ok:
-        ok = ok and not np.any(np.isnan(a))
-    ok = ok and bool(np.all(np.isfinite(a[~np.isnan(a)])))
-    if not ok:
-        raise AtlasqtlError(f"{name} must be a non-empty a numeric matrix"
-                            + (f" of dimension {shape[0]} x {shape[1]}" if shape is not None else "")
-                            + ", finite" + ("" if na_ok else " without missing value") + ".")
-    return a
-
-
-def check_verbose_(verbose):                                  # R/prepare_atlasqtl.R:90-95
-    if verbose not in (0, 1, 2):
-        raise AtlasqtlError("The verbose argument must be set to 0, 1 or 2.")
-
-
-def check_annealing_(anneal):                                 # R/prepare_atlasqtl.R:100-124
-    if anneal is None:
-        return
-    a = check_vector_(anneal, "anneal", size=3)
-    check_natural_(a[[0, 2]], "anneal[c(1, 3)]")
-    check_positive_(a[1], "anneal[2]")
-    if a[0] not in (1, 2, 3):
-        raise AtlasqtlError("The annealing spacing scheme must be set to 1 for geometric 2 for harmonic or 3 "
-                            "for linear spacing.")
-    if a[1] < 1.5:
-        raise AtlasqtlError("Initial annealing temperature very small. May not be large enough for a "
-                            "successful exploration. Please increase it or select no annealing.")
-    if a[2] > 1000:
-        raise AtlasqtlError("Temperature grid size very large. This may be unnecessarily computationally "
-                            "demanding. Please decrease it.")
-
-
-class PreparedData:
-    """The standardised compact X (n x p) and the centred Y resident on the GPU (aq_prepare_data).  VbRun takes it in place
-    of the X array; `Y` is the host copy of the centred responses (n x q, small) that the hyper-parameter rules need."""
-
-    def __init__(self, handle, n, p, q, Y, device, genotype_counts=None, n_cov=0, cov_absorbed=None, cov_r2=None, y_n_obs=None,
-                 y_n_tied=None):
-        self.handle, self.n, self.p, self.q, self.Y, self.device = handle, n, p, q, Y, device
-        self.shape = (n, p)
-        # LD pruning (prepare_on_device(ld_prune=)), per column given: removed for LD (bool), the index of the kept column that
-        # tags it (-1: none) and its r^2 with that column (NaN: not removed for LD).  None without pruning.
-        self.ld_removed = self.ld_of = self.ld_r2 = None
-        self.genotype_counts = genotype_counts      # 4 x p_given int32 (hom A1, het, hom A2, missing): PlinkBed input only
-        # covariates regressed out of X and Y (0: none); per column given: absorbed by them (bool), and the share of its
-        # variance they explain (NaN for a constant column).  None without covariates.
-        self.n_cov, self.cov_absorbed, self.cov_r2 = n_cov, cov_absorbed, cov_r2
-        # transform_y: per trait, its observed values and those among them that share their value with another one.  None
-        # without the transform.
-        self.y_n_obs, self.y_n_tied = y_n_obs, y_n_tied
-
-    @property
-    def x_ptr(self):
-        return _lib.lib().aq_prep_x_device(self.handle)
-
-    @property
-    def y_ptr(self):
-        return _lib.lib().aq_prep_y_device(self.handle)
-
-    def X_host(self):
-        out = np.empty((self.n, self.p), order="F")
-        _lib.check(_lib.lib().aq_prep_get(self.handle, _lib.as_dp(out), None), "aq_prep_get")
-        return out
-
-    def x_moments(self, p_given):
-        """The column means and n - 1 standard deviations that scale(X) used, per column given (aq_prep_info)."""
-        mean = np.empty(int(p_given)); sd = np.empty(int(p_given))
-        _lib.check(_lib.lib().aq_prep_info(self.handle, None, None, None, None, _lib.as_dp(mean), _lib.as_dp(sd)), "aq_prep_info")
-        return mean, sd
-
-    def ld_band(self, window):
-        """r(j - 1 - b, j) of the matrix as it stands, p x window (NaN where j - 1 - b < 0): aq_prep_ld_band."""
-        out = np.empty((self.p, int(window)), order="F")
-        _lib.check(_lib.lib().aq_prep_ld_band(self.handle, int(window), _lib.as_dp(out)), "aq_prep_ld_band")
-        return out
-
-    def grm(self, return_trace=False):
-        """The genetic relationship matrix Xs Xs' / p of the matrix as it stands, n x n and exactly symmetric: aq_prep_grm.
-        return_trace: also the sum of its diagonal, added in index order."""
-        import ctypes as C
-        out = np.empty((self.n, self.n), order="F")
-        tr = C.c_double(0.0)
-        _lib.check(_lib.lib().aq_prep_grm(self.handle, _lib.as_dp(out), C.byref(tr)), "aq_prep_grm")
-        return (out, float(tr.value)) if return_trace else out
-
-    def grm_apply(self, Q, return_trace=False):
-        """Z = Xs (Xs' Q) / p of the matrix as it stands, n x L for Q n x L (1 <= L <= 128), without the n x n matrix:
-        aq_prep_grm_apply.  return_trace: also the trace of the relationship matrix, (sum of Xs^2) / p."""
-        import ctypes as C
-        Q = np.asfortranarray(Q, dtype=np.float64)
-        if Q.ndim != 2 or Q.shape[0] != self.n:
-            raise AtlasqtlError(f"grm_apply: Q must be n x L with n = {self.n} rows, not {Q.shape}.")
-        out = np.empty(Q.shape, order="F")
-        tr = C.c_double(0.0)
-        _lib.check(_lib.lib().aq_prep_grm_apply(self.handle, _lib.as_dp(Q), Q.shape[1], _lib.as_dp(out),
-                                                C.byref(tr) if return_trace else None), "aq_prep_grm_apply")
-        return (out, float(tr.value)) if return_trace else out
-
-    def marginal(self, r2_cut, cap, dense=False):
-        """The marginal screen of the matrix as it stands against every trait: aq_prep_marginal.  r2_cut: q cutoffs on r^2
-        (trait t selects r^2 >= r2_cut[t]; +inf: none); cap: rows of the table (0 only counts).  Returns dict(snp, trait, r:
-        the min(n_pairs, cap) rows written, in no particular order; n_pairs: the full count; rs: selected traits per
-        predictor (p); best_snp, best_r: per trait, the predictor of largest r^2 (-1 / NaN: none defined); n_undefined;
-        r_dense: p x q with dense=True, else None)."""
-        import ctypes as C
-        cut = np.ascontiguousarray(r2_cut, dtype=np.float64)
-        if cut.shape != (self.q,):
-            raise AtlasqtlError(f"marginal: r2_cut must hold one cutoff per trait ({self.q}), not {cut.shape}.")
-        cap = int(cap)
-        rows = max(cap, 0)
-        snp = np.empty(rows, dtype=np.int32); trait = np.empty(rows, dtype=np.int32); r = np.empty(rows)
-        rs = np.zeros(self.p, dtype=np.int64); best_snp = np.empty(self.q, dtype=np.int32); best_r = np.empty(self.q)
-        n_pairs, n_undef = C.c_int64(0), C.c_int64(0)
-        r_dense = np.empty((self.p, self.q), order="F") if dense else None
-        _lib.check(_lib.lib().aq_prep_marginal(self.handle, _lib.as_dp(cut), cap, _lib.as_ip(snp), _lib.as_ip(trait), _lib.as_dp(r),
-                                               C.byref(n_pairs), rs.ctypes.data_as(C.POINTER(C.c_int64)), _lib.as_ip(best_snp),
-                                               _lib.as_dp(best_r), C.byref(n_undef), None if r_dense is None else _lib.as_dp(r_dense)),
-                   "aq_prep_marginal")
-        k = min(int(n_pairs.value), rows)
-        return dict(snp=snp[:k], trait=trait[:k], r=r[:k], n_pairs=int(n_pairs.value), rs=rs, best_snp=best_snp, best_r=best_r,
-                    n_undefined=int(n_undef.value), r_dense=r_dense)
-
-    def marginal_permute(self, r2_cut, perms):
-        """Permutation nulls of the marginal screen: aq_prep_marginal_perm.  r2_cut: q cutoffs on r^2, as for marginal();
-        perms: B x n integers, every row a permutation of 0 ... n - 1 (row b permutes the sample rows of Y: Y'[i] = Y[perms[b][i]]).
-        Returns dict(max_r2: B x q, the largest defined r^2 of every trait under every permutation (-1.0: none defined);
-        hs_max: B, the largest number of selected traits of one predictor; n_sel: B, selected pairs; n_undef: B)."""
-        import ctypes as C
-        cut = np.ascontiguousarray(r2_cut, dtype=np.float64)
-        if cut.shape != (self.q,):
-            raise AtlasqtlError(f"marginal_permute: r2_cut must hold one cutoff per trait ({self.q}), not {cut.shape}.")
-        perms = np.asarray(perms)
-        if perms.ndim != 2 or perms.shape[0] < 1 or perms.shape[1] != self.n or not np.issubdtype(perms.dtype, np.integer):
-            raise AtlasqtlError(f"marginal_permute: perms must be a B x n integer array with n = {self.n}, not "
-                                f"{perms.dtype} {perms.shape}.")
-        if perms.size and (perms.min() < 0 or perms.max() >= self.n):       # before the cast to int32 can wrap a value
-            raise AtlasqtlError(f"marginal_permute: every row of perms must be a permutation of 0 ... {self.n - 1}.")
-        perms = np.ascontiguousarray(perms, dtype=np.int32)
-        B = perms.shape[0]
-        max_r2 = np.empty((B, self.q))
-        hs, nsel, nundef = (np.zeros(B, dtype=np.int64) for _ in range(3))
-        i64 = C.POINTER(C.c_int64)
-        _lib.check(_lib.lib().aq_prep_marginal_perm(self.handle, _lib.as_dp(cut), B, _lib.as_ip(perms), _lib.as_dp(max_r2),
-                                                    hs.ctypes.data_as(i64), nsel.ctypes.data_as(i64), nundef.ctypes.data_as(i64)),
-                   "aq_prep_marginal_perm")
-        return dict(max_r2=max_r2, hs_max=hs, n_sel=nsel, n_undef=nundef)
-
-    def _cis_windows_arg(self, s_lo, s_hi, who):
-        """The windows as the library takes them: two contiguous int32 vectors of q entries with 0 <= s_lo <= s_hi <= p,
-        checked before the cast to int32 can wrap a value (the library checks them again, and names the trait)."""
-        lo, hi = np.asarray(s_lo), np.asarray(s_hi)
-        for a in (lo, hi):
-            if a.shape != (self.q,) or not np.issubdtype(a.dtype, np.integer):
-                raise AtlasqtlError(f"{who}: s_lo and s_hi must hold one whole number per trait ({self.q}), not {a.dtype} {a.shape}.")
-        if lo.size and (lo.min() < 0 or hi.max() > self.p or np.any(lo > hi)):
-            raise AtlasqtlError(f"{who}: every window must satisfy 0 <= s_lo <= s_hi <= p = {self.p}.")
-        return np.ascontiguousarray(lo, dtype=np.int32), np.ascontiguousarray(hi, dtype=np.int32)
-
-    def cis(self, s_lo, s_hi, r2_cut, cap):
-        """The cis scan of the matrix as it stands: aq_prep_cis.  Trait t is tested against the predictors s_lo[t] <= s <
-        s_hi[t] only.  r2_cut, cap: as for marginal().  Returns dict(snp, trait, r: the min(n_pairs, cap) rows written, in no
-        particular order; n_pairs: the full count; best_snp, best_r: per trait, the in-window predictor of largest r^2 (-1 /
-        NaN: none defined); n_undef: per trait, the undefined pairs inside its window; plan: the dict of aq_cis_plan)."""
-        import ctypes as C
-        lo, hi = self._cis_windows_arg(s_lo, s_hi, "cis")
-        cut = np.ascontiguousarray(r2_cut, dtype=np.float64)
-        if cut.shape != (self.q,):
-            raise AtlasqtlError(f"cis: r2_cut must hold one cutoff per trait ({self.q}), not {cut.shape}.")
-        cap = int(cap)
-        rows = max(cap, 0)
-        snp = np.empty(rows, dtype=np.int32); trait = np.empty(rows, dtype=np.int32); r = np.empty(rows)
-        best_snp = np.empty(self.q, dtype=np.int32); best_r = np.empty(self.q); n_undef = np.zeros(self.q, dtype=np.int64)
-        n_pairs, plan = C.c_int64(0), _lib.AqCisPlan()
-        _lib.check(_lib.lib().aq_prep_cis(self.handle, _lib.as_ip(lo), _lib.as_ip(hi), _lib.as_dp(cut), cap, _lib.as_ip(snp),
-                                          _lib.as_ip(trait), _lib.as_dp(r), C.byref(n_pairs), _lib.as_ip(best_snp), _lib.as_dp(best_r),
-                                          n_undef.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(plan)), "aq_prep_cis")
-        k = min(int(n_pairs.value), rows)
-        return dict(snp=snp[:k], trait=trait[:k], r=r[:k], n_pairs=int(n_pairs.value), best_snp=best_snp, best_r=best_r,
-                    n_undef=n_undef, plan={name: int(getattr(plan, name)) for name, _ in _lib.AqCisPlan._fields_})
-
-    def cis_permute(self, s_lo, s_hi, perms):
-        """Permutation nulls of the cis scan: aq_prep_cis_perm.  perms: B x n integers as for marginal_permute().  Returns
-        max_r2, B x q: the largest defined r^2 of every trait over its window under every permutation (-1.0: none)."""
-        lo, hi = self._cis_windows_arg(s_lo, s_hi, "cis_permute")
-        perms = np.asarray(perms)
-        if perms.ndim != 2 or perms.shape[0] < 1 or perms.shape[1] != self.n or not np.issubdtype(perms.dtype, np.integer):
-            raise AtlasqtlError(f"cis_permute: perms must be a B x n integer array with n = {self.n}, not {perms.dtype} {perms.shape}.")
-        if perms.size and (perms.min() < 0 or perms.max() >= self.n):       # before the cast to int32 can wrap a value
-            raise AtlasqtlError(f"cis_permute: every row of perms must be a permutation of 0 ... {self.n - 1}.")
-        perms = np.ascontiguousarray(perms, dtype=np.int32)
-        B = perms.shape[0]
-        max_r2 = np.empty((B, self.q))
-        _lib.check(_lib.lib().aq_prep_cis_perm(self.handle, _lib.as_ip(lo), _lib.as_ip(hi), B, _lib.as_ip(perms), _lib.as_dp(max_r2)),
-                   "aq_prep_cis_perm")
-        return max_r2
-
-    def _cis_cond_arg(self, cond, who):
-        """The conditioning lists as the library takes them, (cond_ptr [q + 1 offsets], cond_idx), int32 each: `cond` is q lists
-        of at most 4 distinct column indices in [0, p), checked before the cast to int32 can wrap a value."""
-        cond = list(cond)
-        if len(cond) != self.q:
-            raise AtlasqtlError(f"{who}: cond must hold one list per trait ({self.q}), not {len(cond)}.")
-        ptr = np.zeros(self.q + 1, dtype=np.int32)
-        idx = []
-        for t, c in enumerate(cond):
-            a = np.atleast_1d(np.asarray(c))
-            if a.size == 0:
-                a = np.zeros(0, dtype=np.int64)
-            if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
-                raise AtlasqtlError(f"{who}: the conditioning list of trait {t} must hold whole numbers, not {a.dtype} {a.shape}.")
-            if a.size > 4:
-                raise AtlasqtlError(f"{who}: trait {t} conditions on {a.size} variants; at most 4 are supported.")
-            if a.size and (a.min() < 0 or a.max() >= self.p):
-                raise AtlasqtlError(f"{who}: the conditioning list of trait {t} must hold column indices in [0, {self.p}).")
-            if np.unique(a).size != a.size:
-                raise AtlasqtlError(f"{who}: the conditioning list of trait {t} names a variant more than once.")
-            idx += [int(v) for v in a]
-            ptr[t + 1] = len(idx)
-        return ptr, np.ascontiguousarray(idx + [0], dtype=np.int32)      # one spare entry: never an empty buffer
-
-    def cis_conditional(self, s_lo, s_hi, cond, r2_cut, cap):
-        """The conditional cis scan of the matrix as it stands: aq_prep_cis_cond.  s_lo, s_hi, r2_cut, cap: as for cis().
-        cond: q lists, trait t is tested after the columns cond[t] (at most 4 distinct indices, in this order, inside the
-        trait's window or not) have been regressed out of it and of every predictor.  Complete Y only.  Returns the dict of
-        cis() with r the partial correlation, and k_eff: per trait, the columns of its list that were not collinear with the
-        earlier ones (df_t = n - 2 - n_cov - k_eff[t]; 0 for a trait with an empty window); plan: the dict of
-        aq_ciscond_plan, the fields of its aq_cis_plan alongside."""
-        import ctypes as C
-        lo, hi = self._cis_windows_arg(s_lo, s_hi, "cis_conditional")
-        ptr, idx = self._cis_cond_arg(cond, "cis_conditional")
-        cut = np.ascontiguousarray(r2_cut, dtype=np.float64)
-        if cut.shape != (self.q,):
-            raise AtlasqtlError(f"cis_conditional: r2_cut must hold one cutoff per trait ({self.q}), not {cut.shape}.")
-        if np.isnan(self.Y).any():
-            raise AtlasqtlError("cis_conditional: Y has missing values; the conditional scan takes complete Y only.")
-        cap = int(cap)
-        rows = max(cap, 0)
-        snp = np.empty(rows, dtype=np.int32); trait = np.empty(rows, dtype=np.int32); r = np.empty(rows)
-        best_snp = np.empty(self.q, dtype=np.int32); best_r = np.empty(self.q); n_undef = np.zeros(self.q, dtype=np.int64)
-        k_eff = np.zeros(self.q, dtype=np.int32)
-        n_pairs, plan = C.c_int64(0), _lib.AqCiscondPlan()
-        _lib.check(_lib.lib().aq_prep_cis_cond(self.handle, _lib.as_ip(lo), _lib.as_ip(hi), _lib.as_ip(ptr), _lib.as_ip(idx),
-                                               _lib.as_dp(cut), cap, _lib.as_ip(snp), _lib.as_ip(trait), _lib.as_dp(r), C.byref(n_pairs),
-                                               _lib.as_ip(best_snp), _lib.as_dp(best_r), n_undef.ctypes.data_as(C.POINTER(C.c_int64)),
-                                               _lib.as_ip(k_eff), C.byref(plan)), "aq_prep_cis_cond")
-        k = min(int(n_pairs.value), rows)
-        pd = {name: int(getattr(plan.cis, name)) for name, _ in _lib.AqCisPlan._fields_}
-        pd.update({name: int(getattr(plan, name)) for name, _ in _lib.AqCiscondPlan._fields_ if name != "cis"})
-        return dict(snp=snp[:k], trait=trait[:k], r=r[:k], n_pairs=int(n_pairs.value), best_snp=best_snp, best_r=best_r,
-                    n_undef=n_undef, k_eff=k_eff, plan=pd)
-
-    def cis_interaction(self, s_lo, s_hi, basis, mult, r2_cut, cap):
-        """The interaction cis scan of the matrix as it stands: aq_prep_cis_int.  s_lo, s_hi, r2_cut, cap: as for cis().
-        basis: nb x n, orthonormal rows spanning the intercept, the covariates the matrix was prepared with and the interaction
-        variable e (cis.interaction_basis); mult: n, e centred.  Complete Y only.  Returns the dict of cis() with r the partial
-        correlation of the interaction term g o e given [1, Z, e, g] (df = n - nb - 2), and int_tol: per column, the share of
-        g o e that [1, Z, e, g] leave (NaN where the column is undefined for every trait); plan: the dict of aq_cisint_plan,
-        the fields of its aq_cis_plan alongside."""
-        import ctypes as C
-        lo, hi = self._cis_windows_arg(s_lo, s_hi, "cis_interaction")
-        cut = np.ascontiguousarray(r2_cut, dtype=np.float64)
-        if cut.shape != (self.q,):
-            raise AtlasqtlError(f"cis_interaction: r2_cut must hold one cutoff per trait ({self.q}), not {cut.shape}.")
-        B = np.ascontiguousarray(basis, dtype=np.float64)
-        m = np.ascontiguousarray(mult, dtype=np.float64)
-        if B.ndim != 2 or B.shape[0] < 1 or B.shape[1] != self.n or m.shape != (self.n,):
-            raise AtlasqtlError(f"cis_interaction: basis must be nb x n and mult must hold n = {self.n} values, not {B.shape} and "
-                                f"{m.shape}.")
-        if np.isnan(self.Y).any():
-            raise AtlasqtlError("cis_interaction: Y has missing values; the interaction scan takes complete Y only.")
-        cap = int(cap)
-        rows = max(cap, 0)
-        snp = np.empty(rows, dtype=np.int32); trait = np.empty(rows, dtype=np.int32); r = np.empty(rows)
-        best_snp = np.empty(self.q, dtype=np.int32); best_r = np.empty(self.q); n_undef = np.zeros(self.q, dtype=np.int64)
-        int_tol = np.empty(self.p)
-        n_pairs, plan = C.c_int64(0), _lib.AqCisintPlan()
-        _lib.check(_lib.lib().aq_prep_cis_int(self.handle, _lib.as_ip(lo), _lib.as_ip(hi), _lib.as_dp(B), B.shape[0], _lib.as_dp(m),
-                                              _lib.as_dp(cut), cap, _lib.as_ip(snp), _lib.as_ip(trait), _lib.as_dp(r), C.byref(n_pairs),
-                                              _lib.as_ip(best_snp), _lib.as_dp(best_r), n_undef.ctypes.data_as(C.POINTER(C.c_int64)),
-                                              _lib.as_dp(int_tol), C.byref(plan)), "aq_prep_cis_int")
-        k = min(int(n_pairs.value), rows)
-        pd = {name: int(getattr(plan.cis, name)) for name, _ in _lib.AqCisPlan._fields_}
-        pd.update({name: int(getattr(plan, name)) for name, _ in _lib.AqCisintPlan._fields_ if name != "cis"})
-        return dict(snp=snp[:k], trait=trait[:k], r=r[:k], n_pairs=int(n_pairs.value), best_snp=best_snp, best_r=best_r,
-                    n_undef=n_undef, int_tol=int_tol, plan=pd)
-
-    def close(self):
-        if self.handle is not None:
-            _lib.lib().aq_prep_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+from .checks import AtlasqtlError, _is_real, _is_whole, check_matrix_, check_natural_, check_positive_, check_vector_
+from .plink import PlinkBed
+from .prepared import PreparedData, raise_for_code
 
 
 def _covariates_arg(covariates, n):
@@ -405,8 +49,6 @@ PC_SOLVER_DEFAULTS = {"solver": "eigh", "oversample": None, "tol": 1e-8, "max_it
 COV_MAX_D = 96                # AQ_COV_MAX_D: covariates that aq_prepare_data_cov takes
 LD_PRUNE_DEFAULTS = {"r2": 0.8, "window": 500, "window_bp": None, "groups": None, "positions": None}
 LD_MAX_WINDOW = 4096          # AQ_LD_MAX_WINDOW of csrc/aq_ld_kernels.h
-
-
 TRANSFORM_Y_DEFAULTS = {"method": "int", "offset": 0.375}
 
 
@@ -428,7 +70,7 @@ def transform_y_options(transform_y):
 
 
 def _check_int_offset(c, what):
-    if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, float, np.integer, np.floating)) or not (0.0 <= float(c) <= 0.5):
+    if not _is_real(c, 0.0, 0.5):
         raise AtlasqtlError(f"{what}: offset must be a number in [0, 1/2], not {c!r}.")
     return float(c)
 
@@ -460,18 +102,9 @@ def rank_normalize(Y, offset=0.375, device=0):
         raise AtlasqtlError(f"rank_normalize: n = {n} samples given, at most {N_MAX} are supported.")
     out = np.empty((n, q), order="F")
     n_obs = np.zeros(q, dtype=np.int32); n_tied = np.zeros(q, dtype=np.int32)
-    L = _lib.lib()
-    rc = L.aq_rank_int(_lib.as_dp(Ya), n, q, c, _lib.as_dp(out), _lib.as_ip(n_obs), _lib.as_ip(n_tied), int(device))
-    if rc != 0:
-        msg = L.aq_last_error().decode("utf-8", "replace")
-        if rc == 1:
-            raise AtlasqtlError(msg)
-        raise _lib.AtlasqtlHipError(f"aq_rank_int: [{rc}] {msg}")
+    raise_for_code(_lib.lib().aq_rank_int(_lib.as_dp(Ya), n, q, c, _lib.as_dp(out), _lib.as_ip(n_obs), _lib.as_ip(n_tied), int(device)),
+                   "aq_rank_int")
     return dict(Y=out, n_obs=n_obs, n_tied=n_tied)
-
-
-def _is_whole(x):
-    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
 
 
 def ld_prune_options(ld_prune):
@@ -482,7 +115,7 @@ def ld_prune_options(ld_prune):
         raise AtlasqtlError("ld_prune must be None or a dict with keys among 'r2', 'window', 'window_bp', 'groups', 'positions'.")
     o = {**LD_PRUNE_DEFAULTS, **ld_prune}
     r2 = o["r2"]
-    if isinstance(r2, (bool, np.bool_)) or not isinstance(r2, (int, float, np.integer, np.floating)) or not (0.0 < float(r2) <= 1.0):
+    if not _is_real(r2, 0.0, 1.0, lo_open=True):
         raise AtlasqtlError(f"ld_prune: r2 must be a number in (0, 1], not {r2!r}.")
     if not _is_whole(o["window"]) or not (1 <= int(o["window"]) <= LD_MAX_WINDOW):
         raise AtlasqtlError(f"ld_prune: window must be a whole number in [1, {LD_MAX_WINDOW}], not {o['window']!r}.")
@@ -513,8 +146,6 @@ def _ld_arg(ld_prune, X):
     before the first device call."""
     if ld_prune is None:
         return None, None
-    import ctypes as C
-    from .plink import PlinkBed
     o = ld_prune_options(ld_prune)
     p = X.p if isinstance(X, PlinkBed) else (np.shape(X)[1] if np.ndim(X) == 2 else -1)
     groups, positions = o["groups"], o["positions"]
@@ -545,17 +176,14 @@ def _ld_arg(ld_prune, X):
 
 def _ld_prune_handle(ret, ld):
     """aq_prep_ld_prune on the PreparedData of a prepare_on_device return value; fills its ld_* fields."""
-    import ctypes as C
     prep = ret[0]
     L = _lib.lib()
     p = len(ret[1])
-    rc = L.aq_prep_ld_prune(prep.handle, C.byref(ld))
-    if rc != 0:
-        msg = L.aq_last_error().decode("utf-8", "replace")
+    try:
+        raise_for_code(L.aq_prep_ld_prune(prep.handle, C.byref(ld)), "aq_prep_ld_prune")
+    except Exception:
         prep.close()
-        if rc == 1:
-            raise AtlasqtlError(msg)
-        raise _lib.AtlasqtlHipError(f"aq_prep_ld_prune: [{rc}] {msg}")
+        raise
     pk = C.c_int32(0)
     rm = np.zeros(p, dtype=np.uint8); of = np.zeros(p, dtype=np.int32); r2 = np.zeros(p)
     _lib.check(L.aq_prep_ld_info(prep.handle, C.byref(pk), rm.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.as_ip(of), _lib.as_dp(r2)),
@@ -582,8 +210,6 @@ def prepare_on_device(Y, X, device=0, covariates=None, ld_prune=None, transform_
     of every column of Y over its observed rows, before the regression on the covariates or the centring (rank_normalize); the
     PreparedData then carries y_n_obs and y_n_tied.  X is prepared as without it.
     Returns (PreparedData, bool_cst_x [p], bool_coll_x [p, original numbering], dup_of [p])."""
-    import ctypes as C
-    from .plink import PlinkBed
     Y = np.asfortranarray(Y, dtype=np.float64)
     n, q = Y.shape
     cov, Z = _covariates_arg(covariates, n)
@@ -595,8 +221,6 @@ def prepare_on_device(Y, X, device=0, covariates=None, ld_prune=None, transform_
 
 def _prepare_unpruned(Y, X, device, cov, yt=None):
     """prepare_on_device before any pruning: Y float64 in Fortran order, cov from _covariates_arg, yt from _ytrans_arg."""
-    import ctypes as C
-    from .plink import PlinkBed
     n, q = Y.shape
     if isinstance(X, PlinkBed):
         return _prepare_bed_on_device(Y, X, device, cov, yt)
@@ -617,7 +241,6 @@ def _prepare_unpruned(Y, X, device, cov, yt=None):
 def _prepare_opt(pin, bed, cov, yt, n, p, q, device):
     """aq_prepare_data_opt on the one input given (pin: an AqPrepBedInput if bed, else an AqPrepInput; cov, yt: None where
     absent) and the return value of prepare_on_device from its handle.  An error names the entry that the arguments name."""
-    import ctypes as C
     h = C.c_void_p()
     rc = _lib.lib().aq_prepare_data_opt(None if bed else C.byref(pin), C.byref(pin) if bed else None, None if cov is None else C.byref(cov),
                                         None if yt is None else C.byref(yt), C.byref(h))
@@ -627,12 +250,7 @@ def _prepare_opt(pin, bed, cov, yt, n, p, q, device):
 
 def _prepared_from_handle(rc, h, what, n, p, q, device, bed=False, cov=False, ytrans=False):
     """The return value of prepare_on_device from the handle aq_prepare_data / aq_prepare_data_bed made (or their error)."""
-    import ctypes as C
-    if rc != 0:
-        msg = _lib.lib().aq_last_error().decode("utf-8", "replace")
-        if rc == 1:
-            raise AtlasqtlError(msg)                       # where the reference calls stop()
-        raise _lib.AtlasqtlHipError(f"{what}: [{rc}] {msg}")
+    raise_for_code(rc, what)
     pk = C.c_int32(0)
     cst = np.zeros(p, dtype=np.uint8); coll = np.zeros(p, dtype=np.uint8); dup = np.zeros(p, dtype=np.int32)
     _lib.check(_lib.lib().aq_prep_info(h, C.byref(pk), cst.ctypes.data_as(C.POINTER(C.c_uint8)),
@@ -661,7 +279,6 @@ def _prepared_from_handle(rc, h, what, n, p, q, device, bed=False, cov=False, yt
 def _prepare_bed_on_device(Y, bed, device, cov=None, yt=None):
     """prepare_on_device for a plink.PlinkBed: the packed blocks go to the library as they are (the .bed input of
     aq_prepare_data_opt)."""
-    import ctypes as C
     n, q = Y.shape
     if bed.n != n:
         raise AtlasqtlError("X and Y must have the same number of samples.")
@@ -688,7 +305,6 @@ def prepare_data_(Y, X, tol, maxit, user_seed, verbose, checkpoint_path, trace_p
     removed for another reason).  Both are None without pruning.
     With transform_y (prepare_on_device) Y is rank-normalised before all that; transform_y holds the options used and y_n_obs /
     y_n_tied the observed and the tied values per trait.  All three are None without it."""
-    from .plink import PlinkBed
     is_bed = isinstance(X, PlinkBed)
     check_vector_(user_seed, "user_seed", size=1, null_ok=True)
     check_vector_(tol, "tol", size=1)
@@ -761,7 +377,6 @@ def pcs_from_grm_(K, k, trace=None):
 
 
 def _n_of(X):
-    from .plink import PlinkBed
     if isinstance(X, PlinkBed):
         return X.n
     if np.ndim(X) != 2 or np.shape(X)[0] < 1:
@@ -788,8 +403,7 @@ def pc_solver_options(k, n, what, solver="eigh", oversample=None, tol=1e-8, max_
         raise AtlasqtlError(f"{what}: max_iter must be a whole number >= 1, not {max_iter!r}.")
     if not _is_whole(seed) or int(seed) < 0:
         raise AtlasqtlError(f"{what}: seed must be a whole number >= 0, not {seed!r}.")
-    if isinstance(tol, (bool, np.bool_)) or not isinstance(tol, (int, float, np.integer, np.floating)) or not (float(tol) > 0.0) \
-            or not np.isfinite(float(tol)):
+    if not _is_real(tol, 0.0, np.inf, lo_open=True, hi_open=True):
         raise AtlasqtlError(f"{what}: tol must be a number > 0, not {tol!r}.")
     if _is_whole(k) and oversample is not None and int(k) + int(oversample) > PCS_MAX_L:
         raise AtlasqtlError(f"{what}: k + oversample must be at most {PCS_MAX_L} (the block of vectors of solver='subspace'), "
@@ -819,7 +433,6 @@ def subspace_pcs_(apply, n, k, oversample=16, tol=1e-8, max_iter=300, seed=0, tr
     block Krylov method would be the tool, and is not built.  `max_iter` bounds the work: when it is reached a warning is
     given, converged is False, and what is returned is still an orthonormal Ritz basis with its residuals -- never an
     exception.  Equal inputs give equal bits."""
-    import warnings
     n, k, L = int(n), int(k), int(k) + int(oversample)
     Q = np.linalg.qr(np.random.default_rng(int(seed)).standard_normal((n, L)))[0]
     converged, it = False, 0

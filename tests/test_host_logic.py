@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 import atlasqtl_amd as A
+from atlasqtl_amd import checks as CK
 from atlasqtl_amd import hyper_init as H
 from atlasqtl_amd import prepare as P
 from atlasqtl_amd import synth
@@ -60,9 +61,9 @@ def test_input_guards():
                                         ((1, 2, 2000), "grid size very large"), ((1, 2), "anneal")])
 def test_check_annealing(anneal, msg):
     with pytest.raises(A.AtlasqtlError, match=msg):
-        P.check_annealing_(anneal)
-    P.check_annealing_(None)
-    P.check_annealing_((2, 1.5, 3))
+        CK.check_annealing_(anneal)
+    CK.check_annealing_(None)
+    CK.check_annealing_((2, 1.5, 3))
 
 
 def test_set_hyper_and_init_validation():
