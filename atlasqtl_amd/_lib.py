@@ -105,6 +105,16 @@ class AqCisintPlan(C.Structure):
                 ("yo_bytes", C.c_int64), ("pred_bytes", C.c_int64), ("basis_bytes", C.c_int64)]
 
 
+class AqFinemapParams(C.Structure):
+    _fields_ = [("L", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double), ("scaled_prior_variance", C.c_double),
+                ("coverage", C.c_double), ("alpha_min", C.c_double)]
+
+
+class AqFinemapPlan(C.Structure):
+    _fields_ = [("cis", AqCisPlan), ("L", C.c_int32), ("batch_tiles", C.c_int32), ("n_batches", C.c_int32), ("forced", C.c_int32),
+                ("state_budget", C.c_int64), ("state_bytes", C.c_int64), ("band_bytes", C.c_int64), ("fit_bytes", C.c_int64)]
+
+
 class AqPredictPlan(C.Structure):
     _fields_ = [("sample_tiles", C.c_int32), ("trait_tiles", C.c_int32), ("sample_blocks", C.c_int32), ("trait_groups", C.c_int32),
                 ("splits", C.c_int32), ("chunk", C.c_int32), ("chunks_per_split", C.c_int32), ("n_pad", C.c_int32),
@@ -200,6 +210,7 @@ SYMBOLS = {
     "aq_q_approx_vec": (C.c_int, [dp, dp, C.c_int64, ip]),
     "aq_vb_debug_raise_errflag": (C.c_int, [C.c_void_p]),
     "aq_debug_live_device_bytes": (C.c_int64, []),
+    "aq_prep_debug_set_column": (C.c_int, [C.c_void_p, C.c_int32, dp]),
     "aq_vb_debug_get_setup": (C.c_int64, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),
     "aq_prepare_data_bed": (C.c_int, [C.POINTER(AqPrepBedInput), C.POINTER(C.c_void_p)]),
     "aq_prep_genotype_counts": (C.c_int, [C.c_void_p, ip]),
@@ -242,6 +253,12 @@ SYMBOLS = {
     "aq_prep_cis_int": (C.c_int, [C.c_void_p, ip, ip, dp, C.c_int32, dp, dp, C.c_int64, ip, ip, dp, C.POINTER(C.c_int64), ip, dp,
                                   C.POINTER(C.c_int64), dp, C.POINTER(AqCisintPlan)]),
     "aq_prep_cis_int_time": (C.c_int, [C.c_void_p, ip, ip, dp, C.c_int32, dp, C.c_int32, dp, dp, C.POINTER(AqCisintPlan)]),
+    "aq_finemap_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, ip, C.c_int32, C.POINTER(AqFinemapPlan)]),
+    "aq_prep_cis_finemap": (C.c_int, [C.c_void_p, ip, ip, ip, C.POINTER(AqFinemapParams), C.c_int64, ip, ip, ip, dp, dp, dp,
+                                      C.POINTER(C.c_int64), dp, dp, dp, dp, ip, ip, C.POINTER(C.c_int64), dp, dp,
+                                      C.POINTER(AqFinemapPlan)]),
+    "aq_prep_set_purity": (C.c_int, [C.c_void_p, ip, ip, C.c_int32, dp, dp]),
+    "aq_prep_cis_finemap_time": (C.c_int, [C.c_void_p, ip, ip, C.c_int32, C.c_int32, dp, dp, dp, dp, C.POINTER(AqFinemapPlan)]),
     "aq_predict_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AqPredictPlan)]),
     "aq_vb_predict": (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int8), C.c_int32, dp, dp, dp]),
     "aq_vb_fitted": (C.c_int, [C.c_void_p, C.c_void_p, dp]),

@@ -406,3 +406,13 @@ extern "C" int aq_prep_get(aq_prep_handle h, double *X_out, double *Y_out) {
     return aq_fail(AQ_ERR_DEVICE, "aq_prep_get: copy of Y failed");
   return AQ_OK;
 }
+
+// Test hook: column `col` of the standardised compact X replaced by `values` (n doubles), so that a test can plant what the
+// preparation never leaves behind, a column of zeros for example.
+extern "C" int aq_prep_debug_set_column(aq_prep_handle h, int32_t col, const double *values) {
+  if (!h || !values) return aq_fail(AQ_ERR_ARG, "aq_prep_debug_set_column: NULL argument");
+  if (col < 0 || col >= h->p_kept) return aq_fail(AQ_ERR_ARG, "aq_prep_debug_set_column: col outside [0, p_kept)");
+  AQ_HIP(hipSetDevice(h->device));
+  AQ_HIP(hipMemcpy(h->Xs.get() + (size_t)col * (size_t)h->n, values, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice));
+  return AQ_OK;
+}

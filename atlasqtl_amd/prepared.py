@@ -1,6 +1,7 @@
 """PreparedData: the handle of a prepared problem (prepare.py makes it), the standardised compact X and the centred Y
 resident on the GPU, and every entry that runs on it as it stands: the copies back, the LD band, the relationship matrix and its
-application, and the screen family, whose six methods only marshal (marginal.py and cis.py make results of what they return).
+application, the screen family, whose six methods only marshal (marginal.py and cis.py make results of what they return), and
+the fine-mapping of the cis windows with the purity of its credible sets (cis_finemap, set_purity; cis.py makes the sets).
 What several of them need has one text here: _cutoff_arg, _perms_arg, _cis_windows_arg, _scan_outputs / _scan_dict, _plan_dict,
 _refuse_missing_y; and so has the translation of a return code into an exception, raise_for_code.
 """
@@ -266,6 +267,61 @@ class PreparedData:
                                               _lib.as_dp(cut), o.cap, *o.table, *o.best, o.n_undef.ctypes.data_as(_i64p),
                                               _lib.as_dp(int_tol), C.byref(plan)), "aq_prep_cis_int")
         return _scan_dict(o, n_undef=o.n_undef, int_tol=int_tol, plan=_plan_dict(plan))
+
+    def cis_finemap(self, s_lo, s_hi, L=10, tol=1e-3, max_iter=100, scaled_prior_variance=0.2, coverage=0.95, alpha_min=1e-4,
+                    active=None, cap=0, dense=False):
+        """Cis fine-mapping of the matrix as it stands: aq_prep_cis_finemap, SuSiE with L single effects per trait over the
+        predictors s_lo[t] <= s < s_hi[t], by IBSS on the GPU.  Complete Y only: the library refuses missing values under its
+        entry's name (AtlasqtlHipError).  active: q booleans, the traits to fit (None:
+        all); nothing is reported for the others (their entries below stay NaN, or 0 for the counts).  cap: rows of the table (0 only counts).
+        Returns dict(snp, trait, effect, alpha, mu, mu2: the min(n_rows, cap) rows written, in no particular order -- every
+        (predictor, trait, effect) with V > 0 and alpha >= min(alpha_min, 0.1 (1 - coverage) / P_t); n_rows: the full count;
+        sigma2 [q]; V, lbf [q x L]; elbo [max_iter x q, NaN where the trait did not run]; n_iter, converged, n_undef [q];
+        alpha_dense, mu_dense [q x L x p with dense=True, else None]; plan: the dict of aq_finemap_plan, the fields of its
+        aq_cis_plan alongside)."""
+        lo, hi = self._cis_windows_arg(s_lo, s_hi, "cis_finemap")
+        pm = _lib.AqFinemapParams(int(L), int(max_iter), float(tol), float(scaled_prior_variance), float(coverage), float(alpha_min))
+        act = None
+        if active is not None:
+            act = np.ascontiguousarray(np.asarray(active, dtype=bool), dtype=np.int32)
+            if act.shape != (self.q,):
+                raise AtlasqtlError(f"cis_finemap: active must hold one flag per trait ({self.q}), not {act.shape}.")
+        q, L, cap, iters = self.q, int(L), int(cap), max(int(max_iter), 0)
+        Lc = min(max(L, 0), 16)                                   # the library refuses what lies outside; no huge buffer before it does
+        snp, trait, effect = (np.empty(max(cap, 0), dtype=np.int32) for _ in range(3))
+        alpha, mu, mu2 = (np.empty(max(cap, 0)) for _ in range(3))
+        n_rows = C.c_int64(0)
+        sigma2, V, lbf = np.full(q, np.nan), np.full((q, Lc), np.nan), np.full((q, Lc), np.nan)
+        elbo = np.full((iters, q), np.nan)
+        n_iter, conv, n_undef = np.zeros(q, dtype=np.int32), np.zeros(q, dtype=np.int32), np.zeros(q, dtype=np.int64)
+        a_dense = np.zeros((q, Lc, self.p)) if dense else None
+        m_dense = np.zeros((q, Lc, self.p)) if dense else None
+        plan = _lib.AqFinemapPlan()
+        raise_for_code(_lib.lib().aq_prep_cis_finemap(
+            self.handle, _lib.as_ip(lo), _lib.as_ip(hi), None if act is None else _lib.as_ip(act), C.byref(pm), cap, _lib.as_ip(snp),
+            _lib.as_ip(trait), _lib.as_ip(effect), _lib.as_dp(alpha), _lib.as_dp(mu), _lib.as_dp(mu2), C.byref(n_rows), _lib.as_dp(sigma2),
+            _lib.as_dp(V), _lib.as_dp(lbf), _lib.as_dp(elbo), _lib.as_ip(n_iter), _lib.as_ip(conv), n_undef.ctypes.data_as(_i64p),
+            None if a_dense is None else _lib.as_dp(a_dense), None if m_dense is None else _lib.as_dp(m_dense), C.byref(plan)),
+            "aq_prep_cis_finemap")
+        k = min(int(n_rows.value), max(cap, 0))
+        return dict(snp=snp[:k], trait=trait[:k], effect=effect[:k], alpha=alpha[:k], mu=mu[:k], mu2=mu2[:k], n_rows=int(n_rows.value),
+                    sigma2=sigma2, V=V, lbf=lbf, elbo=elbo, n_iter=n_iter, converged=conv, n_undef=n_undef, alpha_dense=a_dense,
+                    mu_dense=m_dense, plan=_plan_dict(plan))
+
+    def set_purity(self, sets):
+        """(min |r|, mean |r|) over the pairs of columns of each set, of the matrix as it stands: aq_prep_set_purity.  sets: lists
+        of 1 ... 100 column indices; a set of one has purity 1."""
+        sets = [np.atleast_1d(np.asarray(s, dtype=np.int64)) for s in sets]
+        for b, s in enumerate(sets):
+            if s.ndim != 1 or not 1 <= s.size <= 100 or s.min() < 0 or s.max() >= self.p:
+                raise AtlasqtlError(f"set_purity: set {b} must hold 1 ... 100 column indices in [0, {self.p}).")
+        ptr = np.zeros(len(sets) + 1, dtype=np.int32)
+        ptr[1:] = np.cumsum([s.size for s in sets])
+        idx = np.ascontiguousarray(np.concatenate(sets + [np.zeros(1, dtype=np.int64)]), dtype=np.int32)   # never an empty buffer
+        mn, mean = np.empty(len(sets)), np.empty(len(sets))
+        raise_for_code(_lib.lib().aq_prep_set_purity(self.handle, _lib.as_ip(ptr), _lib.as_ip(idx), len(sets), _lib.as_dp(mn),
+                                                     _lib.as_dp(mean)), "aq_prep_set_purity")
+        return mn, mean
 
     def close(self):
         if self.handle is not None:

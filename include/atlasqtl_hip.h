@@ -408,6 +408,9 @@ int aq_vb_debug_raise_errflag(aq_vb_handle h);
  * prepared data, buffers of entries in flight).  0 in a fresh process; back at its earlier value once everything that was
  * created since has been destroyed. */
 int64_t aq_debug_live_device_bytes(void);
+/* Test hook: column col of a prepare handle's standardised compact X replaced by values[n].  The preparation removes constant
+ * columns, so a column of zeros -- which the cis fine-mapping must give no prior weight -- reaches a handle only this way. */
+int aq_prep_debug_set_column(aq_prep_handle h, int32_t col, const double *values);
 /* Test hook: one of the buffers aq_vb_create builds once per handle, as it lies in device memory (the layouts are described in
  * atlasqtl_amd/csrc/aq_core_sweep.h and aq_vb.h).  Returns the buffer's length in bytes and copies it to buf when cap_bytes
  * suffices (buf may be NULL with cap_bytes = 0: the length alone); 0 for a buffer this handle does not hold -- GK without the
@@ -932,6 +935,88 @@ int aq_prep_cis_int(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, 
                     double *best_r, int64_t *n_undef, double *int_tol, aq_cisint_plan *plan_out);
 int aq_prep_cis_int_time(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, const double *basis, int32_t n_basis,
                          const double *mult, int32_t reps, double *ms_stats, double *ms_scan, aq_cisint_plan *plan_out);
+
+/* ------------------------------------------------------------------------------------------
+ * Cis fine-mapping of a finished handle: per trait the credible sets of the variants that carry its independent signals, by
+ * SuSiE (the sum of L single effects, fitted by IBSS; tensorQTL's susie.map), over the predictors of the trait's own window.
+ * The windows, the order of the traits and the work items are those of aq_prep_cis.
+ * The model.  Complete Y only.  The fit is on the handle's own matrices, Xs [p1][n] and Yc [q][n], without further centring
+ * or scaling: susieR's susie(standardize = FALSE, intercept = FALSE).  Per trait with window [lo, hi) and effects l < L:
+ * d_s = x_s'x_s; a predictor with d_s <= 1e-10 n has prior weight 0 and is counted in n_undef, the other P have the weight
+ * pi = 1 / P.
+ *   Start.          alpha = pi, mu = 0, fit_l = 0, sigma2 = y'y / (n - 1), V_l = scaled_prior_variance y'y / (n - 1), ELBO = -inf.
+ *   An iteration.   Rf = y - sum_l fit_l, subtracted in the order l = 0 ... L - 1.  Then for l = 0 ... L - 1:
+ *                   r_l = Rf + fit_l;  z_s = x_s'r_l;
+ *                   lbf_s = 1/2 log(sigma2 / (sigma2 + V_l d_s)) + 1/2 z_s^2 V_l / (sigma2 (sigma2 + V_l d_s)), 0 if V_l = 0;
+ *                   alpha_s = pi exp(lbf_s) / sum pi exp(lbf), the largest lbf taken out first;  lbf_model = log sum pi exp(lbf);
+ *                   v_s = 1 / (d_s / sigma2 + 1 / V_l);  mu_s = v_s z_s / sigma2;  mu2_s = v_s + mu_s^2;
+ *                   V_l <- sum alpha_s mu2_s, used from the next iteration on, and V_l <- 0 if lbf_model at that new V_l is <= 0;
+ *                   fit_l <- sum_s x_s alpha_s mu_s;  Rf <- r_l - fit_l;
+ *                   KL_l = -lbf_model + (2 sum z_s alpha_s mu_s - sum d_s alpha_s mu2_s) / (2 sigma2).
+ *   After them.     ERSS = |Rf|^2 + sum_l (sum_s d_s alpha_ls mu2_ls - |fit_l|^2);
+ *                   ELBO = -(n / 2) log(2 pi sigma2) - ERSS / (2 sigma2) - sum_l KL_l with the sigma2 the iteration used.
+ *                   The trait has converged if tol > 0 and ELBO - ELBO_prev < tol; otherwise sigma2 <- ERSS / n.  At most
+ *                   max_iter iterations; tol = 0 never converges.  A converged trait's state is not written again.
+ * x'r_l over the window is the cis tile loop with the residuals in the place of the traits, X (alpha mu) its banded
+ * transpose, both on the f64 matrix pipe for the 64 traits of a trait tile at once; consecutive trait tiles run in lockstep
+ * in batches whose alpha and mu stay within a budget (aq_finemap_plan).  Traits are independent: the batches change no bit,
+ * and neither does `active`, which leaves the tiles as they are.  Every sum runs in a fixed order and no floating-point atomic
+ * is used: two calls give the same set of rows and the same bits in every other output.
+ *   aq_prep_cis_finemap       active: int32[q] or NULL (all); a trait with active[t] = 0 is not fitted and NO output of it is
+ *                             written.  cap: rows of the table (0 only counts); n_rows: always the full count.  A row is
+ *                             (snp, trait, effect l, alpha, mu, mu2) of the iteration in which the trait stopped, for every
+ *                             effect whose final V_l > 0 and every in-window predictor with alpha >= thr_t =
+ *                             min(alpha_min, 0.1 (1 - coverage) / P): the mass an effect loses is below 0.1 (1 - coverage).
+ *                             sigma2: double[q]; V, lbf: double[q][L] (the final V_l; lbf_model of the last iteration);
+ *                             elbo_trace: double[max_iter][q], NaN where the trait did not run; n_iter, converged: int32[q];
+ *                             n_undef: int64[q].  alpha_dense, mu_dense: double[q][L][p1], 0.0 outside the window (tests and
+ *                             small problems: they go through the host).  A trait with an empty window, or without a
+ *                             predictor of prior weight, gets no rows, n_iter = 0 and NaN in sigma2, V, lbf.  Any output
+ *                             may be NULL.  The handle is not changed.
+ *   aq_finemap_plan_query     the plan without a device: a function of its arguments and of the environment variable
+ *                             AQ_FM_BATCH_TILES (>= 1; tests, small shapes), which forces the trait tiles per batch in the
+ *                             entries and which the query reads as they do.  L outside [1, 16] is AQ_ERR_ARG.
+ *   aq_prep_set_purity        set b = the columns set_idx[set_ptr[b]] ... set_idx[set_ptr[b + 1] - 1], 1 ... 100 of them:
+ *                             min_abs_r[b] and mean_abs_r[b], the smallest and the mean |Pearson correlation| over its pairs
+ *                             of columns of Xs; 1 and 1 for a set of one; a pair with a constant column counts as 0.
+ *   aq_prep_cis_finemap_time  measurement: the four kernels of one iteration at the default parameters, each `reps` times
+ *                             between two events after a warm-up: ms_xtr, ms_ser, ms_fit (L launches each) and ms_iter_end,
+ *                             summed over the batches.
+ * AQ_ERR_ARG, in this order, before any device call: a NULL s_lo or s_hi; NULL params; L outside [1, 16]; max_iter < 1; tol
+ * negative or not finite; scaled_prior_variance not positive; coverage outside (0, 1); alpha_min outside [0, 1]; cap < 0; a
+ * NULL handle; the window errors of aq_prep_cis.  A handle whose Y has missing values is AQ_ERR_UNSUPPORTED, and the message
+ * says so.  No index out of range reaches a kernel.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct aq_finemap_params {
+  int32_t L;                  /* single effects, 1 ... 16                                          */
+  int32_t max_iter;           /* most IBSS iterations                                             */
+  double tol;                 /* converged when the ELBO gains less; 0: never                     */
+  double scaled_prior_variance; /* V_l at the start, as a share of y'y / (n - 1)                  */
+  double coverage;            /* of the credible sets the rows are meant for: enters thr_t        */
+  double alpha_min;           /* rows with alpha below min(alpha_min, 0.1 (1 - coverage) / P) are dropped */
+} aq_finemap_params;
+typedef struct aq_finemap_plan {
+  aq_cis_plan cis;            /* the plan of the windows: complete Y, no permutations             */
+  int32_t L;                  /* single effects                                                   */
+  int32_t batch_tiles;        /* trait tiles that run in lockstep: batch b = tiles [b batch_tiles, ...) */
+  int32_t n_batches;          /* ceil(trait_tiles / batch_tiles)                                  */
+  int32_t forced;             /* 1: batch_tiles is AQ_FM_BATCH_TILES                              */
+  int64_t state_budget;       /* the bound on alpha and mu of a batch, 4 GiB                      */
+  int64_t state_bytes;        /* alpha and mu of the largest batch: 2 L 64 64 8 per work item     */
+  int64_t band_bytes;         /* its band buffer x'r: 64 64 8 per work item                       */
+  int64_t fit_bytes;          /* its residuals and fits: 8 (L + 2) n per trait                    */
+} aq_finemap_plan;
+int aq_finemap_plan_query(int32_t n, int32_t p1, int32_t q, int32_t ncu, const int32_t *s_lo, const int32_t *s_hi, int32_t L,
+                          aq_finemap_plan *out);
+int aq_prep_cis_finemap(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, const int32_t *active,
+                        const aq_finemap_params *params, int64_t cap, int32_t *row_snp, int32_t *row_trait, int32_t *row_effect,
+                        double *row_alpha, double *row_mu, double *row_mu2, int64_t *n_rows, double *sigma2, double *V, double *lbf,
+                        double *elbo_trace, int32_t *n_iter, int32_t *converged, int64_t *n_undef, double *alpha_dense, double *mu_dense,
+                        aq_finemap_plan *plan_out);
+int aq_prep_set_purity(aq_prep_handle h, const int32_t *set_ptr, const int32_t *set_idx, int32_t n_sets, double *min_abs_r,
+                       double *mean_abs_r);
+int aq_prep_cis_finemap_time(aq_prep_handle h, const int32_t *s_lo, const int32_t *s_hi, int32_t L, int32_t reps, double *ms_xtr,
+                             double *ms_ser, double *ms_fit, double *ms_iter_end, aq_finemap_plan *plan_out);
 
 /* ------------------------------------------------------------------------------------------
  * Prediction: the fitted model applied to genotypes,
