@@ -29,6 +29,13 @@
 // (waves 4-6 start a phase when their partner is a given number of tiles into it: a.stagger); that paid while the matrix
 // SIMDs were the bound, with tiles on the recurrence wave SIMD 3 is co-critical and any stagger 0 .. 9 measures the same.
 //
+// On SIMD 3 an MFMA and any other VALU operation exclude each other, so every instruction the helper wave does not issue is
+// time.  Its per-block work comes in forms picked from two wave-uniform facts (c_one, blk_full in the helper's role): without
+// annealing (c = 1: every sweep after the ladder) the second table pass reuses the interval and local variable of the first and
+// nothing is multiplied by c, sqrt(c) or 1 / sqrt(c); in a block whose entries are all real ones no validity is tested per
+// entry.  Both forms keep every fp64 operation's operands and order: the results are the general form's bits
+// (profiles/r04_c1_valu.txt: 263 of the 2 133 non-MFMA VALU operations per workgroup and phase at C3; 0.4 - 1.4 % of the kernel time).
+//
 // The X operand stream is issued by inline-asm loads with explicit s_waitcnt vmcnt counts: the compiler can neither
 // hoist the loads of a fully unrolled tile loop (which cost 16 VGPRs per residual tile and spilled) nor has it to
 // guess the prefetch distance.  LDS buffers are double-buffered by block parity; the hand-offs are point-to-point LDS
@@ -104,6 +111,15 @@ __device__ __forceinline__ void aq_static_for(F &&f) {
     asm volatile("global_load_dwordx4 %0, %2, %3 offset:%4\n\tglobal_load_dwordx4 %1, %2, %3 offset:%5"        \
                  : "=&v"(d0), "=&v"(d1)                                                                         \
                  : "v"(voff), "s"(u_), "i"(IMM), "i"((IMM) + 1024));                                            \
+  } while (0)
+// one 4-byte load whose value nobody reads (L2 warm-up): lane address = sbase + voff, sbase wave-uniform as above
+#define AQ_TOUCH(d, voff, sbase)                                                                               \
+  do {                                                                                                          \
+    const unsigned long long b_ = (unsigned long long)(sbase);                                                  \
+    const unsigned lo_ = __builtin_amdgcn_readfirstlane((unsigned)b_);                                          \
+    const unsigned hi_ = __builtin_amdgcn_readfirstlane((unsigned)(b_ >> 32));                                  \
+    const unsigned long long u_ = ((unsigned long long)hi_ << 32) | lo_;                                        \
+    asm volatile("global_load_dword %0, %1, %2" : "=v"(d) : "v"(voff), "s"(u_));                                \
   } while (0)
 // wait until at most N of this wave's vector-memory operations are outstanding; the operands tie the wait to the
 // registers it covers so that no use can be scheduled above it
@@ -1008,21 +1024,36 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
     aq_lds_cdouble *ptab = (aq_lds_cdouble *)(__attribute__((address_space(3))) double *)Lpt;
     const double inv_sqrt_c = 1.0 / a.sqrt_c;
     const double cst_k = MASK ? 0.0 : a.cst[ktrait];                                 // -(log_tau + log_sig2_inv + log sig2_beta) / 2
+    // Two facts that are the same for every lane and known before a block is touched pick the form of stage() and finalize():
+    //   c_one: no annealing in this launch (c is fixed per launch; every sweep after the ladder).  sqrt(c) u is then u bit for
+    //     bit, so the second table pass reuses the interval and the local variable of the first, and every product with c,
+    //     sqrt(c) or 1 / sqrt(c) -- exact identities at 1.0 -- is not issued;
+    //   blk_full(b): every entry of block b is a real one -- the block lies below p and the workgroup holds no padding trait --
+    //     so the per-entry validity selects and exec-mask branches go.
+    // Either form performs, for the entries that count, the same fp64 operations on the same operands in the same order as the
+    // general one: the results are the same bits.
+    const bool c_one = (a.c == 1.0) && (a.sqrt_c == 1.0);
+    const bool wg_full = tile0 * 16 + NTR <= a.q;
+    auto blk_full = [&](int b) __attribute__((always_inline)) { return wg_full && 16 * b + 16 <= a.p; };
+    // The lane's entries of block b are rows hg + NG r: in gam, mu (and rowGB, theta) one base per block and compile-time
+    // offsets of NG r rows, which land in the instructions' immediate fields.
+    auto ent_base = [&](int b) __attribute__((always_inline)) { return tbase + (size_t)(16 * b + hg) * 16; };
     double th[RPG];   // theta of the block to be staged next, loaded a phase earlier so that the arithmetic never waits for HBM
     auto theta_load = [&](int b) __attribute__((always_inline)) {
+      const double *tp = a.theta + (16 * b + hg);
 #pragma unroll
-      for (int r = 0; r < RPG; r++) th[r] = a.theta[16 * b + hg + NG * r];
+      for (int r = 0; r < RPG; r++) th[r] = tp[NG * r];
     };
     // complete Y: gam and mu of the block to be staged next, requested together with its theta a phase ahead; stage() turns them
     // into m1 = gam mu first thing, so that their registers are free again while the probit tables are evaluated
     double pg[MASK ? 1 : RPG], pm[MASK ? 1 : RPG];
     auto gm_load = [&](int b) __attribute__((always_inline)) {
       if constexpr (!MASK) {
+        const double *gp = a.gam + ent_base(b), *mp = a.mu + ent_base(b);
 #pragma unroll
         for (int r = 0; r < RPG; r++) {
-          const size_t off = tbase + (size_t)(16 * b + hg + NG * r) * 16;
-          pg[r] = a.gam[off];
-          pm[r] = a.mu[off];
+          pg[r] = gp[NG * 16 * r];
+          pm[r] = mp[NG * 16 * r];
         }
       }
     };
@@ -1052,12 +1083,12 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
     double sv_g[MASK ? RPG : 1], sv_m[MASK ? RPG : 1], sv_xn[MASK ? RPG : 1], sv_th[MASK ? RPG : 1];   // the block being staged
     auto pre_load = [&](int b) __attribute__((always_inline)) {
       const double *gk = gk_block(b);
+      const double *gp = a.gam + ent_base(b), *mp = a.mu + ent_base(b);
 #pragma unroll
       for (int r = 0; r < RPG; r++) {
-        const size_t off = tbase + (size_t)(16 * b + hg + NG * r) * 16;
         const int jj = hg + NG * r;
-        pl_g[r] = a.gam[off];
-        pl_m[r] = a.mu[off];
+        pl_g[r] = gp[NG * 16 * r];
+        pl_m[r] = mp[NG * 16 * r];
         pl_xn[r] = gk[(jj * (jj + 1) / 2 + jj) * 16 + ht];     // X_norm_sq(j,k) = the diagonal of the trait's own block
       }
     };
@@ -1073,7 +1104,10 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
       gk_dma(b, par);
       if (b_next < seg_b1) { pre_load(b_next); theta_load(b_next); }
     };
-    auto stage = [&](int b, int par) __attribute__((always_inline)) {
+    // C1 / FULL: the form for c = 1 / for a block whose entries are all real (see c_one, blk_full above).  <false, false> is the
+    // general form; stage_block() below picks.
+    auto stage = [&](int b, int par, auto c1c, auto fullc) __attribute__((always_inline)) {
+      constexpr bool C1 = decltype(c1c)::value, FULL = decltype(fullc)::value;
       double st_G[4], st_Gx[4], st_xn[MASK ? RPG : 1];
       if constexpr (MASK) {
 #pragma unroll
@@ -1114,23 +1148,24 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
       // R/update_vb.R:219-233), u = theta_j + zeta_k, for the RPG entries of this lane.
       auto emitA = [&](int r, double A) __attribute__((always_inline)) {
         const int j = 16 * b + hg + NG * r, e = lane + 64 * r;
-        const bool valid = kvalid && j < a.p;
-        if constexpr (MASK) {
-          LA[par][e] = a.c * ((valid ? A : 0.0) - 0.5 * ls2r[r] + cstna_k);    // src/coreLoop.cpp:127-129
-        } else {
-          LA[par][e] = a.c * ((valid ? A : 0.0) + cst_k);                        // c (log(1-Phi) - log Phi + cst), src/coreLoop.cpp:75-77
-        }
+        const bool valid = FULL || (kvalid && hg < a.p - 16 * b - NG * r);
+        const double Av = FULL ? A : (valid ? A : 0.0);
+        // MASK: src/coreLoop.cpp:127-129; complete Y: c (log(1-Phi) - log Phi + cst), src/coreLoop.cpp:75-77
+        double t;
+        if constexpr (MASK) t = Av - 0.5 * ls2r[r] + cstna_k;
+        else t = Av + cst_k;
+        LA[par][e] = C1 ? t : a.c * t;
       };
       auto emitZ = [&](int r, double zb, double za) __attribute__((always_inline)) {
         const int j = 16 * b + hg + NG * r, e = lane + 64 * r;
-        const bool valid = kvalid && j < a.p;
+        const bool valid = FULL || (kvalid && hg < a.p - 16 * b - NG * r);
         LB[par][e] = valid ? zb : 0.0;
         Laa[par][e] = valid ? za : 0.0;
       };
       // the same three probit-dependent fields again, for a run-time r (second pass of a block with lanes outside the tables)
       auto emit2 = [&](int r, double A, double zb, double za) __attribute__((always_inline)) {
         const int j = 16 * b + hg + NG * r, e = lane + 64 * r;
-        const bool valid = kvalid && j < a.p;
+        const bool valid = kvalid && hg < a.p - 16 * b - NG * r;
         LB[par][e] = valid ? zb : 0.0;
         Laa[par][e] = valid ? za : 0.0;
         if constexpr (MASK) LA[par][e] = a.c * ((valid ? A : 0.0) - 0.5 * Lls2[par][e] + cstna_k);
@@ -1141,7 +1176,8 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
 #pragma unroll
       for (int r = 0; r < RPG; r++) {
         uu[r] = (MASK ? sv_th[r] : th[r]) + zk;
-        inr = inr && fabs(uu[r]) < AQ_PT_R && fabs(a.sqrt_c * uu[r]) < AQ_PT_R;   // (false for NaN)
+        if constexpr (C1) inr = inr && fabs(uu[r]) < AQ_PT_R;                     // (false for NaN)
+        else inr = inr && fabs(uu[r]) < AQ_PT_R && fabs(a.sqrt_c * uu[r]) < AQ_PT_R;
       }
       {
         // Tables (aq_probit_tab.h: A, b, d as piecewise polynomials of degree AQ_PT_DEG; coefficient k of function f on interval
@@ -1159,18 +1195,23 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
           *xloc = fma(2.0, t - (double)i, -1.0);
           return ptab + i;
         };
+        // C1: the second pass is at the same point as the first (sqrt(c) u = u): the first pass keeps each entry's interval
+        // pointer and local variable (RPG x 3 VGPRs) and the second reads b and d through them -- no second locate()
+        aq_lds_cdouble *pp1[C1 ? RPG : 1];
+        double xl1[C1 ? RPG : 1];
         {
           double co[2][NC], xl[2];
-          auto fetch = [&](int r, auto setc) __attribute__((always_inline)) {
-            constexpr int set = decltype(setc)::value;
+          auto fetch = [&](auto rc, auto setc) __attribute__((always_inline)) {
+            constexpr int r = decltype(rc)::value, set = decltype(setc)::value;
             aq_lds_cdouble *pp = locate(uu[r], &xl[set]);
+            if constexpr (C1) { pp1[r] = pp; xl1[r] = xl[set]; }
 #pragma unroll
             for (int k = 0; k < NC; k++) co[set][k] = pp[k * S];
           };
-          fetch(0, std::integral_constant<int, 0>{});
+          fetch(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
           aq_static_for<RPG>([&](auto rc) __attribute__((always_inline)) {
             constexpr int r = decltype(rc)::value, set = r & 1;
-            if constexpr (r + 1 < RPG) fetch(r + 1, std::integral_constant<int, (r + 1) & 1>{});
+            if constexpr (r + 1 < RPG) fetch(std::integral_constant<int, r + 1>{}, std::integral_constant<int, (r + 1) & 1>{});
             __builtin_amdgcn_sched_barrier(0);
             double pa = co[set][NC - 1];
 #pragma unroll
@@ -1181,19 +1222,21 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
         }
         {
           double co[2][2 * NC], xl[2];
-          auto fetch = [&](int r, auto setc) __attribute__((always_inline)) {
-            constexpr int set = decltype(setc)::value;
-            aq_lds_cdouble *pp = locate(a.sqrt_c * uu[r], &xl[set]);
+          auto fetch = [&](auto rc, auto setc) __attribute__((always_inline)) {
+            constexpr int r = decltype(rc)::value, set = decltype(setc)::value;
+            aq_lds_cdouble *pp;
+            if constexpr (C1) { pp = pp1[r]; xl[set] = xl1[r]; }
+            else pp = locate(a.sqrt_c * uu[r], &xl[set]);
 #pragma unroll
             for (int k = 0; k < NC; k++) {
               co[set][k] = pp[F + k * S];
               co[set][NC + k] = pp[2 * F + k * S];
             }
           };
-          fetch(0, std::integral_constant<int, 0>{});
+          fetch(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
           aq_static_for<RPG>([&](auto rc) __attribute__((always_inline)) {
             constexpr int r = decltype(rc)::value, set = r & 1;
-            if constexpr (r + 1 < RPG) fetch(r + 1, std::integral_constant<int, (r + 1) & 1>{});
+            if constexpr (r + 1 < RPG) fetch(std::integral_constant<int, r + 1>{}, std::integral_constant<int, (r + 1) & 1>{});
             __builtin_amdgcn_sched_barrier(0);
             double pb = co[set][NC - 1], pd = co[set][2 * NC - 1];
 #pragma unroll
@@ -1203,7 +1246,8 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
             }
             const double d = uu[r] < 0.0 ? -pd : pd;                     // d is odd, b is even
             // imr0 = -M(U) = -(b + d) / 2:  a = u + imr0 / sqrt(c),  slope = b / sqrt(c)
-            emitZ(r, pb * inv_sqrt_c, uu[r] - 0.5 * inv_sqrt_c * (pb + d));
+            if constexpr (C1) emitZ(r, pb, uu[r] - 0.5 * (pb + d));       // (1 / sqrt(c) = 1: the same values)
+            else emitZ(r, pb * inv_sqrt_c, uu[r] - 0.5 * inv_sqrt_c * (pb + d));
             __builtin_amdgcn_sched_barrier(0);
           });
         }
@@ -1242,19 +1286,21 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
     // running column sums of this lane's entries (they all belong to trait ht): sum gam, sum m2, sum beta^2 (MASK: sum
     // X_norm_sq (m2 - beta^2), R/update_vb.R:152-154), sum Z, and for MASK sum gam log sig2_beta
     double cs0 = 0.0, cs1 = 0.0, cs2 = 0.0, cs3 = 0.0, cs5 = 0.0;
-    auto finalize = [&](int b, int par) __attribute__((always_inline)) {
+    auto finalize = [&](int b, int par, auto fullc) __attribute__((always_inline)) {
+      constexpr bool FULL = decltype(fullc)::value;   // every entry of the block is a real one: no test per entry
+      double *gp = a.gam + ent_base(b), *mp = a.mu + ent_base(b);
+      double *rowp = a.rowGB + (size_t)(tile0 + (ht >> 4)) * a.p_pad + (16 * b + hg);
 #pragma unroll
       for (int r = 0; r < RPG; r++) {
         const int e = lane + 64 * r, hj = hg + NG * r;
         const double gm = Lgam[par][e], mu = Lmu[par][e];
-        const size_t off = tbase + (size_t)(16 * b + hj) * 16;
         if (lead) {
-          a.gam[off] = gm;
-          a.mu[off] = mu;
+          gp[NG * 16 * r] = gm;
+          mp[NG * 16 * r] = mu;
         }
         const int j = 16 * b + hj;
         double gb = 0.0;
-        if (kvalid && j < a.p) {
+        if (FULL || (kvalid && hg < a.p - 16 * b - NG * r)) {
           const double be = gm * mu;
           gb = Laa[par][e] + gm * LB[par][e];       // Z_jk = a + gam b: its row and column sums are all that is needed
           cs0 += gm;
@@ -1272,8 +1318,21 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
           }
         }
         gb = aq_row16_sum(gb);                      // over the 16 traits of the tile (one DPP row)
-        if ((ht & 15) == 0 && lead) a.rowGB[(size_t)(tile0 + (ht >> 4)) * a.p_pad + j] = gb;
+        if ((ht & 15) == 0 && lead) rowp[NG * r] = gb;
       }
+    };
+    // the form of a block, from wave-uniform facts alone.  The annealed sweeps (c != 1: the ten of the ladder) stage in the
+    // general form throughout.
+    using aq_no = std::false_type;
+    using aq_yes = std::true_type;
+    auto stage_block = [&](int b, int par) __attribute__((always_inline)) {
+      if (!c_one) stage(b, par, aq_no{}, aq_no{});
+      else if (blk_full(b)) stage(b, par, aq_yes{}, aq_yes{});
+      else stage(b, par, aq_yes{}, aq_no{});
+    };
+    auto finalize_block = [&](int b, int par) __attribute__((always_inline)) {
+      if (blk_full(b)) finalize(b, par, aq_yes{});
+      else finalize(b, par, aq_no{});
     };
     // sample split, exchange on this wave (a.xhelper): a block ahead of the chain -- S' of block b is complete a phase before the
     // chain of block b starts -- so the round trip through the shared cache level is off the recurrence wave's path
@@ -1333,36 +1392,45 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
       // helper wave therefore touches 8 KB slices (its lane: one 128-B line each) of the panels the NEXT phase will read -- the
       // S' operands of block b+2 and the update operands of block b -- a phase ahead; the workgroups that share an XCD (block
       // index modulo 8 under the round-robin placement: speed only) take different slices, up to four each.  The loaded words
-      // are never used; their registers stay reserved until the wait at the next call.  C3: 34.96 -> 34.49 ms.
+      // are never used; their registers stay reserved until the wait further down the same iteration (x_wait) -- a request that
+      // stayed out across the loop's back edge had its register copied or re-used on the edges out of the loop, which the ISA
+      // proof refuses.  C3: 34.96 -> 34.49 ms.
       int xt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       const long long xt_blk = (long long)NTT * C * 2048;                      // bytes of one panel
       const int xt_nsl = (int)((xt_blk + 8191) / 8192);                        // slices of a panel
       const int xt_wg = (int)(gridDim.x < 256 ? gridDim.x : 256) / 8 > 0 ? (int)(gridDim.x < 256 ? gridDim.x : 256) / 8 : 1;   // workgroups of this launch per XCD
       auto x_touch = [&](int bA, int bU) __attribute__((always_inline)) {
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(xt[0]), "+v"(xt[1]), "+v"(xt[2]), "+v"(xt[3]), "+v"(xt[4]), "+v"(xt[5]), "+v"(xt[6]), "+v"(xt[7]));
-        const char *pa = (const char *)a.XA + (long long)bA * xt_blk + lane * 128, *pu = (const char *)a.XU + (long long)bU * xt_blk + lane * 128;
+        // (the slice's base is wave-uniform: an SGPR pair plus the lane's 32-bit offset, no 64-bit address per lane and load)
+        const char *pa = (const char *)a.XA + (long long)bA * xt_blk, *pu = (const char *)a.XU + (long long)bU * xt_blk;
+        const unsigned xt_lane = (unsigned)lane * 128u;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
           const int sl = (int)((blockIdx.x >> 3) % xt_wg) + k * xt_wg;
           if (sl < xt_nsl && (long long)sl * 8192 + lane * 128 < xt_blk) {
-            asm volatile("global_load_dword %0, %1, off" : "=v"(xt[2 * k]) : "v"(pa + (long long)sl * 8192));
-            asm volatile("global_load_dword %0, %1, off" : "=v"(xt[2 * k + 1]) : "v"(pu + (long long)sl * 8192));
+            AQ_TOUCH(xt[2 * k], xt_lane, pa + (long long)sl * 8192);
+            AQ_TOUCH(xt[2 * k + 1], xt_lane, pu + (long long)sl * 8192);
           }
         }
+      };
+      auto x_wait = [&]() __attribute__((always_inline)) {
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(xt[0]), "+v"(xt[1]), "+v"(xt[2]), "+v"(xt[3]), "+v"(xt[4]), "+v"(xt[5]), "+v"(xt[6]), "+v"(xt[7]));
       };
       theta_load(seg_b0);
       gm_load(seg_b0);
       if constexpr (MASK) { pre_load(seg_b0); stage_dma(seg_b0, seg_b0 & 1, seg_b0 + 1); }
-      stage(seg_b0, seg_b0 & 1);
-      signal(7, 1);
-      if constexpr (!SEG && TT == 1) { if (C > 1 && a.xhelper) exchange(seg_b0); }
-      if constexpr (!MASK) { if (seg_b0 + 1 < seg_b1) { theta_load(seg_b0 + 1); gm_load(seg_b0 + 1); } }
-      for (int b = seg_b0; b < seg_b1; b++) {
+      // Iteration b finalises block b-1 and stages block b+1 while the chain of block b runs; the first one (b = seg_b0 - 1) only
+      // stages, the last one (b = seg_b1) only finalises.  One loop, so that stage() and finalize(), each in several forms, exist
+      // once in the code.
+      // (the per-trait constants loaded at the top are used here once, so that their loads are complete before the loop: a load
+      // that could still be out on the way into the loop makes hipcc wait for everything outstanding -- the next block's theta,
+      // gam and mu among it -- at the constants' uses inside the loop)
+      asm volatile("" : : "v"(zk), "v"(cst_k), "v"(sig2b_k), "v"(tau_k), "v"(sig2_inv_h), "v"(cstna_k));
+      for (int b = seg_b0 - 1; b <= seg_b1; b++) {
         const int par = b & 1;
         if constexpr (MASK) {
           // the Gram blocks of block b+1 go on their way as soon as the chain of block b has applied the cross blocks (which
           // also means that block b-1, the last reader of the other diagonal buffer, is through)
-          if (b + 1 < seg_b1) { wait_ge(13, b - seg_b0 + 1); stage_dma(b + 1, par ^ 1, b + 2); }
+          if (b >= seg_b0 && b + 1 < seg_b1) { wait_ge(13, b - seg_b0 + 1); stage_dma(b + 1, par ^ 1, b + 2); }
         }
         // block b-1 must be through the recurrence: its gam / mu are read here, and the parity buffers about to be
         // overwritten with block b+1 are the ones it read
@@ -1371,32 +1439,33 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
           if constexpr (!MASK && !CXC) {
             // cross-block correction X_b'X_{b-1} delta_{b-1} of block b for the recurrence wave (a 16 x 16 by 16 x NTR product: 128
             // multiply-adds and 144 LDS reads per lane that would otherwise sit between "S' complete" and the first chain step)
-            double dlp[16];
+            if (b < seg_b1) {
+              double dlp[16];
 #pragma unroll
-            for (int i = 0; i < 16; i++) dlp[i] = Ldel[par ^ 1][i * NTR + ht];
+              for (int i = 0; i < 16; i++) dlp[i] = Ldel[par ^ 1][i * NTR + ht];
 #pragma unroll
-            for (int r = 0; r < RPG; r++) {
-              double cx = 0.0;
-              const double *gx = &LGx[par][(hg + NG * r) * 16];
+              for (int r = 0; r < RPG; r++) {
+                double cx = 0.0;
+                const double *gx = &LGx[par][(hg + NG * r) * 16];
 #pragma unroll
-              for (int i = 0; i < 16; i++) cx += gx[i] * dlp[i];
-              Lcx[lane + 64 * r] = cx;
+                for (int i = 0; i < 16; i++) cx += gx[i] * dlp[i];
+                Lcx[lane + 64 * r] = cx;
+              }
+              signal(12, b - seg_b0 + 1);
             }
-            signal(12, b - seg_b0 + 1);
           }
-          finalize(b - 1, par ^ 1);
         }
+        // the panels of the next phase, requested before this iteration's own work and waited for behind it (x_wait)
+        if (a.xtouch && b >= seg_b0 && b + 2 < seg_b1) x_touch(b + 2, b);
+        if (b > seg_b0) finalize_block(b - 1, par ^ 1);
         if (b + 1 < seg_b1) {
-          stage(b + 1, par ^ 1);
+          stage_block(b + 1, par ^ 1);
           signal(7, b - seg_b0 + 2);
           if constexpr (!SEG && TT == 1) { if (C > 1 && a.xhelper) exchange(b + 1); }
-          if (a.xtouch && b + 2 < seg_b1) x_touch(b + 2, b);
-          if constexpr (!MASK) { if (b + 2 < seg_b1) { theta_load(b + 2); gm_load(b + 2); } }
         }
+        x_wait();
+        if constexpr (!MASK) { if (b + 2 < seg_b1) { theta_load(b + 2); gm_load(b + 2); } }
       }
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(xt[0]), "+v"(xt[1]), "+v"(xt[2]), "+v"(xt[3]), "+v"(xt[4]), "+v"(xt[5]), "+v"(xt[6]), "+v"(xt[7]));
-      wait_ge(6, nblk);
-      finalize(seg_b1 - 1, (seg_b1 - 1) & 1);
     }
     Lred[0][lane] = cs0; Lred[1][lane] = cs1; Lred[2][lane] = cs2; Lred[3][lane] = cs3; Lred[5][lane] = cs5;   // [row group][trait]
     __syncthreads();   // matches the matrix waves' barrier before the final sums
