@@ -154,6 +154,11 @@ class AqVbStatus(C.Structure):
     ]
 
 
+class AqKernelInstance(C.Structure):
+    """aq_kernel_instance: the template parameters of a compiled core-kernel instance (aq_instance_query)."""
+    _fields_ = [(k, C.c_int32) for k in ("core_kernel", "nt", "nt2", "seg", "tt", "mask", "nt3", "wide", "ne", "wpt")]
+
+
 # every symbol include/atlasqtl_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "aq_last_error": (C.c_char_p, []),
@@ -175,6 +180,7 @@ SYMBOLS = {
     "aq_vb_get_overrides": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_int32]),
     "aq_plan_query": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_char_p,
                                 C.POINTER(AqVbStatus)]),
+    "aq_instance_query": (C.c_int, [C.POINTER(AqVbStatus), C.c_int32, C.c_int32, C.POINTER(AqKernelInstance)]),
     "aq_vb_get_elbo_trace": (C.c_int32, [C.c_void_p, ip, dp, C.c_int32]),
     "aq_vb_get_result": (C.c_int, [C.c_void_p, dp, dp, dp, dp, dp, dp, dp, dp, dp]),
     "aq_vb_run_multi": (C.c_int, [C.POINTER(AqVbProblem), C.c_int32, ip, C.c_int32, C.POINTER(AqVbMultiOut)]),

@@ -1,13 +1,5 @@
 // aq_launch_la1wm.hip -- MASK instances (Y with missing values) of the wide sample split (see aq_launch_la1w.hip): no residual
 // tiles on the recurrence wave, as in every MASK instance (aq_launch_la1m.hip).
-#include "aq_launch_la.h"
-#include "aq_core_sweep_la.h"
+#include "aq_launch_la_unit.h"
 
-int aq_la_launch_wide_mask(int NT, unsigned grid, hipStream_t st, const AqCoreArgs &a) {
-#define AQ_LW(NT_) \
-  if (NT == NT_) { hipLaunchKernelGGL((aq_core_sweep_la_kernel<NT_, NT_, false, 1, true, -1, true>), dim3(grid), dim3(512), 0, st, a); return 0; }
-  AQ_LW(1) AQ_LW(2) AQ_LW(3) AQ_LW(4) AQ_LW(5) AQ_LW(6) AQ_LW(7) AQ_LW(8) AQ_LW(9)
-  AQ_LW(10) AQ_LW(11) AQ_LW(12) AQ_LW(13) AQ_LW(14) AQ_LW(15) AQ_LW(16) AQ_LW(17) AQ_LW(18)
-#undef AQ_LW
-  return -1;
-}
+int aq_la_unit_wide_mask(const AqLaRequest &rq, const AqLaRun &run) { return aq_la_unit<1, true, true>(rq, run); }

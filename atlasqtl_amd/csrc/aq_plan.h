@@ -171,13 +171,13 @@ static inline int aq_plan_chain(AqHooks &h, bool mis, int nwg, int nb, int ncu, 
 
 // ---- masked kernel geometry ---------------------------------------------------------------------------------------------------
 static inline void aq_plan_mis(const AqPlanInput &in, AqHooks &h, AqPlan *pl) {
-  // n_pad = 128 NT C: C workgroups per trait tile, NT in {1,2,4,8,16} residual tiles per wave.  Model of a sweep:
+  // n_pad = 128 NT C: C workgroups per trait tile, NT in AQ_MIS_NT residual tiles per wave.  Model of a sweep:
   // whole rounds of workgroups (one per CU) x time per SNP block (4.5 + 0.94 NT us, + 6 us for the exchange)
   {
     const int ntile_ = (in.q + 15) / 16;
     double best = 1e300;
     for (int C = 1; C <= 8; C++)
-      for (int NT = 1; NT <= 16; NT *= 2) {
+      for (int NT : AQ_MIS_NT) {
         if (128 * NT * C < in.n) continue;
         double rounds = (double)(((long long)ntile_ * C + pl->ncu - 1) / pl->ncu);
         double cost = rounds * (4.5 + 0.94 * NT + (C > 1 ? 6.0 : 0.0));
@@ -187,8 +187,9 @@ static inline void aq_plan_mis(const AqPlanInput &in, AqHooks &h, AqPlan *pl) {
   const AqOpt &e = h[AQ_H_MIS_C];   // test hook: force the sample split at small n
   if (e.set && e.v >= 1 && e.v <= 8) {
     pl->misC = e.v;
-    pl->NT = 16;
-    for (int NT = 16; NT >= 1; NT /= 2) if (128 * NT * e.v >= in.n) pl->NT = NT;
+    constexpr int NNT = sizeof AQ_MIS_NT / sizeof *AQ_MIS_NT;
+    pl->NT = AQ_MIS_NT[NNT - 1];
+    for (int i = NNT - 1; i >= 0; i--) if (128 * AQ_MIS_NT[i] * e.v >= in.n) pl->NT = AQ_MIS_NT[i];
   }
   pl->Mmax = std::max(16, aq_round16(in.max_missing));
   if (pl->misC == 1) pl->chain = aq_plan_chain(h, true, pl->ntile, pl->nb, pl->ncu, false);   // same chained-segment choice as for the look-ahead kernel
@@ -198,11 +199,15 @@ static inline void aq_plan_mis(const AqPlanInput &in, AqHooks &h, AqPlan *pl) {
 
 // ---- generic kernel geometry: n_pad = 64 * NE * WPT samples, WPT waves (and workgroups) per trait (tile) ----------------------
 static inline void aq_plan_tw(const AqPlanInput &in, AqHooks &h, AqPlan *pl) {
-  pl->WPT = in.n <= 2048 ? 1 : in.n <= 5120 ? 2 : 4;
+  // the fewest waves whose largest instance holds n (n <= 2048: 1, n <= 5120: 2), else the most; then the smallest NE that does
+  constexpr int NNE = sizeof AQ_TW_NE / sizeof *AQ_TW_NE, NWPT = sizeof AQ_TW_WPT / sizeof *AQ_TW_WPT;
+  pl->WPT = AQ_TW_WPT[NWPT - 1];
+  for (int i = NWPT - 1; i >= 0; i--) if (in.n <= 64 * aq_tw_ne_max(AQ_TW_WPT[i]) * AQ_TW_WPT[i]) pl->WPT = AQ_TW_WPT[i];
   const AqOpt &e = h[AQ_H_TW_WPT];   // test hook
-  if (e.set && (e.v == 2 || e.v == 4) && e.v > pl->WPT) pl->WPT = e.v;
+  if (e.set && aq_tw_built(AQ_TW_NE[0], e.v) && e.v > pl->WPT) pl->WPT = e.v;
   const int per_lane = (in.n + 64 * pl->WPT - 1) / (64 * pl->WPT);
-  pl->NE = per_lane <= 4 ? 4 : per_lane <= 8 ? 8 : per_lane <= 16 ? 16 : per_lane <= 32 ? 32 : 40;
+  pl->NE = AQ_TW_NE[NNE - 1];
+  for (int i = NNE - 1; i >= 0; i--) if (per_lane <= AQ_TW_NE[i]) pl->NE = AQ_TW_NE[i];
   pl->n_pad = 64 * pl->NE * pl->WPT;
   // SNP columns staged in LDS at a time: ns * n_pad doubles next to 18 KB of block scalars, within 160 KB
   pl->tw_ns = 4;
@@ -212,7 +217,8 @@ static inline void aq_plan_tw(const AqPlanInput &in, AqHooks &h, AqPlan *pl) {
 // ---- look-ahead kernel geometry -----------------------------------------------------------------------------------------------
 // 6 matrix waves (NT tiles on waves 0-2, NT2 = NT or NT - 1 on waves 4-6: NT + NT2 per SIMD) + the recurrence wave,
 // which owns aq_la_nt3(NT, TT) tiles of its own when two trait tiles share a workgroup.
-// aq_la_fit: smallest geometry that holds tiles_needed: NT in 1..nt_max, NT2 in {NT, NT - 1}, plus the recurrence wave's aq_la_nt3
+// aq_la_fit: smallest geometry that holds tiles_needed: NT in 1..nt_max (AQ_LA_NT_UNSPLIT or, for a sample split, AQ_LA_NT_SPLIT: the
+// instance set of aq_plan_const.h), NT2 in {NT, NT - 1}, plus the recurrence wave's aq_la_nt3
 // tiles; among equals the one with more tiles on the recurrence wave (AQ_NT3=0/3/6 pins its tile count for experiments).
 // Returns the tile count, 1 << 30 when nothing fits.
 static inline int aq_la_fit(int TT, bool la_mask, const AqOpt &e3, int tiles_needed, int nt_max, int *NTo, int *NT2o, int *N3xo) {
@@ -223,15 +229,11 @@ static inline int aq_la_fit(int TT, bool la_mask, const AqOpt &e3, int tiles_nee
       // n = 1000.  While the recurrence wave's MFMAs hold SIMD 3's datapath the helper wave's fp64 work crawls (38.4 ms at C3
       // against 34.3 for 10 / 9 / 6), so it comes with the helper wave one priority level up (aq_plan_la): 33.9 ms
       // (profiles/r03_nt9_stagger.txt).  AQ_NT3 pins another count; the diagnostic build, whose NT / NT / 9 instances do not
-      // pass the ISA proof, takes it only on request.
-#ifdef AQ_DIAG_TIME
-      const bool x9_ok = TT == 2 && NT >= 8 && NT2 == NT && e3.set && e3.v == 9;
-#else
+      // pass the ISA proof and are not built (AQ_LA_TT2_REC9, aq_plan_const.h), takes it only on request.
       // (by default from NT = 9 on: 8 / 8 / 9 -- n around 900 -- loses to 9 / 8 / 6, 8.68 against 8.42 us per phase; measured per
       // geometry in profiles/r03_nt9_stagger.txt: a phase takes max(matrix SIMDs, SIMD 3) with SIMD 3 at 7.6 - 7.7 us for three or
       // six tiles and 8.7 for nine, the matrix SIMDs at 7.6 / 7.7 / 8.4 / 8.4 / 8.9 / 9.3 / 9.7 / 10.3 us for (8,7) ... (11,11))
-      const bool x9_ok = TT == 2 && NT2 == NT && (e3.set ? (NT >= 8 && e3.v == 9) : NT >= 9);
-#endif
+      const bool x9_ok = TT == 2 && NT2 == NT && (e3.set ? (NT >= AQ_LA_NT_REC && e3.v == 9) : (AQ_LA_TT2_REC9 && NT >= 9));
       for (int x9 = 0; x9 <= (x9_ok ? 1 : 0); x9++) {
         int nt3 = x9 ? 9 : aq_la_nt3(NT, NT2, TT);
         // one tile per workgroup, unsplit (the trait shards of N = 2, 4: MFMA-bound on three SIMDs while SIMD 3 only runs
@@ -239,10 +241,9 @@ static inline int aq_la_fit(int TT, bool la_mask, const AqOpt &e3, int tiles_nee
         // 15.48 -> 14.83; six or nine make its chain + tiles the bound (30 and 33 ms).  AQ_NT3 = 0 / 3 / 6 / 9 pins the count.
         int x1 = -1;
         bool second = false;
-        if (TT == 1 && !la_mask && NT >= 8 && nt_max <= 11) {
+        if (TT == 1 && !la_mask && NT >= AQ_LA_NT_REC && nt_max <= AQ_LA_NT_UNSPLIT) {
           const int w = e3.set ? e3.v : 3;
-          if ((w == 3 || w == 9) && NT2 == NT) x1 = w;
-          else if (w == 6 && NT2 == NT - 1) x1 = w;
+          if ((w == 3 || w == 6 || w == 9) && NT2 == aq_la_rec_nt2(NT, w)) x1 = w;
           else if (e3.set && w != 0) continue;
           if (x1 > 0) nt3 = x1;
           second = !e3.set && x1 > 0;        // by default the plain geometry competes as well (it wins when it needs fewer tiles)
@@ -252,7 +253,7 @@ static inline int aq_la_fit(int TT, bool la_mask, const AqOpt &e3, int tiles_nee
           if (tiles0 >= tiles_needed && tiles0 < best_tiles) { best_tiles = tiles0; best_nt3 = 0; *NTo = NT; *NT2o = NT2; *N3xo = -1; }
         }
         const int tiles = 3 * (NT + NT2) + nt3;
-        if (tiles < tiles_needed || (e3.set && e3.v != nt3 && TT == 2 && NT >= 8)) continue;
+        if (tiles < tiles_needed || (e3.set && e3.v != nt3 && TT == 2 && NT >= AQ_LA_NT_REC)) continue;
         if (tiles < best_tiles || (tiles == best_tiles && nt3 > best_nt3)) { best_tiles = tiles; best_nt3 = nt3; *NTo = NT; *NT2o = NT2; *N3xo = x9 ? 9 : x1; }
       }
     }
@@ -262,7 +263,7 @@ static inline int aq_la_fit(int TT, bool la_mask, const AqOpt &e3, int tiles_nee
 // n <= 1056: one workgroup per trait group holds all samples; with few trait groups the idle CUs share them
 static inline int aq_plan_la_unsplit(AqHooks &h, AqPlan *pl, const AqOpt &e3, int ntiles, std::string *err) {
   pl->laC = 1;
-  const int tiles = aq_la_fit(pl->TT, pl->la_mask, e3, ntiles, 11, &pl->NT, &pl->NT2, &pl->NT3x);    // n <= 1056 always fits (11, 11) ...
+  const int tiles = aq_la_fit(pl->TT, pl->la_mask, e3, ntiles, AQ_LA_NT_UNSPLIT, &pl->NT, &pl->NT2, &pl->NT3x);    // n <= 1056 always fits (11, 11) ...
   if (tiles >= (1 << 30)) return aq_plan_fail(err, AQ_ERR_ARG, "AQ_NT3 excludes every look-ahead geometry for this n");   // ... unless the test hook forbids it
   pl->n_pad = 16 * tiles;
   // Few trait groups (a trait shard of a multi-GPU run, a small q): the CUs left idle share the samples.  Per SNP block an
@@ -275,7 +276,7 @@ static inline int aq_plan_la_unsplit(AqHooks &h, AqPlan *pl, const AqOpt &e3, in
     double best = std::max(0.213 * (pl->NT + pl->NT2) + 1.0, 3.3) * 0.95;   // a split must win by 5 %
     for (int C = 2; C <= 8 && (long long)pl->ntile * C <= pl->ncu; C++) {
       int NT = 0, NT2 = 0, N3x = -1;
-      const int tiles_c = aq_la_fit(pl->TT, pl->la_mask, e3, (ntiles + C - 1) / C, 18, &NT, &NT2, &N3x);
+      const int tiles_c = aq_la_fit(pl->TT, pl->la_mask, e3, (ntiles + C - 1) / C, AQ_LA_NT_SPLIT, &NT, &NT2, &N3x);
       if (tiles_c >= (1 << 30)) continue;
       const double cost = std::max(0.213 * (NT + NT2) + 1.0, 4.5 + 0.2 * (C - 2));
       if (cost < best - 1e-9) { best = cost; pl->laC = C; pl->NT = NT; pl->NT2 = NT2; pl->NT3x = N3x; pl->n_pad = 16 * tiles_c * C; }
@@ -293,7 +294,7 @@ static inline double aq_plan_la_medium(AqPlan *pl, const AqOpt &e3, const AqOpt 
   for (int C = 2; C <= 8; C++) {
     if (ec.set && ec.v != C) continue;
     int NT = 0, NT2 = 0, N3x = -1;
-    const int tiles = aq_la_fit(pl->TT, pl->la_mask, e3, (ntiles + C - 1) / C, 18, &NT, &NT2, &N3x);
+    const int tiles = aq_la_fit(pl->TT, pl->la_mask, e3, (ntiles + C - 1) / C, AQ_LA_NT_SPLIT, &NT, &NT2, &N3x);
     if (tiles >= (1 << 30)) continue;
     const double rounds = (double)(((long long)pl->ntile * C + pl->ncu - 1) / pl->ncu);
     const double cost = rounds * std::max(0.213 * (NT + NT2) + 1.0, 4.5 + 0.2 * (C - 2));
@@ -316,7 +317,7 @@ static inline double aq_plan_la_wide(AqPlan *pl, const AqOpt &ec, int ntiles) {
   for (int C = 9; C <= AQ_LA_CMAX && C <= pl->ncu; C++) {
     if (cf >= 9 && C != cf) continue;
     const int NT = ((ntiles + C - 1) / C + 5) / 6;
-    if (NT > 18) continue;
+    if (NT > AQ_LA_NT_WIDE) continue;
     const double rounds = (double)(((long long)pl->ntile * C + pl->ncu - 1) / pl->ncu);
     const double cost = rounds * std::max(0.213 * 2 * NT + 1.0, helper_us(C));
     if (cost < best - 1e-9) { best = cost; pl->laC = C; pl->NT = NT; pl->NT2 = NT; pl->NT3x = -1; pl->n_pad = 16 * 6 * NT * C; }
@@ -364,7 +365,7 @@ static inline int aq_plan_la(const AqPlanInput &in, AqHooks &h, bool wide, AqPla
   // on another; the split C5 shard 241.1 -> 242.0, complete Y the same within noise: profiles/r03_hprio_na.txt)
   if (pl->la_mask && pl->laC <= 1) pl->la_hprio = 1;
   // six or nine tiles on the recurrence wave of a two-tile workgroup: see aq_la_fit (n = 800, geometry 8 / 7 / 6: 33.5 -> 29.6 ms)
-  if (pl->TT == 2 && pl->NT >= 8 && (pl->NT3x == 9 || (pl->NT3x < 0 && pl->NT2 == pl->NT - 1))) pl->la_hprio = 1;
+  if (pl->TT == 2 && pl->NT >= AQ_LA_NT_REC && (pl->NT3x == 9 || (pl->NT3x < 0 && pl->NT2 == pl->NT - 1))) pl->la_hprio = 1;
   if (h[AQ_H_MPRIO].set) pl->la_mprio = h[AQ_H_MPRIO].v != 0;
   const AqOpt &ehp = h[AQ_H_HPRIO];
   if (ehp.set) pl->la_hprio = ehp.v >= 0 && ehp.v <= 3 ? ehp.v : 0;
@@ -436,7 +437,7 @@ static inline void aq_plan_to_status(const AqPlan &pl, aq_vb_status *st) {
   // the instance aq_launch_core dispatches to (aq_launch_la.h): a wide instance has NT2 == NT and no tiles on the recurrence wave
   st->tiles_matrix = (pl.use_la || pl.use_mis) ? pl.NT : 0;
   st->tiles_matrix2 = pl.use_la ? pl.NT2 : 0;
-  st->tiles_recurrence = (pl.use_la && !pl.la_wide) ? (pl.NT3x > 0 ? pl.NT3x : aq_la_nt3(pl.NT, pl.NT2, pl.TT)) : 0;
+  st->tiles_recurrence = (pl.use_la && !pl.la_wide) ? aq_la_rec_tiles(pl.NT, pl.NT2, pl.TT, pl.NT3x) : 0;
   st->instance_flags = pl.use_la ? (pl.la_mask ? 1 : 0) | (pl.la_wide ? 2 : 0) | (pl.chain > 1 ? 4 : 0) : 0;
   st->n_pad = pl.n_pad;
 }

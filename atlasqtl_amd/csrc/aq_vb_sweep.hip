@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <string>
 #include <vector>
@@ -17,20 +18,68 @@
 
 bool aq_all_equal_1(double c) { return std::fabs(c - 1.0) < 1.5e-8; }   // isTRUE(all.equal(c, 1)), R/update_vb.R:219
 
+// ---- the three core-kernel dispatches ---------------------------------------------------------------------------------------
+// Each walks the instance set of aq_plan_const.h at compile time (aq_first_arm), instantiates what is built and launches the
+// instance a request names -- or, run dry, writes that instance's own template parameters and touches no device:
+// aq_instance_query.  The look-ahead kernel's walk is aq_la_unit (aq_launch_la_unit.h), in its five units.
+struct AqFbRun { const void *args; unsigned ntile; size_t lds; aq_kernel_instance *dry; };   // the two fallback kernels
+
+static int aq_tw_dispatch(int NE, int WPT, const AqFbRun &r) {
+  constexpr int NNE = sizeof AQ_TW_NE / sizeof *AQ_TW_NE, NWPT = sizeof AQ_TW_WPT / sizeof *AQ_TW_WPT;
+  const int rc = aq_first_arm<NNE * NWPT>([&](auto cell) -> int {
+    constexpr int NE_ = AQ_TW_NE[decltype(cell)::value / NWPT], WPT_ = AQ_TW_WPT[decltype(cell)::value % NWPT];
+    if constexpr (aq_tw_built(NE_, WPT_)) {
+      if (NE != NE_ || WPT != WPT_) return -1;
+      if (r.dry) { r.dry->ne = NE_; r.dry->wpt = WPT_; return AQ_OK; }
+      AQ_HIP(hipFuncSetAttribute((const void *)aq_trait_wave_kernel<NE_, WPT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds));
+      hipLaunchKernelGGL((aq_trait_wave_kernel<NE_, WPT_>), dim3(r.ntile * WPT_), dim3(1024), r.lds, 0, *(const AqTwArgs *)r.args);
+      return AQ_OK;
+    }
+    return -1;
+  });
+  return rc >= 0 ? rc : aq_fail(AQ_ERR_UNSUPPORTED, "no generic kernel instantiation for this n");
+}
+
+static int aq_mis_dispatch(int NT, unsigned parts, const AqFbRun &r) {
+  const int rc = aq_first_arm<sizeof AQ_MIS_NT / sizeof *AQ_MIS_NT>([&](auto cell) -> int {
+    constexpr int NT_ = AQ_MIS_NT[decltype(cell)::value];
+    if (NT != NT_) return -1;
+    if (r.dry) { r.dry->nt = NT_; return AQ_OK; }
+    AQ_HIP(hipFuncSetAttribute((const void *)aq_core_sweep_mis_kernel<NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds));
+    hipLaunchKernelGGL((aq_core_sweep_mis_kernel<NT_>), dim3(r.ntile * parts), dim3(512), r.lds, 0, *(const AqMisArgs *)r.args);
+    return AQ_OK;
+  });
+  return rc >= 0 ? rc : aq_fail(AQ_ERR_UNSUPPORTED, "no masked MFMA kernel instantiation for this n");
+}
+
+// the look-ahead request that the instance fields of a status name (aq_plan_to_status wrote them, or a caller of aq_instance_query)
+static AqLaRequest aq_la_request(const aq_vb_status &q) {
+  return {q.tiles_matrix, q.tiles_matrix2, q.tiles_recurrence, q.tiles_per_group, (q.instance_flags & 4) != 0, (q.instance_flags & 1) != 0,
+          (q.instance_flags & 2) != 0};
+}
+static int aq_la_dispatch(const AqLaRequest &rq, unsigned grid, const AqCoreArgs *a, aq_kernel_instance *dry) {
+  if (aq_la_launch(rq, grid, 0, a, dry) != 0) return aq_fail(AQ_ERR_UNSUPPORTED, "no look-ahead kernel instantiation for this n");
+  return AQ_OK;
+}
+
+extern "C" int aq_instance_query(const aq_vb_status *request, int32_t ne, int32_t wpt, aq_kernel_instance *out) {
+  if (!request || !out) return aq_fail(AQ_ERR_ARG, "aq_instance_query: NULL argument");
+  std::memset(out, 0, sizeof(*out));
+  aq_kernel_instance got = {};
+  got.core_kernel = request->core_kernel;
+  if (request->core_kernel == 3) AQ_TRY(aq_mis_dispatch(request->tiles_matrix, 0, AqFbRun{nullptr, 0, 0, &got}));
+  else if (request->core_kernel == 2) AQ_TRY(aq_tw_dispatch(ne, wpt, AqFbRun{nullptr, 0, 0, &got}));
+  else if (request->core_kernel == 0) AQ_TRY(aq_la_dispatch(aq_la_request(*request), 0, nullptr, &got));
+  else return aq_fail(AQ_ERR_ARG, "aq_instance_query: core_kernel is 0 (look-ahead), 2 (generic) or 3 (masked)");
+  *out = got;
+  return AQ_OK;
+}
+
 static int aq_launch_tw(aq_vb *s, int mode, double c) {
   AqTwArgs &t = s->tw_args;
   t.c = c; t.mode = mode;
   size_t lds = (size_t)(s->tw_ns * s->n_pad + 8 * 256 + 32) * sizeof(double);
-#define AQ_TW(NE_, WPT_)                                                                                       \
-  if (s->NE == NE_ && s->WPT == WPT_) {                                                                        \
-    AQ_HIP(hipFuncSetAttribute((const void *)aq_trait_wave_kernel<NE_, WPT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL((aq_trait_wave_kernel<NE_, WPT_>), dim3(s->ntile * WPT_), dim3(1024), lds, 0, t);     \
-  } else
-  AQ_TW(4, 1) AQ_TW(8, 1) AQ_TW(16, 1) AQ_TW(32, 1)
-  AQ_TW(4, 2) AQ_TW(8, 2) AQ_TW(16, 2) AQ_TW(32, 2) AQ_TW(40, 2)
-  AQ_TW(4, 4) AQ_TW(8, 4) AQ_TW(16, 4) AQ_TW(32, 4) AQ_TW(40, 4)
-  { return aq_fail(AQ_ERR_UNSUPPORTED, "no generic kernel instantiation for this n"); }
-#undef AQ_TW
+  AQ_TRY(aq_tw_dispatch(s->NE, s->WPT, AqFbRun{&t, (unsigned)s->ntile, lds, nullptr}));
   AQ_HIP(hipGetLastError());
   return AQ_OK;
 }
@@ -41,14 +90,7 @@ static int aq_launch_mis(aq_vb *s, int mode, double c) {
   t.c = c; t.mode = mode; t.nseg = nseg;
   if (nseg > 1) AQ_HIP(hipMemsetAsync(s->done.get(), 0, (size_t)s->ntile * sizeof(int), 0));
   if (s->misC > 1) AQ_HIP(hipMemsetAsync(s->pflag.get(), 0, (size_t)s->ntile * s->misC * sizeof(int), 0));
-  const size_t lds = aq_mis_lds_bytes(s->Mmax);
-#define AQ_MIS(NT_)                                                                                             \
-  if (s->NT == NT_) {                                                                                          \
-    AQ_HIP(hipFuncSetAttribute((const void *)aq_core_sweep_mis_kernel<NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL((aq_core_sweep_mis_kernel<NT_>), dim3(s->ntile * s->misC * nseg), dim3(512), lds, 0, t); \
-  } else
-  AQ_MIS(1) AQ_MIS(2) AQ_MIS(4) AQ_MIS(8) AQ_MIS(16) { return aq_fail(AQ_ERR_UNSUPPORTED, "no masked MFMA kernel instantiation for this n"); }
-#undef AQ_MIS
+  AQ_TRY(aq_mis_dispatch(s->NT, (unsigned)(s->misC * nseg), AqFbRun{&t, (unsigned)s->ntile, aq_mis_lds_bytes(s->Mmax), nullptr}));
   if (nseg > 1)
     hipLaunchKernelGGL(aq_k_combine_segment_sums6, dim3((s->q_pad + 255) / 256), dim3(256), 0, 0, s->sums.get(), s->q_pad, nseg);
   if (s->misC > 1)
@@ -120,10 +162,11 @@ static int aq_launch_core(aq_vb *s, int mode, double c) {
     const unsigned grid = chained ? (unsigned)((long long)s->chain * nwg) : nwg * (unsigned)s->laC;
     // One instance per handle for annealed and post-annealing sweeps alike: with the probit tables an annealed entry costs the
     // same three polynomials as any other (round 2 swapped to a (NT, NT, 3) geometry for the annealed sweeps).
-    int lrc = s->la_wide ? (s->la_mask ? aq_la_launch_wide_mask(s->NT, grid, 0, a) : aq_la_launch_wide(s->NT, grid, 0, a))
-              : s->la_mask ? aq_la_launch_mask(s->NT, s->NT2, s->NT3x, chained, grid, 0, a)
-              : s->TT == 2 ? aq_la_launch_tt2(s->NT, s->NT2, s->NT3x, chained, grid, 0, a) : aq_la_launch_tt1(s->NT, s->NT2, s->NT3x, chained, grid, 0, a);
-    if (lrc != 0) return aq_fail(AQ_ERR_UNSUPPORTED, "no look-ahead kernel instantiation for this n");
+    aq_vb_status st;
+    aq_plan_to_status(*s, &st);            // the instance in the terms of aq_vb_status ...
+    AqLaRequest rq = aq_la_request(st);
+    rq.seg = chained;                      // ... but for SEG: the ELBO-only launch (mode 1) of a chained plan is not chained
+    AQ_TRY(aq_la_dispatch(rq, grid, &a, nullptr));
     if (chained) {
       if (s->la_mask) hipLaunchKernelGGL(aq_k_combine_segment_sums6, dim3((s->q_pad + 255) / 256), dim3(256), 0, 0, s->sums.get(), s->q_pad, s->chain);
       else hipLaunchKernelGGL(aq_k_combine_segment_sums, dim3((s->q_pad + 255) / 256), dim3(256), 0, 0, s->sums.get(), s->q_pad, s->chain);

@@ -232,6 +232,20 @@ int32_t aq_vb_get_overrides(aq_vb_handle h, char *buf, int32_t cap);
 int aq_plan_query(int32_t n, int32_t p, int32_t q, int32_t max_missing, int32_t max_short_list, int32_t ncu, int64_t total_bytes,
                   const char *overrides, aq_vb_status *out);
 
+/* Which compiled template instance of a core kernel a launch request reaches, without a launch and without a device: the
+ * launchers' own dispatch, run dry.  The request is read from the instance fields of *request as aq_vb_get_status and
+ * aq_plan_query fill them: core_kernel; for the look-ahead kernel (0) tiles_matrix, tiles_matrix2, tiles_recurrence,
+ * tiles_per_group and instance_flags; for the masked kernel (3) tiles_matrix; for the generic kernel (2), whose status names
+ * no instance, the arguments ne (samples per lane) and wpt (waves per trait).  On AQ_OK *out holds the template parameters of
+ * the kernel that would be launched -- its own, not a copy of the request -- and zeroes for the other kernels' fields;
+ * AQ_ERR_UNSUPPORTED, with the launcher's own message, when no instance is compiled for the request.  No GPU needed. */
+typedef struct aq_kernel_instance {
+  int32_t core_kernel;                    /* 0 look-ahead, 2 generic, 3 masked                                            */
+  int32_t nt, nt2, seg, tt, mask, nt3, wide;   /* look-ahead kernel: NT, NT2, SEG, TT, MASK, the resolved NT3, WIDE; masked kernel: nt */
+  int32_t ne, wpt;                        /* generic kernel: NE, WPT                                                       */
+} aq_kernel_instance;
+int aq_instance_query(const aq_vb_status *request, int32_t ne, int32_t wpt, aq_kernel_instance *out);
+
 /* ELBO trace: up to cap (iteration, value) pairs in evaluation order; returns the count. */
 int32_t aq_vb_get_elbo_trace(aq_vb_handle h, int32_t *it_out, double *lb_out, int32_t cap);
 

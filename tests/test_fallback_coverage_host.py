@@ -1,8 +1,8 @@
 """CPU: the tables of tests/test_gpu_fallback_instances.py against the launch planner and the launch code.
 
-  * the generic instances the tables claim are exactly the AQ_TW list of aq_vb_sweep.hip, each for complete Y and for NA, and
-    all three staging widths ns; the masked tables name every NT of the AQ_MIS list: an instance added to a list fails here
-    until a case runs it;
+  * the generic instances the tables claim are exactly those the library compiles (aq_instance_query), each for complete Y and
+    for NA, and all three staging widths ns; the masked tables name every compiled NT: an instance added to the set
+    (aq_plan_const.h) fails here until a case runs it;
   * every row is planned as written (aq_plan_query, 256 CUs, with the missingness counts of the case's own Y): the fields
     the GPU case asserts from its handle;
   * the (NT, C) pairs of the masked kernel that are planned for some n <= 10 240 -- all 40, by a sweep of aq_plan_query over
@@ -11,7 +11,6 @@
     of every G row comes from the planner itself: tests/tools/plan_probe.cpp, built with the host compiler."""
 import functools
 import os
-import re
 import shutil
 import subprocess
 
@@ -27,12 +26,8 @@ PLAIN = {"tiles_per_group": 1, "tiles_matrix2": 0, "tiles_recurrence": 0, "insta
 
 
 def _listed():
-    with open(os.path.join(PH.CSRC, "aq_vb_sweep.hip")) as f:
-        src = f.read()
-    tw = [(int(a), int(b)) for a, b in re.findall(r"\bAQ_TW\((\d+),\s*(\d+)\)", src)]
-    mis = [int(a) for a in re.findall(r"\bAQ_MIS\((\d+)\)", src)]
-    assert len(set(tw)) == len(tw) and len(set(mis)) == len(mis)
-    return set(tw), set(mis)
+    """(generic (NE, WPT), masked NT) the library compiles: aq_instance_query over a box of requests (tests/test_plan_host.py)."""
+    return PH.compiled(2), {nt for nt, in PH.compiled(3)}
 
 
 @functools.lru_cache(maxsize=None)
@@ -68,7 +63,7 @@ def _generic_rows():
 
 
 def test_generic_tables_name_exactly_the_compiled_instances():
-    """An instance added to (or taken from) the AQ_TW list fails here until the tables follow."""
+    """An instance added to (or taken from) the compiled set fails here until the tables follow."""
     compiled, _ = _listed()
     generic, ns, _, _ = F.ledger()
     assert len(compiled) == 14

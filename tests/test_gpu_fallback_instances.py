@@ -26,7 +26,7 @@ lands elsewhere fails -- and then holds the run to the parity bars of tests/test
 
 aq_vb_status reports only n_pad for the generic kernel, and three instances share n_pad = 1024:
 tests/test_fallback_coverage_host.py proves (NE, WPT, ns) of every G row from the planner itself, checks every row against
-aq_plan_query, and holds the tables to the AQ_TW and AQ_MIS lists of aq_vb_sweep.hip."""
+aq_plan_query, and holds the tables to the instances the library compiles (aq_instance_query)."""
 import functools
 
 import numpy as np

@@ -4,10 +4,10 @@ oracle (which works in Gram space, so its cost does not grow with n).
 aq_core_sweep_la_kernel is compiled once per residual-tile geometry, each instance with a register allocation and a load
 schedule of its own.  The ISA proof (tools/check_isa_operands.py) shows that no instance has a load hazard; only a run shows
 that it computes the right numbers.  The families below walk
-  a / b  the medium split's geometries 12/11 ... 18/18 (AQ_LB of aq_launch_la1.hip and aq_launch_la1m.hip), forced at small n
+  a / b  the medium split's geometries 12/11 ... 18/18 (the split-only instances of aq_launch_la1.hip and aq_launch_la1m.hip), forced at small n
          and as the planner picks them for 8448 < n <= 10 240 and for a shard of many traits; and the split exchange inside
-         the geometries 1/1 ... 11/11 (AQ_LA of the same files), forced by the same rule,
-  c      the wide split's NT = 1 ... 18 (AQ_LW of aq_launch_la1w.hip and aq_launch_la1wm.hip),
+         the geometries 1/1 ... 11/11 (the unsplit launches' instances in the same units), forced by the same rule,
+  c      the wide split's NT = 1 ... 18 (the WIDE instances of aq_launch_la1w.hip and aq_launch_la1wm.hip),
   d      every part count C = 9 ... 48 of split_exchange_wide (17 lane layouts, some with a dead last chunk),
   e      the geometric limit n = 82 944 = AQ_N_MAX: 48 parts of 18/18, no padding anywhere.
 Every case first asserts, from aq_vb_get_status, that the handle launches the instance the case was written for -- a plan that
@@ -33,7 +33,7 @@ MEDIUM_FORCED = {23: (12, 11), 24: (12, 12), 25: (13, 12), 26: (13, 13), 27: (14
                  30: (15, 15), 31: (16, 15), 32: (16, 16), 33: (17, 16), 34: (17, 17), 35: (18, 17), 36: (18, 18)}
 MEDIUM_NA = 0.05
 MEDIUM_XHELPER_BOTH = (23, 30, 36)     # these also run with the exchange on the helper wave (AQ_LA_XHELPER = 1)
-# ... and the same rule below the AQ_LB list: the AQ_LA instances 1/1 ... 11/11 of the unsplit launches (which
+# ... and the same rule below the split-only instances: the instances 1/1 ... 11/11 of the unsplit launches (which
 # tests/test_gpu_unsplit_instances.py runs unsplit), here in two parts: the exchange is a runtime path inside them
 MEDIUM_FORCED_SMALL = {2: (1, 1), 3: (2, 1), 4: (2, 2), 5: (3, 2), 6: (3, 3), 7: (4, 3), 8: (4, 4), 9: (5, 4), 10: (5, 5), 11: (6, 5),
                        12: (6, 6), 13: (7, 6), 14: (7, 7), 15: (8, 7), 16: (8, 8), 17: (9, 8), 18: (9, 9), 19: (10, 9), 20: (10, 10),
@@ -200,7 +200,7 @@ def _check(family, prob, instance, maxit=SHORT, n_pad=None, keep=False, assert_i
 @pytest.mark.parametrize("na", [0.0, MEDIUM_NA])
 @pytest.mark.parametrize("k", sorted(MEDIUM_FORCED))
 def test_medium_split_every_geometry_matches_oracle(k, na, monkeypatch):
-    """The 14 AQ_LB geometries 12/11 ... 18/18 in two parts, complete Y and MASK, exchange on the recurrence wave: whole run."""
+    """The 14 split-only geometries 12/11 ... 18/18 in two parts, complete Y and MASK, exchange on the recurrence wave: whole run."""
     monkeypatch.setenv("AQ_LA_C", "2")
     monkeypatch.setenv("AQ_LA_XHELPER", "0")
     nt, nt2 = MEDIUM_FORCED[k]
@@ -224,7 +224,7 @@ def test_medium_split_exchange_on_helper_wave_matches_oracle(k, na, monkeypatch)
 @pytest.mark.parametrize("na", [0.0, MEDIUM_NA])
 @pytest.mark.parametrize("k", sorted(MEDIUM_FORCED_SMALL))
 def test_medium_split_every_small_geometry_matches_oracle(k, na, monkeypatch):
-    """The 21 AQ_LA geometries 1/1 ... 11/11 in two parts, complete Y and MASK, exchange on the recurrence wave: the ladder and
+    """The 21 geometries 1/1 ... 11/11 in two parts, complete Y and MASK, exchange on the recurrence wave: the ladder and
     two ELBO evaluations."""
     monkeypatch.setenv("AQ_LA_C", "2")
     monkeypatch.setenv("AQ_LA_XHELPER", "0")
@@ -266,7 +266,7 @@ def test_medium_split_as_planned_matches_oracle(shape, plan, monkeypatch):
     assert mm <= MIS_MMAX, mm     # beyond it the host rightly plans the generic kernel
     if _pin_256_cus(monkeypatch):
         _check("b", prob, (MASK if na else 0, C, nt, nt2), maxit=maxit)
-    else:   # fewer CUs than the tables assume: whatever the planner picks must still be one of the AQ_LB instances
+    else:   # fewer CUs than the tables assume: whatever the planner picks must still be one of the split-only instances
         got = _check("b", prob, None, maxit=maxit)
         st = got["status"]
         assert st["core_kernel"] == 0 and st["instance_flags"] == (MASK if na else 0) and st["tiles_matrix"] >= 12

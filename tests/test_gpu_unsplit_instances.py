@@ -37,11 +37,11 @@ N_TOP = 1051                     # 66 tiles, the last with 11 of 16 samples
 NA = 0.05                        # U4
 CHAIN = (0, 3)                   # AQ_CHAIN of the plain and of the chained case
 
-# NT + NT2 = k -> (NT, NT2): the AQ_LA lists
+# NT + NT2 = k -> (NT, NT2): the pairs of the instance set, NT = 1 ... 11 (aq_plan_const.h)
 PAIRS = {2: (1, 1), 3: (2, 1), 4: (2, 2), 5: (3, 2), 6: (3, 3), 7: (4, 3), 8: (4, 4), 9: (5, 4), 10: (5, 5), 11: (6, 5), 12: (6, 6),
          13: (7, 6), 14: (7, 7), 15: (8, 7), 16: (8, 8), 17: (9, 8), 18: (9, 9), 19: (10, 9), 20: (10, 10), 21: (11, 10), 22: (11, 11)}
-# (NT, NT2, NT3) with tiles on the recurrence wave: AQ_L3 of aq_launch_la1.hip; with TT = 2 aq_la_nt3 (three tiles for NT / NT,
-# six for NT / NT - 1) and aq_la_go9 of aq_launch_la2.hip.  AQ_NT3 = NT3 selects each.  (11/11/9 is not here: UNREACHABLE.)
+# (NT, NT2, NT3) with tiles on the recurrence wave: the forms 3, 6, 9 of aq_launch_la1.hip; with TT = 2 aq_la_nt3 (three tiles for NT / NT,
+# six for NT / NT - 1) and NT / NT / 9 of aq_launch_la2.hip.  AQ_NT3 = NT3 selects each.  (11/11/9 is not here: UNREACHABLE.)
 RECURRENCE = [(8, 8, 3), (8, 7, 6), (8, 8, 9), (9, 9, 3), (9, 8, 6), (9, 9, 9), (10, 10, 3), (10, 9, 6), (10, 10, 9), (11, 11, 3), (11, 10, 6)]
 U3_PLAIN_K = tuple(range(2, 15))     # TT = 2 without tiles on the recurrence wave: NT <= 7
 

@@ -198,13 +198,11 @@ def test_split_instance_ledger_is_complete():
     """tests/test_gpu_split_instances.py claims to run every sample-split instance of the look-ahead kernel and every part count
     of the wide exchange against the oracle.  Its tables must name the complete set -- wide: NT = 1 ... 18, medium split: NT =
     12 ... 18 with NT2 in {NT, NT - 1}, each for complete Y and MASK; C = 9 ... 48 -- and that set must be the one the launch
-    files compile: an instance added to an AQ_LB / AQ_LW list fails here until a case runs it.  So must the split inside the
-    geometries of the unsplit launches, NT = 1 ... 11 of AQ_LA (MEDIUM_FORCED_SMALL)."""
-    import os
-    import re
+    units compile: an instance added to the set (aq_plan_const.h) fails here until a case runs it.  So must the split inside the
+    geometries of the unsplit launches, NT = 1 ... 11 (MEDIUM_FORCED_SMALL)."""
     from tests import test_gpu_split_instances as T
     medium_all, wide, parts = T.ledger()
-    # below the AQ_LB list the split runs inside the AQ_LA instances of the unsplit launches (NT <= 11): every one of them too
+    # below the split-only instances (NT >= 12) the split runs inside those of the unsplit launches (NT <= 11): every one of them too
     medium, medium_small = {g for g in medium_all if g[1] >= 12}, {g for g in medium_all if g[1] <= 11}
     want_small = {(m, nt, nt2) for m in (0, 1) for nt in range(1, 12) for nt2 in (nt, nt - 1) if nt2 >= 1}
     assert medium_small == want_small and len(want_small) == 42, sorted(want_small ^ medium_small)
@@ -232,15 +230,10 @@ def test_split_instance_ledger_is_complete():
     assert {layout(C) for C in T.PARTS_NA_C} == {layout(C) for C in range(9, 49)}
     assert len({layout(C) for C in range(9, 49)}) == 17
     assert any(layout(C)[2] for C in T.PARTS_WHOLE_C) and any(layout(C)[2] for C in T.PARTS_TWICE_C)
-    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "atlasqtl_amd", "csrc")
-
-    def listed(name, macro):
-        with open(os.path.join(csrc, name)) as f:
-            src = f.read()
-        body = src.split("#define " + macro + "(NT_)", 1)[1].split("#undef " + macro, 1)[0]
-        return sorted(int(x) for x in re.findall(macro + r"\((\d+)\)", body))
-    for name in ("aq_launch_la1.hip", "aq_launch_la1m.hip"):
-        assert listed(name, "AQ_LB") == sorted({nt for _, nt, _ in medium}), name
-        assert listed(name, "AQ_LA") == sorted({nt for _, nt, _ in medium_small}), name
-    for m, name in ((0, "aq_launch_la1w.hip"), (1, "aq_launch_la1wm.hip")):
-        assert listed(name, "AQ_LW") == sorted(nt for mm, nt in wide if mm == m), name
+    # ... and that is what the library compiles (aq_instance_query over a box of requests, tests/test_plan_host.py): one tile per
+    # workgroup, no tiles on the recurrence wave; the split never launches chained
+    from tests.test_plan_host import compiled
+    la = {k for k in compiled(0) if k[2] == 1 and k[5] == 0 and k[6] == 0}       # (mask, wide, TT, NT, NT2, NT3, seg)
+    assert {(m, nt, nt2) for m, w, _tt, nt, nt2, _nt3, _seg in la if not w} == medium | medium_small
+    assert {(m, nt) for m, w, _tt, nt, nt2, _nt3, _seg in la if w and nt2 == nt} == wide and not [k for k in la if k[1] and k[4] != k[3]]
+    assert not [k for k in compiled(0) if k[6] and (k[1] or k[3] >= 12)]          # no chained wide or 12 ... 18 instance

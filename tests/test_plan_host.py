@@ -5,8 +5,12 @@
     fields, or the same error;
   * the tables of expected plans of tests/test_gpu_split_instances.py hold at 256 CUs;
   * invariants over a sweep of n from 2 to AQ_N_MAX: the plan succeeds, n_pad follows the geometry of its kernel, the parts of
-    a split fit the chip, a split is never chained, and the instance is one the launch files compile."""
+    a split fit the chip, a split is never chained, and the instance is one the library compiles;
+  * what the library compiles, and which kernel a request reaches: aq_instance_query (the launchers' own dispatch, run dry) over
+    a box of requests that strictly contains the compiled set -- the source of every other module's "compiled" set."""
 import ctypes as C
+import functools
+import itertools
 import json
 import os
 import re
@@ -136,57 +140,86 @@ def test_limit_table(hiplib):
 # ------------------------------------------------------------------------------------------------------------------------------
 # invariants over n
 
-def _listed(name, macro):
-    with open(os.path.join(CSRC, name)) as f:
-        src = f.read()
-    body = src.split("#define " + macro + "(NT_)", 1)[1].split("#undef " + macro, 1)[0]
-    return {int(x) for x in re.findall(macro + r"\((\d+)\)", body)}
+LA_FIELDS = ("nt", "nt2", "seg", "tt", "mask", "nt3", "wide")
+NO_INSTANCE = {0: "no look-ahead kernel instantiation for this n", 2: "no generic kernel instantiation for this n",
+               3: "no masked MFMA kernel instantiation for this n"}
 
 
-def _compiled():
-    """The instances the launch files compile, as a predicate on (flags, TT, NT, NT2, NT3) of a status."""
-    la1 = {m: _listed("aq_launch_la1.hip", m) for m in ("AQ_L3", "AQ_LA", "AQ_LB")}
-    la1m = {m: _listed("aq_launch_la1m.hip", m) for m in ("AQ_LA", "AQ_LB")}
-    la2 = _listed("aq_launch_la2.hip", "AQ_LA")
-    with open(os.path.join(CSRC, "aq_launch_la2.hip")) as f:
-        la2_9 = {int(x) for x in re.findall(r"case (\d+): aq_la_go9<\1>", f.read())}
-    wide = {0: _listed("aq_launch_la1w.hip", "AQ_LW"), MASK: _listed("aq_launch_la1wm.hip", "AQ_LW")}
-    assert la1["AQ_L3"] and la1["AQ_LB"] and la2_9 and wide[0] and wide[MASK]
+def resolve(hiplib, request, ne=0, wpt=0):
+    """aq_instance_query: the launchers' own dispatch, run dry.  The resolved instance as a dict of aq_kernel_instance, or None
+    when the launch path refuses the request -- which it must do as AQ_ERR_UNSUPPORTED, in the launcher's words."""
+    out = _lib.AqKernelInstance()
+    rc = hiplib.aq_instance_query(C.byref(request), ne, wpt, C.byref(out))
+    if rc:
+        assert rc == 3 and hiplib.aq_last_error().decode() == NO_INSTANCE[request.core_kernel], (rc, hiplib.aq_last_error())
+        assert bytes(out) == bytes(C.sizeof(out))                   # nothing but zeroes on refusal
+        return None
+    return {k: getattr(out, k) for k, _t in _lib.AqKernelInstance._fields_}
 
-    def pair(NT, NT2):
-        return NT2 == NT or (NT2 == NT - 1 and NT > 1)
 
-    def ok(flags, TT, NT, NT2, NT3):
-        seg = bool(flags & SEG)
-        if flags & WIDE:
-            return TT == 1 and not seg and NT2 == NT and NT3 == 0 and NT in wide[flags & MASK]
-        if flags & MASK:
-            return TT == 1 and NT3 == 0 and pair(NT, NT2) and (NT in la1m["AQ_LA"] or (not seg and NT in la1m["AQ_LB"]))
-        if TT == 2:
-            if NT3 == 9:
-                return NT2 == NT and NT in la2_9
-            return pair(NT, NT2) and NT in la2 and NT3 == ((3 if NT2 == NT else 6) if NT >= 8 else 0)      # aq_la_nt3
-        if NT3 > 0:
-            return NT in la1["AQ_L3"] and ((NT3 in (3, 9) and NT2 == NT) or (NT3 == 6 and NT2 == NT - 1))
-        return pair(NT, NT2) and (NT in la1["AQ_LA"] or (not seg and NT in la1["AQ_LB"]))
-    return ok
+def la_request(mask, wide, TT, NT, NT2, NT3, seg):
+    return _lib.AqVbStatus(core_kernel=0, instance_flags=(MASK if mask else 0) | (WIDE if wide else 0) | (SEG if seg else 0),
+                           tiles_per_group=TT, tiles_matrix=NT, tiles_matrix2=NT2, tiles_recurrence=NT3)
+
+
+@functools.lru_cache(maxsize=None)
+def instance_box():
+    """Every request of a box that strictly contains the compiled set -> what it resolves to (None: refused).  Look-ahead
+    kernel: (0, mask, wide, TT, NT, NT2, NT3, seg) over mask, wide, seg in 0/1, TT in 1 ... 3 (3 must be refused), NT and NT2 in
+    0 ... 20, NT3 in 0, 3, 6, 9; generic kernel: (2, NE, WPT) over 1 ... 64 x 1 ... 8; masked kernel: (3, NT) over 1 ... 32."""
+    hiplib = _lib.lib()
+    box = {}
+    for mask, wide, TT, seg in itertools.product((0, 1), (0, 1), (1, 2, 3), (0, 1)):
+        for NT, NT2, NT3 in itertools.product(range(21), range(21), (0, 3, 6, 9)):
+            box[(0, mask, wide, TT, NT, NT2, NT3, seg)] = resolve(hiplib, la_request(mask, wide, TT, NT, NT2, NT3, seg))
+    for ne, wpt in itertools.product(range(1, 65), range(1, 9)):
+        box[(2, ne, wpt)] = resolve(hiplib, _lib.AqVbStatus(core_kernel=2), ne, wpt)
+    for nt in range(1, 33):
+        box[(3, nt)] = resolve(hiplib, _lib.AqVbStatus(core_kernel=3, tiles_matrix=nt))
+    return box
+
+
+def compiled(kernel):
+    """The accepted requests of one kernel, without the kernel id: what the library compiles."""
+    return {k[1:] for k, v in instance_box().items() if k[0] == kernel and v is not None}
 
 
 def compiled_unsplit():
-    """The kernels the three launch files of the unsplit launches compile from AQ_LA, AQ_L3 and aq_la_go9, each plain and
-    chained: (mask, TT, NT, NT2, NT3, seg), NT3 as aq_vb_status reports it (aq_la_nt3 of a two-tile workgroup).  (AQ_LB is the
-    split's: tests/test_host_logic.py::test_split_instance_ledger_is_complete.)"""
-    def pairs(nts):
-        return {(nt, nt2) for nt in nts for nt2 in (nt, nt - 1) if nt2 >= 1}
-    with open(os.path.join(CSRC, "aq_launch_la2.hip")) as f:
-        go9 = {int(x) for x in re.findall(r"case (\d+): aq_la_go9<\1>", f.read())}
-    geo = {(0, 1, nt, nt2, 0) for nt, nt2 in pairs(_listed("aq_launch_la1.hip", "AQ_LA"))}
-    for nt in _listed("aq_launch_la1.hip", "AQ_L3"):
-        geo |= {(0, 1, nt, nt, 3), (0, 1, nt, nt - 1, 6), (0, 1, nt, nt, 9)}
-    geo |= {(0, 2, nt, nt2, (3 if nt2 == nt else 6) if nt >= 8 else 0) for nt, nt2 in pairs(_listed("aq_launch_la2.hip", "AQ_LA"))}
-    geo |= {(0, 2, nt, nt, 9) for nt in go9}
-    geo |= {(1, 1, nt, nt2, 0) for nt, nt2 in pairs(_listed("aq_launch_la1m.hip", "AQ_LA"))}
-    return {g + (seg,) for g in geo for seg in (0, 1)}
+    """The kernels of the unsplit launches, each plain and chained: (mask, TT, NT, NT2, NT3, seg), NT3 as aq_vb_status reports it
+    (aq_la_nt3 of a two-tile workgroup) -- every compiled instance that is not WIDE and exists chained as well.  (The others are
+    the split's: tests/test_host_logic.py::test_split_instance_ledger_is_complete.)"""
+    la = compiled(0)
+    return {(m, TT, NT, NT2, NT3, seg) for m, w, TT, NT, NT2, NT3, seg in la if not w and (m, w, TT, NT, NT2, NT3, 1) in la}
+
+
+def test_every_request_resolves_to_itself_or_is_refused():
+    """For every request of the box the library accepts, the template parameters of the kernel it would launch are the request's,
+    one by one; what it refuses, it refuses as the launch does (resolve()).  222 + 14 + 5 are accepted."""
+    box = instance_box()
+    assert len(box) == 2 * 2 * 3 * 2 * 21 * 21 * 4 + 64 * 8 + 32
+    wrong = []
+    for key, got in box.items():
+        if got is None:
+            continue
+        if key[0] == 0:
+            _, mask, wide, TT, NT, NT2, NT3, seg = key
+            want = dict(core_kernel=0, nt=NT, nt2=NT2, seg=seg, tt=TT, mask=mask, nt3=NT3, wide=wide, ne=0, wpt=0)
+        elif key[0] == 2:
+            want = dict(core_kernel=2, nt=0, nt2=0, seg=0, tt=0, mask=0, nt3=0, wide=0, ne=key[1], wpt=key[2])
+        else:
+            want = dict(core_kernel=3, nt=key[1], nt2=0, seg=0, tt=0, mask=0, nt3=0, wide=0, ne=0, wpt=0)
+        if got != want:
+            wrong.append((key, got))
+    assert not wrong, f"{len(wrong)} requests reach another kernel, first: {wrong[:3]}"
+    la = compiled(0)
+    unit = {name: sum(1 for m, w, TT, *_ in la if (m, w, TT) == key)
+            for name, key in (("la1", (0, 0, 1)), ("la2", (0, 0, 2)), ("la1m", (1, 0, 1)), ("la1w", (0, 1, 1)), ("la1wm", (1, 1, 1)))}
+    assert unit == {"la1": 80, "la2": 50, "la1m": 56, "la1w": 18, "la1wm": 18} and len(la) == 222
+    assert len(compiled(2)) == 14 and len(compiled(3)) == 5
+    assert not [k for k in la if k[2] == 3]                          # TT = 3: never
+    # an unknown kernel is an argument error, not a refusal
+    assert _lib.lib().aq_instance_query(C.byref(_lib.AqVbStatus(core_kernel=1)), 0, 0, C.byref(_lib.AqKernelInstance())) == 1
+    assert _lib.lib().aq_instance_query(None, 0, 0, C.byref(_lib.AqKernelInstance())) == 1
 
 
 def _sweep_n():
@@ -197,15 +230,14 @@ def _sweep_n():
 @pytest.mark.parametrize("na", [0.0, 0.04], ids=["complete", "na"])
 @pytest.mark.parametrize("q", [33, 5000])
 def test_plan_invariants_over_n(hiplib, q, na, ncu):
-    ok = _compiled()
     p = 48
-    tw_pads = {64 * ne * w for ne in (4, 8, 16, 32, 40) for w in (1, 2, 4)}
+    tw_pads = {64 * ne * w for ne, w in compiled(2)}
     kernels = set()
     for n in _sweep_n():
         mm, ms = _missing(n, na)
         if na and mm == 0:
             mm = ms = 1
-        rc, msg, st, _ = _query(hiplib, n, p, q, mm, ms, ncu, MEM, {})
+        rc, msg, st, request = _query(hiplib, n, p, q, mm, ms, ncu, MEM, {})
         assert rc == 0, (n, msg)
         k, parts, NT, NT2, NT3 = st["core_kernel"], st["split_parts"], st["tiles_matrix"], st["tiles_matrix2"], st["tiles_recurrence"]
         flags, TT = st["instance_flags"], st["tiles_per_group"]
@@ -217,14 +249,16 @@ def test_plan_invariants_over_n(hiplib, q, na, ncu):
         if k == 0:
             tiles = 6 * NT if flags & WIDE else 3 * (NT + NT2) + NT3
             assert st["n_pad"] == 16 * parts * tiles, (n, st)
-            assert ok(flags, TT, NT, NT2, NT3), (n, st)
+            got = resolve(hiplib, request)                          # the instance is one the library compiles: this one
+            assert got and tuple(got[f] for f in LA_FIELDS) == (NT, NT2, int(bool(flags & SEG)), TT, int(bool(flags & MASK)), NT3,
+                                                                int(bool(flags & WIDE))), (n, st, got)
             assert bool(flags & SEG) == (st["chain_segments"] > 1) and bool(flags & MASK) == bool(na), (n, st)
             assert bool(flags & WIDE) == (n > 10240) and (parts >= 9) == (n > 10240), (n, st)
             if parts > 1 and n <= 1056:
                 assert TT == 1 and parts * ((q + 15) // 16) <= ncu, (n, st)
         elif k == 3:
             assert st["n_pad"] == 128 * NT * parts and NT in (1, 2, 4, 8, 16) and parts <= 8, (n, st)
-            assert (NT2, NT3, flags, TT) == (0, 0, 0, 1), (n, st)
+            assert (NT2, NT3, flags, TT) == (0, 0, 0, 1) and resolve(hiplib, request)["nt"] == NT, (n, st)
         else:
             assert k == 2 and st["n_pad"] in tw_pads and (parts, NT, NT2, NT3, flags, TT) == (1, 0, 0, 0, 0, 1), (n, st)
     assert 0 in kernels

@@ -1,8 +1,8 @@
 """CPU: the tables of tests/test_gpu_unsplit_instances.py (and MEDIUM_FORCED_SMALL of tests/test_gpu_split_instances.py) against
-the launch planner and the launch files.
+the launch planner and the compiled instance set.
 
   * every row is planned as written, on 256 and on 64 CUs;
-  * the kernels the tables claim are the ones the launch files compile, minus UNREACHABLE;
+  * the kernels the tables claim are the ones the library compiles (aq_instance_query), minus UNREACHABLE;
   * a sweep of the planner over n = 1 ... 1056 and its hooks reaches exactly the claimed kernels and none of UNREACHABLE;
   * every wave that owns tiles owns a live one, but for RECURRENCE_TILES_ALL_PADDING."""
 import functools
@@ -82,7 +82,7 @@ def test_every_small_medium_row_is_planned_as_written(hiplib):
 
 
 def test_claimed_kernels_are_the_compiled_ones_but_the_unreachable():
-    """An instance added to AQ_LA, AQ_L3 or aq_la_go9 fails here until a case runs it."""
+    """An instance added to the compiled set (aq_plan_const.h) fails here until a case runs it."""
     compiled, claimed, unreachable = PH.compiled_unsplit(), U.ledger(), set(U.UNREACHABLE)
     assert len(compiled) == 158 and len(unreachable) == 4 and all(U.UNREACHABLE.values())
     assert unreachable == {(0, tt, 11, 11, 9, seg) for tt in (1, 2) for seg in (0, 1)}
