@@ -130,6 +130,22 @@ __device__ __forceinline__ void aq_wait2n(aq_v2 &d0, aq_v2 &d1) {   // the same 
   asm volatile("s_waitcnt vmcnt(%2)" : "+v"(d0), "+v"(d1) : "n"(N));
 }
 
+// One word of the residual R.  COH (the chained instances): as an agent-scope relaxed atomic -- global_load / global_store with
+// sc1: the load is served past the CU's vector L1, the store is written through to the level every XCD reads -- so that the
+// residual passes from one segment's workgroup to the next without a fence (see the hand-over at the end of the kernel).
+// Otherwise a plain access.
+template <bool COH>
+__device__ __forceinline__ double aq_r_load(const double *p) {
+  if constexpr (COH) return __hip_atomic_load(const_cast<double *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else return *p;
+}
+template <bool COH>
+__device__ __forceinline__ void aq_r_store(double *p, double v) {
+  // (through a global-address-space pointer: where the compiler has lost track of the space it would issue a flat store)
+  if constexpr (COH) __hip_atomic_store((__attribute__((address_space(1))) double *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *p = v;
+}
+
 // Operand prefetch with D buffers per stream (tile k in buffer k % D).  Request order of a phase: the tiles left dangling by the
 // phase before -- [XU0 XA0 XU1 XA1 ...], XU up to tile D-2, XA up to D-3 -- then per step t: XU(t+D-1), XA(t+D-2) while they
 // exist.  aq_req_index = position of a request in that order, aq_req_issued = requests out after the issues of step t; a wait
@@ -168,8 +184,8 @@ constexpr int aq_req_issued(int D, int last, int t) {
 // NT = residual tiles of matrix waves 0,1,2; NT2 (= NT or NT-1) those of waves 4,5,6: each SIMD carries NT + NT2.
 // SEG: chained-segment launch (a.nseg * nwg workgroups).  Workgroup s*nwg + k handles SNP segment s of trait-tile group
 // k, starting from the residual that segment s-1 of the same group left in global memory.  Blocks are dispatched in
-// index order, so that workgroup has normally finished long before; correctness does not depend on it: the hand-off
-// is an agent-scope release (producer) / acquire (consumer) around done[k], and the wait is bounded.
+// index order, so that workgroup has normally finished long before; correctness does not depend on it: the residual
+// is stored and loaded at agent scope (aq_r_store / aq_r_load), done[k] is raised behind the drained stores, and the wait is bounded.
 // MASK: Y with missing values (reference coreDualMisLoop, src/coreLoop.cpp:91-138): masked residual, per-trait Gram blocks and
 // per-entry sig2_beta_vb, the NA forms of the column sums (six rows).  One trait tile per workgroup only.
 // WIDE: the wide sample split (9 <= C <= AQ_LA_CMAX parts, n > 10240): the partial S' are combined by split_exchange_wide
@@ -207,8 +223,14 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
           __builtin_amdgcn_s_sleep(32);
           if (++tries > 4000000) { *a.errflag = 1; break; }   // bounded: never hang the GPU
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // No acquire fence.  What this segment reads that an earlier segment of the same launch wrote is the residual R of its
+        // own trait group and nothing else, and every load of R below (aq_r_load in `run`) is an agent-scope load, which is
+        // served past this CU's vector L1: no stale line of it can be met, so nothing has to be invalidated.  Everything else
+        // is either read-only in the launch (X operand panels, G, Gx, GK, mis, theta, zeta and the per-trait vectors, the probit
+        // tables), written and read by this very workgroup (gam, mu of its own SNP blocks: each block belongs to one segment),
+        // or written per segment and read only by later kernels (sums: one slot per segment; gam, mu, rowGB; rnpart is not used
+        // when chained).  done[] is read by the poll above, agent scope.
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the poll's last load has returned before the barrier releases the R loads
       }
       __syncthreads();
     }
@@ -365,7 +387,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
       aq_static_for<NTC>([&](auto tc) __attribute__((always_inline)) {
         constexpr int t = decltype(tc)::value;
 #pragma unroll
-        for (int r = 0; r < 4; r++) Rr[tt][t][r] = Rg[(16 * t + 4 * r) * 16];
+        for (int r = 0; r < 4; r++) Rr[tt][t][r] = aq_r_load<SEG>(&Rg[(16 * t + 4 * r) * 16]);
         if constexpr (MASK) {
           const double *Mg = a.mis + (size_t)tile0 * a.n_pad * 16 + (size_t)(16 * my_t0 + g) * 16 + col;
 #pragma unroll
@@ -445,6 +467,11 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
       AQ_LD2(p0, p1, voff, XUb + seg_b0 * BLK);
       AQ_LD2(c0, c1, voff, XAb + seg_b0 * BLK);
     }
+    // (chained: the planner never makes more segments than SNP blocks -- aq_plan_chain caps the count at nb -- so every segment
+    // holds a block.  Said here because the agent-scope loads of R above are ordered accesses that the compiler keeps in place:
+    // with an edge around the loop it split the live ranges of everything loaded before it on that edge -- the residual tiles
+    // and the operand requests in flight -- into scratch, 132 ... 840 B per instance, which the ISA proof refuses.)
+    if constexpr (SEG) __builtin_assume(nblk >= 1);
     for (int i = 0; i <= nblk + 1; i++) {
       const bool do_u = i >= 2, do_s = i < nblk_s;
       const double mflag = do_u ? -1.0 : 0.0;
@@ -637,7 +664,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
 #pragma unroll
         for (int r = 0; r < 4; r++) {
           const double v = Rr[tt][t][r];
-          Rg[(16 * t + 4 * r) * 16] = v;
+          aq_r_store<SEG>(&Rg[(16 * t + 4 * r) * 16], v);
           rn += v * v;
         }
       });
@@ -1498,13 +1525,14 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
     }
   }
   if (SEG) {
-    // publish this group's residual: every storing wave drains its stores, then one agent-scope release + flag
+    // Hand this group's residual to the next segment.  Every word of R was stored at agent scope (aq_r_store: written through,
+    // no dirty line of it stays in this XCD's L2), every storing wave drains its stores, and behind the barrier one lane raises
+    // the flag: no release fence, whose write-back would walk the whole L2 of the XCD for the sake of these 258 KB.
+    // Ordering relied on: a store that s_waitcnt vmcnt(0) has counted off is complete at the scope it was issued with -- the
+    // same wait is all that orders the flag behind the write-back in the compiler's own agent-scope release (buffer_wbl2 sc1;
+    // s_waitcnt vmcnt(0); store: LLVM AMDGPU usage guide, memory model gfx942, "store atomic release / fence release, agent").
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(&a.done[wg], seg + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (tid == 0) __hip_atomic_store(&a.done[wg], seg + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
