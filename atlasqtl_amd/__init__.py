@@ -13,7 +13,9 @@ from .checks import AtlasqtlError  # noqa: F401
 from .prepare import genotype_grm, genotype_pcs, rank_normalize  # noqa: F401
 from .plink import PlinkBed  # noqa: F401
 from .marginal import marginal_screen  # noqa: F401
-from .cis import cis_finemap, cis_independent, cis_screen, cis_windows, credible_sets_, independent_signals_  # noqa: F401
+from .cis import cis_screen, cis_windows  # noqa: F401
+from .cis_condition import cis_independent, independent_signals_  # noqa: F401
+from .cis_susie import cis_finemap, credible_sets_  # noqa: F401
 from .prediction import predict  # noqa: F401
 
 __all__ = ["atlasqtl", "set_hyper", "set_init", "coreDualLoop", "coreDualMisLoop", "atlasqtl_global_local_core_", "atlasqtl_global_core_",

@@ -1,7 +1,8 @@
 """The argument checks of the reference, R/prepare_atlasqtl.R:90-124 (``check_verbose_``, ``check_annealing_``) and
 R/utils.R:10-100 (``check_*_``), with the reference's wording so that tests read like its own; ``AtlasqtlError``, raised
-wherever the reference calls ``stop()``; and the two predicates the option parsers of the package share, ``_is_whole`` and
-``_is_real``.  This module imports nothing from the package.
+wherever the reference calls ``stop()``; the two predicates the option parsers of the package share, ``_is_whole`` and
+``_is_real``; and the two checks the cis entries share, ``name_or_index_`` (a trait or a variant by its name or its index) and
+``refuse_`` (arguments that do not go together, a path that needs complete Y).  This module imports nothing from the package.
 """
 from __future__ import annotations
 
@@ -108,3 +109,37 @@ def _is_real(x, lo, hi, lo_open=False, hi_open=False):
         return False
     x = float(x)
     return (lo < x if lo_open else lo <= x) and (x < hi if hi_open else x <= hi)
+
+
+def name_or_index_(names, unknown, unusable, outside):
+    """lookup(v) -> the index that v names among `names`: a name in it (the first index of a repeated name) or a whole number
+    in [0, len(names)), no bool.  The three refusals are the caller's texts, formatted with v (as given), i (int(v)) and n
+    (len(names)): `unknown` for a name that is not there, `unusable` for what is neither a name nor a whole number, `outside`
+    for an index out of range.  The names are indexed when the first name is looked up."""
+    first = {}
+
+    def lookup(v):
+        if isinstance(v, (str, np.str_)):
+            if not first:
+                first.update({str(nm): i for i, nm in reversed(list(enumerate(names)))})
+            if str(v) not in first:
+                raise AtlasqtlError(unknown.format(v=v))
+            return first[str(v)]
+        if not _is_whole(v):
+            raise AtlasqtlError(unusable.format(v=v, n=len(names)))
+        if not 0 <= int(v) < len(names):
+            raise AtlasqtlError(outside.format(v=v, i=int(v), n=len(names)))
+        return int(v)
+    return lookup
+
+
+def refuse_(who, together=(), complete_y=None):
+    """What an entry refuses of its arguments' combination, as AtlasqtlError under its name `who`.  together: (value, message)
+    pairs, arguments that do not go with the one asked for: the message of the first whose value is not None.  complete_y:
+    (Y, message), for a path that takes complete Y only: the message where Y has a missing value; a Y of None is not at
+    hand (a file yet to be read) and passes."""
+    for value, message in together:
+        if value is not None:
+            raise AtlasqtlError(f"{who}: {message}")
+    if complete_y is not None and complete_y[0] is not None and np.isnan(np.asarray(complete_y[0], dtype=np.float64)).any():
+        raise AtlasqtlError(f"{who}: {complete_y[1]}")

@@ -30,23 +30,23 @@ INITIAL_CAP = 1 << 16         # rows of the first call's table; a second call wi
 SCREEN_KEYS = ("p_value", "fdr", "max_pairs")
 
 
-def screen_options(p_value=None, fdr=None, max_pairs=None, dense=False, p=None, q=None):
+def screen_options(p_value=None, fdr=None, max_pairs=None, dense=False, p=None, q=None, who="marginal_screen"):
     """The threshold arguments of marginal_screen() checked on the host.  At most one of p_value and fdr, each in (0, 1];
     neither means Bonferroni, p_value = 0.05 / (p q), resolved once p and q are known.  max_pairs: None or a whole number
     >= 1.  dense=True is refused above 2^27 entries.  Returns dict(mode "p_value" | "fdr" | "bonferroni", level (None until p
-    and q are known, for Bonferroni), max_pairs, dense)."""
+    and q are known, for Bonferroni), max_pairs, dense).  who: the entry whose arguments they are, which the messages name."""
     if p_value is not None and fdr is not None:
-        raise AtlasqtlError("marginal_screen: at most one of p_value and fdr may be given.")
+        raise AtlasqtlError(f"{who}: at most one of p_value and fdr may be given.")
     for name, v in (("p_value", p_value), ("fdr", fdr)):
         if v is not None and not _is_real(v, 0.0, 1.0, lo_open=True):
-            raise AtlasqtlError(f"marginal_screen: {name} must be a number in (0, 1], not {v!r}.")
+            raise AtlasqtlError(f"{who}: {name} must be a number in (0, 1], not {v!r}.")
     if max_pairs is not None and (not _is_whole(max_pairs) or int(max_pairs) < 1):
-        raise AtlasqtlError(f"marginal_screen: max_pairs must be None or a whole number >= 1, not {max_pairs!r}.")
+        raise AtlasqtlError(f"{who}: max_pairs must be None or a whole number >= 1, not {max_pairs!r}.")
     if not isinstance(dense, (bool, np.bool_)):
-        raise AtlasqtlError(f"marginal_screen: dense must be True or False, not {dense!r}.")
+        raise AtlasqtlError(f"{who}: dense must be True or False, not {dense!r}.")
     known = p is not None and q is not None
     if dense and known and int(p) * int(q) > DENSE_MAX:
-        raise AtlasqtlError(f"marginal_screen: dense=True would return {int(p) * int(q)} correlations, at most {DENSE_MAX} "
+        raise AtlasqtlError(f"{who}: dense=True would return {int(p) * int(q)} correlations, at most {DENSE_MAX} "
                             "(2^27) are supported; read the selected pairs off `assoc` instead.")
     if p_value is not None:
         mode, level = "p_value", float(p_value)
@@ -219,6 +219,21 @@ def association_table_(out, df, n_tests, mode, level, max_pairs, names_x, names_
     return assoc, best_p, snp, pv
 
 
+def initial_cap_(total):
+    """The rows of a scan's first table, when it could return `total` at the most.  INITIAL_CAP is read when called."""
+    return int(min(total, INITIAL_CAP))
+
+
+def complete_table_(scan, cap, count_key):
+    """The two-call protocol of every entry that returns a table of selected rows: scan(cap) with the first table's size, and,
+    when it counted more rows than that (out[count_key], the full count whatever `cap` is), once more with a table that
+    holds them all -- the complete set, whatever order the first call filled its rows in.  Returns the last call's dict."""
+    out = scan(cap)
+    if out[count_key] > cap:
+        out = scan(out[count_key])
+    return out
+
+
 def screen_handle(prep, names_x, names_y, p_value=None, fdr=None, max_pairs=None, dense=False, permutations=None):
     """The screen on a PreparedData as it stands: marginal_screen() without the preparation.  Returns the result dict without
     the rmvd_* fields."""
@@ -229,10 +244,7 @@ def screen_handle(prep, names_x, names_y, p_value=None, fdr=None, max_pairs=None
     n_obs = np.sum(~np.isnan(prep.Y), axis=0).astype(np.int64)
     df = n_obs - 2 - int(prep.n_cov)
     cut = r2_cutoff(o["level"], df)
-    cap = int(min(p * q, INITIAL_CAP))
-    out = prep.marginal(cut, cap, dense=o["dense"])
-    if out["n_pairs"] > cap:                                  # the complete set, whatever order the first call filled its rows in
-        out = prep.marginal(cut, out["n_pairs"], dense=o["dense"])
+    out = complete_table_(lambda cap: prep.marginal(cut, cap, dense=o["dense"]), initial_cap_(p * q), "n_pairs")
     n_tests = p * q - int(out["n_undefined"])
     assoc, best_p, snp, pv = association_table_(out, df, n_tests, o["mode"], o["level"], o["max_pairs"], names_x, names_y, p)
     n_pairs, best_snp, best_r = assoc["n_pairs"], out["best_snp"], out["best_r"]
@@ -262,9 +274,10 @@ def screen_handle(prep, names_x, names_y, p_value=None, fdr=None, max_pairs=None
 
 
 def on_prepared_(prepare, body, Y, X, device, covariates, ld_prune, transform_y):
-    """What marginal_screen(), cis_screen() and cis_independent() do around their scan: prepare (the caller's prepare_data_,
-    passed in so that the name in the caller's module is what runs: tests replace cis.prepare_data_), run body(prep, dat) on
-    the handle, close it whatever happens, attach the preparation's rmvd_* fields and n_covariates."""
+    """What marginal_screen() and, through cis.on_cis_windows_, cis_screen(), cis_independent() and cis_finemap() do around
+    their work on the handle: prepare (the caller's prepare_data_, passed in so that the name in the caller's module is what
+    runs: tests replace cis.prepare_data_, which all three cis entries go through), run body(prep, dat) on the handle, close it
+    whatever happens, attach the preparation's rmvd_* fields and n_covariates."""
     dat = prepare(Y, X, 0.1, 1, None, 0, None, None, device=device, covariates=covariates, ld_prune=ld_prune, transform_y=transform_y)
     prep = dat["X"]
     try:

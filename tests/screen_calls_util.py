@@ -173,6 +173,7 @@ def _prep(stub, Y):
 def cases():
     """name -> a function of no arguments that returns (the stub it ran on, what came back)."""
     from atlasqtl_amd import cis as CIS
+    from atlasqtl_amd import cis_condition as CC
     from atlasqtl_amd import marginal as M
     from atlasqtl_amd import prepare as PR
     Y, names_x, names_y, e, perms = problem()
@@ -218,18 +219,18 @@ def cases():
 
     def small_cap(call):
         def run(prep):
-            old = M.INITIAL_CAP, CIS.INITIAL_CAP
-            M.INITIAL_CAP = CIS.INITIAL_CAP = 3
+            old = M.INITIAL_CAP
+            M.INITIAL_CAP = 3
             try:
                 return call(prep)
             finally:
-                M.INITIAL_CAP, CIS.INITIAL_CAP = old
+                M.INITIAL_CAP = old
         return run
     method("screen_handle/second_call", small_cap(lambda prep: M.screen_handle(prep, names_x, names_y, p_value=0.5)))
     method("cis_handle/second_call", small_cap(lambda prep: CIS.cis_handle(prep, names_x, names_y, LO, HI, p_value=0.5)))
     method("cis_handle/condition_on/second_call",
            small_cap(lambda prep: CIS.cis_handle(prep, names_x, names_y, LO, HI, p_value=0.5, condition_on=[[3], [], [9]])), k_eff_cap=0)
-    method("cis_independent_handle", lambda prep: CIS.cis_independent_handle(prep, names_x, names_y, LO, HI, fdr=1.0, permutations=perms,
+    method("cis_independent_handle", lambda prep: CC.cis_independent_handle(prep, names_x, names_y, LO, HI, fdr=1.0, permutations=perms,
                                                                              max_signals=2))
 
     # ---- group 3: the three return-code sites ----

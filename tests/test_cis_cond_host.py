@@ -11,6 +11,8 @@ import pytest
 
 from atlasqtl_amd import _lib
 from atlasqtl_amd import cis as CIS
+from atlasqtl_amd import cis_condition as CC
+from atlasqtl_amd import cis_lists as CL
 from atlasqtl_amd.prepare import AtlasqtlError
 from tests import ciscond_util as CU
 
@@ -42,7 +44,7 @@ def test_header_binding_and_library_agree(hiplib):
     assert fields == list(_lib.AqCiscondPlan._fields_)
     assert C.sizeof(_lib.AqCiscondPlan) == C.sizeof(_lib.AqCisPlan) + 4 * 4 + 2 * 8
     for name in ("cis_independent", "independent_signals_"):
-        assert name in A.__all__ and getattr(A, name) is getattr(CIS, name)
+        assert name in A.__all__ and getattr(A, name) is getattr(CC, name)
 
 
 # ---- the planner ----
@@ -129,7 +131,7 @@ def test_plan_refusals(hiplib):
 # ---- condition_on ----
 def test_condition_on_parsing():
     nx, ny = [f"rs{j}" for j in range(10)], ["geneA", "geneB", "geneC"]
-    f = CIS.condition_lists
+    f = CL.condition_lists
     assert f({"geneB": ["rs3", 7], 2: "rs0"}, nx, ny) == [[], [3, 7], [0]]
     assert f({0: 4}, nx, ny) == [[4], [], []]
     assert f([[1, 2, 3, 4], [], ["rs9"]], nx, ny) == [[1, 2, 3, 4], [], [9]]
@@ -157,9 +159,9 @@ def test_condition_on_refusals_come_before_the_device():
         CIS.cis_screen(Yn, X, condition_on=[[0], []], **kw)
     for bad in (0, 6, 2.5, None):
         with pytest.raises(AtlasqtlError, match="max_signals"):
-            CIS.cis_independent(Y, X, max_signals=bad, permutations=10, **kw)
+            CC.cis_independent(Y, X, max_signals=bad, permutations=10, **kw)
     with pytest.raises(AtlasqtlError, match="permutations are required"):
-        CIS.cis_independent(Y, X, permutations=None, **kw)
+        CC.cis_independent(Y, X, permutations=None, **kw)
 
 
 # ---- the reference itself ----
@@ -221,7 +223,7 @@ def test_independent_signals_loop():
     thr = np.full(q, 1e-5)
     thr[[2, 4]] = np.nan
     log = []
-    out = CIS.independent_signals_(CU.numpy_scan(Xs, Yc, lo, hi, 0, log), bs, bp, thr, 5)
+    out = CC.independent_signals_(CU.numpy_scan(Xs, Yc, lo, hi, 0, log), bs, bp, thr, 5)
     assert CU.decisions_are_clear(log, np.where(np.isnan(thr), 1.0, thr))
     assert sorted(out["forward"][0]) == [5, 20] and [s["snp"] for s in out["signals"][0]] == out["forward"][0]
     assert out["forward"][1] == [10] and out["n_signals"][1] == 1                      # the proxies add nothing
@@ -241,14 +243,14 @@ def test_independent_signals_loop():
         assert bool(active[0]) == (i < 2) and not active[1] and not active[5]
     # the cap: with max_signals = 2 gene 3 stops at two signals, and no scan conditions on more than one variant
     log2 = []
-    capped = CIS.independent_signals_(CU.numpy_scan(Xs, Yc, lo, hi, 0, log2), bs, bp, thr, 2)
+    capped = CC.independent_signals_(CU.numpy_scan(Xs, Yc, lo, hi, 0, log2), bs, bp, thr, 2)
     assert capped["n_signals"][3] == 2 and capped["forward"][3] == out["forward"][3][:2]
     assert max(len(c) for cond, _, _, _ in log2 for c in cond) == 1
-    one = CIS.independent_signals_(lambda cond, active: pytest.fail("no scan with max_signals = 1"), bs, bp, thr, 1)
+    one = CC.independent_signals_(lambda cond, active: pytest.fail("no scan with max_signals = 1"), bs, bp, thr, 1)
     assert list(one["n_signals"]) == [1, 1, 0, 1, 0, 1]
     for bad in (0, 6, 1.5):
         with pytest.raises(AtlasqtlError, match="max_signals"):
-            CIS.independent_signals_(None, bs, bp, thr, bad)
+            CC.independent_signals_(None, bs, bp, thr, bad)
 
 
 def test_backward_pass_drops_and_replaces():
@@ -267,7 +269,7 @@ def test_backward_pass_drops_and_replaces():
             bs[t], pv[t] = script[(tuple(cond[t]), int(t))]
         return dict(best_snp=bs, best_pvalue=pv)
 
-    out = CIS.independent_signals_(scan, np.array([7, 4]), np.array([1e-12, 1e-7]), thr, 5)
+    out = CC.independent_signals_(scan, np.array([7, 4]), np.array([1e-12, 1e-7]), thr, 5)
     assert out["forward"] == [[7, 3, 9], [4]]
     assert [(s["rank"], s["snp"], s["forward_snp"]) for s in out["signals"][0]] == [(1, 8, 7), (3, 9, 9)]
     assert [(s["rank"], s["snp"], s["forward_snp"], s["pvalue"]) for s in out["signals"][1]] == [(1, 4, 4, 1e-7)]

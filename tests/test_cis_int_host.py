@@ -11,6 +11,7 @@ import pytest
 
 from atlasqtl_amd import _lib
 from atlasqtl_amd import cis as CIS
+from atlasqtl_amd import cis_interaction as INT
 from atlasqtl_amd.prepare import AtlasqtlError
 from tests import cisint_util as CI
 
@@ -112,7 +113,7 @@ def test_interaction_basis_spans_one_covariates_and_e():
     n = 40
     Z, e = rng.standard_normal((n, 3)), rng.standard_normal(n) + 2.0
     for cov, d in ((None, 0), (Z, 3)):
-        B, m = CIS.interaction_basis(e, cov, n, d)
+        B, m = INT.interaction_basis(e, cov, n, d)
         Q, m2 = CI.basis(e, cov)
         assert B.shape == (d + 2, n) and B.flags["C_CONTIGUOUS"] and B.dtype == np.float64
         np.testing.assert_allclose(m, e - e.mean(), rtol=0, atol=1e-15)
@@ -128,30 +129,30 @@ def test_interaction_basis_refusals():
     n = 30
     Z, e = rng.standard_normal((n, 2)), rng.standard_normal(n)
     with pytest.raises(AtlasqtlError, match=r"one value per sample \(30\)"):
-        CIS.interaction_basis(e[:-1], None, n, 0)
+        INT.interaction_basis(e[:-1], None, n, 0)
     with pytest.raises(AtlasqtlError, match="one value per sample"):
-        CIS.interaction_basis(np.stack([e, e], axis=1), None, n, 0)
+        INT.interaction_basis(np.stack([e, e], axis=1), None, n, 0)
     bad = e.copy()
     bad[3] = np.nan
     with pytest.raises(AtlasqtlError, match="finite without missing value"):
-        CIS.interaction_basis(bad, None, n, 0)
+        INT.interaction_basis(bad, None, n, 0)
     bad[3] = np.inf
     with pytest.raises(AtlasqtlError, match="finite without missing value"):
-        CIS.interaction_basis(bad, None, n, 0)
+        INT.interaction_basis(bad, None, n, 0)
     with pytest.raises(AtlasqtlError, match="interaction is constant"):
-        CIS.interaction_basis(np.full(n, 2.5), None, n, 0)
+        INT.interaction_basis(np.full(n, 2.5), None, n, 0)
     with pytest.raises(AtlasqtlError, match="span of the intercept and the covariates"):
-        CIS.interaction_basis(3.0 + 2.0 * Z[:, 0] - Z[:, 1], Z, n, 2)
+        INT.interaction_basis(3.0 + 2.0 * Z[:, 0] - Z[:, 1], Z, n, 2)
     with pytest.raises(AtlasqtlError, match="have rank 0, but the data were prepared with 2"):
-        CIS.interaction_basis(e, None, n, 2)
+        INT.interaction_basis(e, None, n, 2)
     with pytest.raises(AtlasqtlError, match="have rank 2, but the data were prepared with 0"):
-        CIS.interaction_basis(e, Z, n, 0)
+        INT.interaction_basis(e, Z, n, 0)
     dup = np.column_stack([Z, Z[:, 0] + Z[:, 1]])              # a collinear column is dropped: rank 2, not 3
     with pytest.raises(AtlasqtlError, match="have rank 2, but the data were prepared with 3"):
-        CIS.interaction_basis(e, dup, n, 3)
-    assert CIS.interaction_basis(e, dup, n, 2)[0].shape == (4, n)
+        INT.interaction_basis(e, dup, n, 3)
+    assert INT.interaction_basis(e, dup, n, 2)[0].shape == (4, n)
     with pytest.raises(AtlasqtlError, match="one row per sample"):
-        CIS.interaction_basis(e, Z[:-1], n, 2)
+        INT.interaction_basis(e, Z[:-1], n, 2)
 
 
 def test_cis_screen_refuses_before_any_device_call(monkeypatch):

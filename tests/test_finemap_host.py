@@ -1,5 +1,5 @@
 """Cis fine-mapping without a GPU: the two restatements of tests/finemap_util.py against each other, the ELBO of the reference,
-the credible sets (atlasqtl_amd.cis.credible_sets_) on hand-made rows and against the full vector, the planner
+the credible sets (atlasqtl_amd.cis_susie.credible_sets_) on hand-made rows and against the full vector, the planner
 (aq_finemap_plan_query) and the argument errors of the entries."""
 import ctypes as C
 
@@ -8,7 +8,7 @@ import pytest
 
 import atlasqtl_amd as A
 from atlasqtl_amd import _lib
-from atlasqtl_amd import cis as CIS
+from atlasqtl_amd import cis_susie as CIS
 from tests import finemap_util as FU
 
 LD = FU.LD

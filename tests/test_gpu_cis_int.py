@@ -36,7 +36,7 @@ def _id(run):
 def _case(shape, d, kind):
     """Once per (shape, d, e), shared and left unchanged: the raw inputs, the handle's own matrices, and the basis and the
     multiplier that the library is given."""
-    from atlasqtl_amd import cis as CIS
+    from atlasqtl_amd import cis_interaction as CIS
     from atlasqtl_amd import prepare as P
     n, p, q = shape
     X, Y, Z, e = CI.case(n, p, q, d, kind)

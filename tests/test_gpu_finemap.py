@@ -252,7 +252,7 @@ def test_one_effect_against_the_cis_scan(shape, pattern):
 def test_rows_and_cap(shape, pattern, L):
     """The rows are the dense alpha thresholded at thr_t over the effects with V > 0, as sets; cap = 0 only counts; beyond cap
     n_rows is still the full count."""
-    from atlasqtl_amd import cis as CIS
+    from atlasqtl_amd import cis_susie as CIS
     n, p, q = shape
     lo, hi = FU.windows(pattern, p, q)
     cov, amin = 0.9, 1e-3

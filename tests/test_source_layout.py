@@ -86,3 +86,57 @@ def test_the_rank_collectives_have_one_owner():
                 importing.add(fn)
     assert naming == {"ranks.py"}
     assert importing == {"ranks.py", "_lib.py"}
+
+
+def _package():
+    pkg = os.path.join(ROOT, "atlasqtl_amd")
+    out = {}
+    for fn in sorted(os.listdir(pkg)):
+        if fn.endswith(".py"):
+            with open(os.path.join(pkg, fn)) as f:
+                out[fn] = f.read()
+    return out
+
+
+def _code_only(src):
+    """Python source without its comments and docstrings (the strings that start a statement), token by token."""
+    import io
+    import tokenize
+    out, starts = [], True
+    for tok in tokenize.generate_tokens(io.StringIO(src).readline):
+        if tok.type in (tokenize.COMMENT, tokenize.NL):
+            continue
+        if tok.type in (tokenize.NEWLINE, tokenize.INDENT, tokenize.DEDENT):
+            starts = True
+            continue
+        if not (starts and tok.type == tokenize.STRING):
+            out.append(tok.string)
+        starts = False
+    return " ".join(out)
+
+
+def test_the_screen_entries_shared_steps_have_one_owner():
+    """Among atlasqtl_amd/*.py: the size of a scan's first table is marginal.py's alone (initial_cap_ and complete_table_ are
+    how the others get at the two-call protocol); on_prepared_ is called by marginal.py and by cis.py, whose on_cis_windows_
+    all three cis entries go through; and only prepared.py and _lib.py name an entry of the aq_prep_cis family in their code."""
+    src = _package()
+    assert {fn for fn, s in src.items() if "INITIAL_CAP" in s} == {"marginal.py"}
+    assert {fn for fn, s in src.items() if "on_prepared_(" in _code_only(s).replace(" ", "")} == {"marginal.py", "cis.py"}
+    assert {fn for fn, s in src.items() if "aq_prep_cis" in _code_only(s)} == {"prepared.py", "_lib.py"}
+    for fn in ("cis_condition.py", "cis_susie.py"):
+        assert "on_cis_windows_(" in _code_only(src[fn]).replace(" ", "") and "prepare_data_" not in src[fn], fn
+
+
+def test_the_cis_modules_import_each_other_without_a_cycle():
+    """The `from .x import` lines of the cis* modules, parsed and not imported: a graph without a cycle, in which cis.py is
+    below the two entries built on its scan and above the two argument modules."""
+    src = {fn[:-3]: s for fn, s in _package().items() if fn.startswith("cis")}
+    assert set(src) >= {"cis", "cis_lists", "cis_interaction", "cis_condition", "cis_susie"}
+    graph = {m: set(re.findall(r"^\s*from\s+\.(cis\w*)\s+import\b", s, flags=re.M)) for m, s in src.items()}
+    assert all(not re.search(r"^\s*(?:from\s+\.\s+import|import\s+atlasqtl_amd|from\s+atlasqtl_amd)", s, flags=re.M) for s in src.values())
+    assert graph["cis"] == {"cis_lists", "cis_interaction"} and "cis" in graph["cis_condition"] and "cis" in graph["cis_susie"]
+    done = set()
+    while len(done) < len(graph):                                 # peel off the modules whose imports are all peeled off
+        free = {m for m in graph if m not in done and graph[m] <= done}
+        assert free, f"an import cycle among {sorted(set(graph) - done)}"
+        done |= free

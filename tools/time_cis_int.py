@@ -31,7 +31,8 @@ def main():
     ap.add_argument("--covariates", type=int, default=0)
     args = ap.parse_args()
     from atlasqtl_amd import _lib
-    from atlasqtl_amd.cis import cis_windows, interaction_basis
+    from atlasqtl_amd.cis import cis_windows
+    from atlasqtl_amd.cis_interaction import interaction_basis
     from atlasqtl_amd.prepare import prepare_on_device
     L = _lib.lib()
     n, p, q = (int(v) for v in args.shape.split("x"))
