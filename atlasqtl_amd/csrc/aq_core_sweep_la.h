@@ -44,142 +44,10 @@
 #include <hip/hip_runtime.h>
 #include "aq_core_sweep.h"
 #include <type_traits>
-
-typedef double aq_v2 __attribute__((ext_vector_type(2)));
-
-// Sum over the 16 lanes of a DPP row (lanes 16 k .. 16 k + 15), result in every lane: quad butterflies, then row rotations by
-// 4 and 8 (every quad holds its own sum by then).  Eight v_mov_b32 DPP + four v_add_f64 with register latency, where
-// __shfl_xor costs eight ds_bpermute_b32 round trips through the LDS pipeline.
-__device__ __forceinline__ double aq_row16_sum(double v) {
-  auto step = [&](auto ctrl) __attribute__((always_inline)) {
-    constexpr int C = decltype(ctrl)::value;
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), C, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), C, 0xf, 0xf, false);
-    v += __hiloint2double(hi, lo);
-  };
-  step(std::integral_constant<int, 0xB1>{});    // quad_perm [1,0,3,2]
-  step(std::integral_constant<int, 0x4E>{});    // quad_perm [2,3,0,1]
-  step(std::integral_constant<int, 0x124>{});   // row_ror:4
-  step(std::integral_constant<int, 0x128>{});   // row_ror:8
-  return v;
-}
-
-// cache policy of the Gram-block stream (49 KB per phase and workgroup, read once per sweep): 2 = nt, non-temporal, so that it
-// does not push the X operand panels -- which every workgroup of the XCD re-reads -- out of the L2
-#ifndef AQ_GLDS_AUX
-#define AQ_GLDS_AUX 2
-#endif
-// One LDS-DMA transfer (global_load_lds_dwordx4): 64 lanes x 16 B from per-lane global addresses to lds_base + 16 lane, with
-// no VGPR destination; completion is counted in vmcnt.  lds_base must be wave-uniform.
-__device__ __forceinline__ void aq_glds16(const void *gsrc_lane, void *lds_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc_lane,
-                                   (__attribute__((address_space(3))) void *)lds_base, 16, 0, AQ_GLDS_AUX);
-}
-
-// compile-time loop: f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>).  The residual tiles live in
-// registers only while every index into them is a constant expression.
-template <int... Is, class F>
-__device__ __forceinline__ void aq_static_for_impl(std::integer_sequence<int, Is...>, F &&f) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void aq_static_for(F &&f) {
-  aq_static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
-
-// two 16-byte loads (one operand tile = 2 x 1 KB per wave): lane address = sbase + voff (+ 1024).  The base is wave-uniform
-// but computed inside the role split, where the compiler no longer proves it: v_readfirstlane puts it into the SGPR pair the
-// saddr form needs (folded away wherever uniformity is known).
-#define AQ_LD2(d0, d1, voff, sbase)                                                                            \
-  do {                                                                                                          \
-    const unsigned long long b_ = (unsigned long long)(sbase);                                                  \
-    const unsigned lo_ = __builtin_amdgcn_readfirstlane((unsigned)b_);                                          \
-    const unsigned hi_ = __builtin_amdgcn_readfirstlane((unsigned)(b_ >> 32));                                  \
-    const unsigned long long u_ = ((unsigned long long)hi_ << 32) | lo_;                                        \
-    asm volatile("global_load_dwordx4 %0, %2, %3\n\tglobal_load_dwordx4 %1, %2, %3 offset:1024"                \
-                 : "=&v"(d0), "=&v"(d1)                                                                         \
-                 : "v"(voff), "s"(u_));                                                                         \
-  } while (0)
-// the same with a compile-time byte offset IMM (and IMM + 1024) in the instruction: one SGPR base serves four tiles
-// (IMM in {-4096, -2048, 0, 2048}; the 13-bit signed offset field holds -4096 .. 4095)
-#define AQ_LD2I(d0, d1, voff, sbase, IMM)                                                                      \
-  do {                                                                                                          \
-    const unsigned long long b_ = (unsigned long long)(sbase);                                                  \
-    const unsigned lo_ = __builtin_amdgcn_readfirstlane((unsigned)b_);                                          \
-    const unsigned hi_ = __builtin_amdgcn_readfirstlane((unsigned)(b_ >> 32));                                  \
-    const unsigned long long u_ = ((unsigned long long)hi_ << 32) | lo_;                                        \
-    asm volatile("global_load_dwordx4 %0, %2, %3 offset:%4\n\tglobal_load_dwordx4 %1, %2, %3 offset:%5"        \
-                 : "=&v"(d0), "=&v"(d1)                                                                         \
-                 : "v"(voff), "s"(u_), "i"(IMM), "i"((IMM) + 1024));                                            \
-  } while (0)
-// one 4-byte load whose value nobody reads (L2 warm-up): lane address = sbase + voff, sbase wave-uniform as above
-#define AQ_TOUCH(d, voff, sbase)                                                                               \
-  do {                                                                                                          \
-    const unsigned long long b_ = (unsigned long long)(sbase);                                                  \
-    const unsigned lo_ = __builtin_amdgcn_readfirstlane((unsigned)b_);                                          \
-    const unsigned hi_ = __builtin_amdgcn_readfirstlane((unsigned)(b_ >> 32));                                  \
-    const unsigned long long u_ = ((unsigned long long)hi_ << 32) | lo_;                                        \
-    asm volatile("global_load_dword %0, %1, %2" : "=v"(d) : "v"(voff), "s"(u_));                                \
-  } while (0)
-// wait until at most N of this wave's vector-memory operations are outstanding; the operands tie the wait to the
-// registers it covers so that no use can be scheduled above it
-#define AQ_WAIT2(N, d0, d1) asm volatile("s_waitcnt vmcnt(" #N ")" : "+v"(d0), "+v"(d1))
-template <int N>
-__device__ __forceinline__ void aq_wait2n(aq_v2 &d0, aq_v2 &d1) {   // the same with a count computed at compile time
-  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%2)" : "+v"(d0), "+v"(d1) : "n"(N));
-}
-
-// One word of the residual R.  COH (the chained instances): as an agent-scope relaxed atomic -- global_load / global_store with
-// sc1: the load is served past the CU's vector L1, the store is written through to the level every XCD reads -- so that the
-// residual passes from one segment's workgroup to the next without a fence (see the hand-over at the end of the kernel).
-// Otherwise a plain access.
-template <bool COH>
-__device__ __forceinline__ double aq_r_load(const double *p) {
-  if constexpr (COH) return __hip_atomic_load(const_cast<double *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else return *p;
-}
-template <bool COH>
-__device__ __forceinline__ void aq_r_store(double *p, double v) {
-  // (through a global-address-space pointer: where the compiler has lost track of the space it would issue a flat store)
-  if constexpr (COH) __hip_atomic_store((__attribute__((address_space(1))) double *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *p = v;
-}
-
-// Operand prefetch with D buffers per stream (tile k in buffer k % D).  Request order of a phase: the tiles left dangling by the
-// phase before -- [XU0 XA0 XU1 XA1 ...], XU up to tile D-2, XA up to D-3 -- then per step t: XU(t+D-1), XA(t+D-2) while they
-// exist.  aq_req_index = position of a request in that order, aq_req_issued = requests out after the issues of step t; a wait
-// for a tile is vmcnt(2 x (requests issued after it)): two loads per request, completed in order.
-constexpr int aq_req_index(int D, int last, int stream /* 0 XU, 1 XA */, int k) {
-  int n = 0;
-  for (int j = 0; j <= D - 2; j++) {
-    if (stream == 0 && k == j) return n;
-    n++;
-    if (j <= D - 3) {
-      if (stream == 1 && k == j) return n;
-      n++;
-    }
-  }
-  for (int t = 0; t <= last; t++) {
-    if (t + D - 1 <= last) {
-      if (stream == 0 && k == t + D - 1) return n;
-      n++;
-    }
-    if (t + D - 2 <= last) {
-      if (stream == 1 && k == t + D - 2) return n;
-      n++;
-    }
-  }
-  return -1;
-}
-constexpr int aq_req_issued(int D, int last, int t) {
-  int n = (D - 1) + (D - 2);
-  for (int s = 0; s <= t; s++) n += (s + D - 1 <= last) + (s + D - 2 <= last);
-  return n;
-}
-#ifndef AQ_DEEP_TT1
-#define AQ_DEEP_TT1 4   // buffers per operand stream of the one-tile workgroups
-#endif
+// the pieces that live beside the kernel: operand stream and device primitives, hand-off counters, derived constants
+#include "aq_la_stream.h"
+#include "aq_la_flags.h"
+#include "aq_la_traits.h"
 
 // NT = residual tiles of matrix waves 0,1,2; NT2 (= NT or NT-1) those of waves 4,5,6: each SIMD carries NT + NT2.
 // SEG: chained-segment launch (a.nseg * nwg workgroups).  Workgroup s*nwg + k handles SNP segment s of trait-tile group
@@ -192,16 +60,9 @@ constexpr int aq_req_issued(int D, int last, int t) {
 // (reduce-scatter + all-gather) instead of every part reading every other part's words.  One tile per workgroup, unchained.
 template <int NT, int NT2, bool SEG, int TT, bool MASK = false, int NT3_ = -1, bool WIDE = false>
 __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCoreArgs a) {
-  static_assert(!MASK || TT == 1, "the masked form keeps 16 per-trait Gram blocks in LDS: one trait tile per workgroup");
-  static_assert(!WIDE || (TT == 1 && !SEG), "the wide sample split: one trait tile per workgroup, never chained");
-  constexpr int NWM = 6;                        // matrix waves: 0,1,2,4,5,6
-  // residual tiles of the recurrence wave (its matrix work follows its chain): aq_la_nt3 unless the instance names its own count
-  constexpr int NT3 = NT3_ >= 0 ? NT3_ : aq_la_nt3(NT, NT2, TT);
-  constexpr int NPS = NWM + (NT3 > 0 ? 1 : 0);  // partial S' slots
-  constexpr int NTR = 16 * TT;                  // traits per workgroup
-  constexpr int ENT = 256 * TT;                 // entries of one SNP block: [snp][trait]
-  constexpr int NG = 4 / TT;                    // 16*TT-lane groups of the recurrence / helper wave
-  constexpr int RPG = 16 / NG;                  // SNP rows per group
+  using T = AqLaTraits<NT, NT2, SEG, TT, MASK, NT3_, WIDE>;   // the constants derived from the parameters (aq_la_traits.h)
+  constexpr int NWM = T::NWM, NT3 = T::NT3, NPS = T::NPS, NTR = T::NTR, ENT = T::ENT, NG = T::NG, RPG = T::RPG, NTT = T::NTT;
+  constexpr bool CXC = T::CXC;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = tid >> 6;
@@ -254,12 +115,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
   __shared__ double LB[2][ENT];        // slope b of Z
   __shared__ double Laa[2][ENT];       // intercept a of Z (Z = a + gam b, R/update_vb.R:217-234)
   __shared__ double LG[MASK ? 1 : 2][MASK ? 1 : 512];    // X_b'X_b as [16][32], upper 16 columns zero        (complete Y)
-  // Complete Y, where the cross-block correction X_b'X_{b-1} delta_{b-1} comes from: with two trait tiles per workgroup the matrix
-  // SIMDs are the bound and the helper wave forms the product after each chain (Lcx); with ONE tile per workgroup (the trait
-  // shards of a multi-GPU run, small q: the chain is the critical path) it is accumulated INSIDE the chain of block b-1, one
-  // column of X_b'X_{b-1} per step as that step's delta appears -- complete the moment that chain ends (CXC).  The chain of
-  // block b-1 then needs block b's cross Gram: three buffers, block m in LGx[m % 3], staged a block earlier.
-  constexpr bool CXC = (TT == 1) && !MASK;
+  // (three buffers where the chain of block b-1 builds block b's cross-block correction itself: AqLaTraits::CXC)
   __shared__ double LGx[MASK ? 1 : 3][MASK ? 1 : 256];   // X_b'X_{b-1}  [j][i]                              (complete Y)
   // MASK: the traits' own blocks, written by LDS-DMA.  Diagonal block: lower triangle [i (i + 1) / 2 + j][trait], by block
   // parity; cross block [j][i][trait], ONE buffer (released by the recurrence wave through Fl[13] as soon as the correction
@@ -274,69 +130,9 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
   __shared__ double Lpt[AQ_PT_LEN];    // the probit tables (aq_probit_tab.h), [function][coefficient][interval]: 6.2 KB
   __shared__ double Lred[6][64];       // the helper lanes' column sums [row group][trait], added up per trait at the end
   __shared__ double Lrn[NPS * 4][NTR];
-  // Point-to-point progress counters instead of a workgroup barrier per phase: Fl[0..5] = number of SNP blocks whose
-  // partial S' matrix wave m has written, Fl[6] = blocks the recurrence wave has finished, Fl[7] = blocks the helper
-  // wave has staged, Fl[8..10] = phases that matrix wave 0..2 has carried past its stagger tile (its SIMD partner 4..6
-  // starts the phase then), Fl[11] = phases the recurrence wave's own matrix work has finished (init mode: the helper may
-  // then reuse a beta buffer), Fl[12] = (complete Y) blocks whose cross-block correction the helper wave has put into Lcx, Fl[13] = (MASK) chains that have read their cross blocks, Fl[14] = (sample split) blocks whose
-  // S' the helper wave has exchanged with the other parts.  Each wave waits only for what it really reads, so the matrix waves -- the critical path --
-  // never stop at a barrier.  LDS operations of a wave execute in order and the LDS is one pipeline per CU, so
-  // "data stores; s_waitcnt lgkmcnt(0); counter store" on one side and "counter load ... ; data loads" on the other are
-  // ordered; the asm memory clobbers keep the compiler from moving accesses across them.
-  __shared__ __attribute__((aligned(16))) int Fl[16];
-  // (explicit LDS address space: through a generic pointer the volatile accesses become flat loads with a vmcnt(0) drain)
-  typedef __attribute__((address_space(3))) volatile int aq_lds_vint;
-  aq_lds_vint *Flv = (aq_lds_vint *)(__attribute__((address_space(3))) int *)Fl;
-  auto signal = [&](int idx, int val) __attribute__((always_inline)) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane == 0) Flv[idx] = val;
-  };
-#ifdef AQ_DIAG_TIME
-  long long dg_wait = 0, dg_wait_b = 0;   // waits on the matrix / recurrence counters; on the helper's and the stagger counters
-  const long long dg_t0 = __builtin_readcyclecounter();
-#endif
-#if defined(AQ_DIAG_TIME) || defined(AQ_DIAG_TL)   // (AQ_DIAG_TL: the timeline marks alone -- a lighter build for instances whose
-                                                    // registers the wait counters would push over the edge)
-  // timeline of workgroup 0, phases 64 .. 95: slot k of (wave, phase) <- cycle counter (behind the per-wave counters in a.dbg)
-  auto tl_mark = [&](int i, int k) __attribute__((always_inline)) {
-    if (a.dbg && blockIdx.x == 0 && i >= 64 && i < 96 && lane == 0)
-      a.dbg[(size_t)gridDim.x * 24 + ((size_t)w * 32 + (i - 64)) * 8 + k] = __builtin_readcyclecounter();
-  };
-#else
-  auto tl_mark = [&](int, int) __attribute__((always_inline)) {};
-#endif
-  auto wait_ge = [&](int idx, int val) __attribute__((always_inline)) {
-#ifdef AQ_DIAG_TIME
-    const long long t_in = __builtin_readcyclecounter();
-#endif
-    while (Flv[idx] < val) __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
-#ifdef AQ_DIAG_TIME
-    if (idx >= 7) dg_wait_b += __builtin_readcyclecounter() - t_in;
-    else dg_wait += __builtin_readcyclecounter() - t_in;
-#endif
-  };
-  // the recurrence wave's wait at the top of a chain -- all six matrix waves' partial S' and the helper's staging -- as ONE poll of
-  // two 16-byte LDS reads instead of seven round trips in a row (0.3 us per SNP block where the chain is the critical path)
-  typedef int aq_i4 __attribute__((ext_vector_type(4)));
-  auto wait_s_and_staged = [&](int val) __attribute__((always_inline)) {
-    typedef __attribute__((address_space(3))) volatile aq_i4 aq_lds_vi4;
-    aq_lds_vi4 *fp = (aq_lds_vi4 *)(__attribute__((address_space(3))) int *)Fl;
-#ifdef AQ_DIAG_TIME
-    const long long t_in = __builtin_readcyclecounter();
-#endif
-    for (;;) {
-      const aq_i4 f0 = fp[0], f1 = fp[1];   // Fl[0..3], Fl[4..7]; Fl[6] is this wave's own counter
-      const int lo = min(min(min(f0.x, f0.y), min(f0.z, f0.w)), min(min(f1.x, f1.y), f1.w));
-      if (lo >= val) break;
-      __builtin_amdgcn_s_sleep(1);
-    }
-    asm volatile("" ::: "memory");
-#ifdef AQ_DIAG_TIME
-    dg_wait += __builtin_readcyclecounter() - t_in;
-#endif
-  };
-  if (tid < 16) Fl[tid] = 0;
+  __shared__ AqLaFlagWords Fl;         // the hand-off counters: names, protocol and ordering in aq_la_flags.h
+  AqLaFlags fl{(aq_lds_vint *)(__attribute__((address_space(3))) int *)Fl.v, lane, w, a.dbg};
+  if (tid < AQ_FL_COUNT) Fl.v[tid] = 0;
 
   const int ktrait = tile0 * 16 + ht;           // helper / recurrence: this lane's trait
   const bool kvalid = ktrait < a.q;
@@ -360,6 +156,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
     }
   }
 
+  const int nblk_s = a.mode == 1 ? 0 : nblk;       // init mode: no S'
   // One code path for both kinds of matrix wave and both modes.  Phase i = 0 .. nblk + 1 of a segment starting at block b0:
   //     update with block b0 + i - 2 (i >= 2; its delta must be out: recurrence counter >= i - 1)
   //     S' of block b0 + i          (i < nblk, sweep mode only)           then announce i + 1 on this wave's counter.
@@ -368,8 +165,6 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
   // ROLE 0: matrix waves 0-2 (NT tiles each), 1: matrix waves 4-6 (NT2 each), 2: the recurrence wave (NT3 tiles; `hook(i)` runs
   // its chain for block b0 + i - 1 at the top of phase i -- that block's S' is complete when every matrix wave has announced
   // phase i - 1, and its own share of it was stored by this very wave at the end of its previous phase).
-  constexpr int NTT = 3 * (NT + NT2) + NT3;
-  const int nblk_s = a.mode == 1 ? 0 : nblk;       // init mode: no S'
   auto run = [&](auto ntc, auto rolec, auto hook) __attribute__((always_inline)) {
     constexpr int NTC = decltype(ntc)::value;
     constexpr int ROLE = decltype(rolec)::value;
@@ -477,12 +272,12 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
       const double mflag = do_u ? -1.0 : 0.0;
       const int bu = seg_b0 + (i >= 2 ? i - 2 : 0), bs = seg_b0 + (i < nblk ? i : nblk - 1);
       const int nbu = seg_b0 + (i >= 1 ? (i - 1 < nblk ? i - 1 : nblk - 1) : 0), nbs = seg_b0 + (i + 1 < nblk ? i + 1 : nblk - 1);
-      tl_mark(i, 0);                     // phase entered (recurrence wave: before its chain)
+      fl.tl_mark(i, 0);                  // phase entered (recurrence wave: before its chain)
       hook(i);
-      tl_mark(i, 1);                     // (recurrence wave: chain done)
-      if (do_u && (ROLE != 2 || a.mode == 1)) wait_ge(6, i - 1);   // (sweep mode: the recurrence wave wrote that delta itself)
-      if (ROLE == 1 && a.stagger) wait_ge(8 + (mw - 3), i + 1);
-      tl_mark(i, 2);                     // waits passed: tile loop starts
+      fl.tl_mark(i, 1);                  // (recurrence wave: chain done)
+      if (do_u && (ROLE != 2 || a.mode == 1)) fl.wait_ge(AQ_FL_REC_DONE, i - 1);   // (sweep mode: the recurrence wave wrote that delta itself)
+      if (ROLE == 1 && a.stagger) fl.wait_ge(aq_fl_stagger(mw - 3), i + 1);
+      fl.tl_mark(i, 2);                  // waits passed: tile loop starts
       double nd[TT][4];
       {
         // (4 s + g) NTR + 16 tt + col.  The lane id is recomputed here and hidden from the optimiser: kept in a register
@@ -563,7 +358,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
             dangling(nxu, nxa, std::true_type{});               // XA'0, XU'1, ... (XU'0 is out already)
           }
           if constexpr (HI && t + 1 == ST) {
-            if (a.stagger) signal(8 + mw, i + 1);
+            if (a.stagger) fl.signal(aq_fl_stagger(mw), i + 1);
           }
           __builtin_amdgcn_sched_barrier(0);
         });
@@ -572,7 +367,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
         AQ_WAIT2(0, p0, p1);
         AQ_WAIT2(0, c0, c1);
         U(C0{}, p0, p1);
-        if (HI && a.stagger) signal(8 + mw, i + 1);
+        if (HI && a.stagger) fl.signal(aq_fl_stagger(mw), i + 1);
         __builtin_amdgcn_sched_barrier(0);
         AQ_LD2(p0, p1, voff, nxu);
         if constexpr (MASK) remask(C0{});
@@ -622,7 +417,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
             AQ_LD2(c0, c1, voff, nxa);       // (c0,c1) held XA(t) for even t: S(t) is issued
           }
           if constexpr (HI && t + 1 == ST) {
-            if (a.stagger) signal(8 + mw, i + 1);
+            if (a.stagger) fl.signal(aq_fl_stagger(mw), i + 1);
           }
           __builtin_amdgcn_sched_barrier(0);
         });
@@ -635,8 +430,8 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
 #pragma unroll
           for (int r = 0; r < 4; r++) Sp[ps][slot][(4 * r + g) * NTR + 16 * tt + col] = acc[tt][r];
       }
-      signal(ROLE == 2 ? 11 : mw, i + 1);
-      tl_mark(i, 3);                     // S' stored and announced
+      fl.signal(ROLE == 2 ? AQ_FL_REC_TILES : aq_fl_matrix(mw), i + 1);
+      fl.tl_mark(i, 3);                  // S' stored and announced
     }
     if constexpr (DEEP) {   // the dangling prefetch (the empty statements tie the wait to every buffer)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -760,7 +555,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
     const int par = b & 1;
     const unsigned long long tag = 1ull + (unsigned long long)(((b - seg_b0) >> 1) % 3);
     unsigned long long *slots = (unsigned long long *)a.Pbuf + ((size_t)(wg * 2 + par) * (C + 1)) * ENT;
-    tl_mark(b - seg_b0 + 1, 2);   // (diag) exchange: publish
+    fl.tl_mark(b - seg_b0 + 1, 2);   // (diag) exchange: publish
 #pragma unroll
     for (int r = 0; r < RPG; r++)
       __hip_atomic_store(&slots[(size_t)part * ENT + lane + 64 * r], ((unsigned long long)__double_as_longlong(own[r]) & ~3ull) | tag,
@@ -793,7 +588,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
 #pragma unroll
     for (int m = 0; m < AQ_LA_WPC; m++)
       if (act && m < pc && c0 + m < C) acc += __longlong_as_double((long long)v[m]);
-    tl_mark(b - seg_b0 + 1, 3);   // (diag) exchange: every part's partial of the owned entries has arrived
+    fl.tl_mark(b - seg_b0 + 1, 3);   // (diag) exchange: every part's partial of the owned entries has arrived
     double tot = acc;
     for (int kk = 1; kk < nch; kk++) {                   // chunk sums in ascending k (wave-uniform loop: every lane shuffles)
       const double t = __shfl(acc, min(63, i * nch + kk), 64);
@@ -819,7 +614,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
     }
 #pragma unroll
     for (int r = 0; r < RPG; r++) own[r] = __longlong_as_double((long long)w4[r]);
-    tl_mark(b - seg_b0 + 1, 4);   // (diag) exchange: all totals read
+    fl.tl_mark(b - seg_b0 + 1, 4);   // (diag) exchange: all totals read
   };
 
   __syncthreads();   // counters and the helper's LDS initialisation are visible to every role
@@ -842,13 +637,13 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
         if (C > 1 && a.xhelper) {
           // sample split: the helper wave has added this part's partial S' to the other parts' (a block ahead, off this
           // wave's critical path) -- every part reads the same bits and runs the same chain
-          wait_ge(14, need);
-          wait_ge(7, need);
+          fl.wait_ge(AQ_FL_EXCHANGED, need);
+          fl.wait_ge(AQ_FL_STAGED, need);
 #pragma unroll
           for (int r = 0; r < RPG; r++) Sown[r] = Stot[par][(hg + NG * r) * NTR + ht];
         } else {
           // block b needs its six partial S' and its staged scalars
-          wait_s_and_staged(need);
+          fl.wait_s_and_staged(need);
 #pragma unroll
           for (int r = 0; r < RPG; r++) {
             const int j = hg + NG * r;
@@ -858,7 +653,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
             Sown[r] = sv;
           }
         }
-        tl_mark(need, 4);                  // (diag) partial S' complete and summed
+        fl.tl_mark(need, 4);               // (diag) partial S' complete and summed
         // cross-block correction X_b'X_{b-1} delta_{b-1} of this group's rows (a segment starts from a complete residual);
         // MASK: with the trait's own cross block X_b' diag(mis_k) X_{b-1}.  It does not depend on S': with the sample split it
         // is computed while the partial sums travel.
@@ -878,7 +673,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
           } else if constexpr (!MASK) {
             // complete Y: the helper wave formed the 16 x 16 product right after the previous chain (Fl[12]); here it is 8 reads
             if (b > seg_b0) {
-              wait_ge(12, need);
+              fl.wait_ge(AQ_FL_CX_READY, need);
 #pragma unroll
               for (int r = 0; r < RPG; r++) {
                 const double cx = Lcx[lane + 64 * r];
@@ -918,7 +713,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
           }
         }
         if (!corrected) correction(std::true_type{});
-        tl_mark(need, 5);                  // (diag) correction applied: the 16 steps start
+        fl.tl_mark(need, 5);               // (diag) correction applied: the 16 steps start
         double sb = __shfl(Sown[0], ht, 64);     // S of SNP 0 (group 0) to every group
         // The 16 steps.  What one step costs is its dependent chain s -> x -> sigmoid -> delta (about 26 fp64 operations) --
         // provided nothing else sits on it.  Two things did (ISA of round 2: the ds_bpermute that fetches the next SNP's S from
@@ -935,7 +730,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
         aq_lds_double *wmu = wsel ? (aq_lds_double *)Lmu[par] + ht : wdum;
         aq_lds_double *wdel = wsel ? (aq_lds_double *)Ldel[par] + ht : wdum;
         if constexpr (MASK) {
-          signal(13, b - seg_b0 + 1);              // the single cross-block buffer is free for block b+1
+          fl.signal(AQ_FL_XBLOCK_READ, b - seg_b0 + 1);   // the single cross-block buffer is free for block b+1
           // ---- the same chain with the trait's own diagonal block (lower triangle in LGk) and per-entry sig2_beta_vb
           // (src/coreLoop.cpp:115-133): coef, K and cA come per entry from the helper
           const double *LGk = &LGk2[par][0];
@@ -1017,10 +812,10 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
           wmu[j * NTR] = mu;
           wdel[j * NTR] = dl;
           m1o = m1o_n; cA = cA_n; dj = d_n;
-          if (j == 7) tl_mark(need, 6);    // (diag) half of the steps
+          if (j == 7) fl.tl_mark(need, 6);   // (diag) half of the steps
         }
         }
-        signal(6, b - seg_b0 + 1);   // delta, gam, mu of block b are in LDS
+        fl.signal(AQ_FL_REC_DONE, b - seg_b0 + 1);   // delta, gam, mu of block b are in LDS
       };
       if constexpr (NT3 > 0) {
         // chain for block b0 + i - 1, then this wave's share of the matrix work of phase i
@@ -1299,7 +1094,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
 #endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the Gram blocks have landed
 #ifdef AQ_DIAG_TIME
-        dg_wait += __builtin_readcyclecounter() - t_dma;   // (shows up as the helper's "waiting on matrix/recurrence")
+        fl.dg_wait += __builtin_readcyclecounter() - t_dma;   // (shows up as the helper's "waiting on matrix/recurrence")
 #endif
       } else {
 #pragma unroll
@@ -1365,11 +1160,11 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
     // chain of block b starts -- so the round trip through the shared cache level is off the recurrence wave's path
     auto exchange = [&](int b) __attribute__((always_inline)) {
       const int par = b & 1, kdone = b - seg_b0 + 1;
-      if constexpr (WIDE) tl_mark(kdone, 0);        // (diag) helper enters the exchange of block b
+      if constexpr (WIDE) fl.tl_mark(kdone, 0);     // (diag) helper enters the exchange of block b
 #pragma unroll
-      for (int m = 0; m < NWM; m++) wait_ge(m, kdone);
-      if constexpr (NT3 > 0) wait_ge(11, kdone);   // the recurrence wave's own tiles
-      if constexpr (WIDE) tl_mark(kdone, 1);        // (diag) this part's S' of block b is complete
+      for (int m = 0; m < NWM; m++) fl.wait_ge(aq_fl_matrix(m), kdone);
+      if constexpr (NT3 > 0) fl.wait_ge(AQ_FL_REC_TILES, kdone);   // the recurrence wave's own tiles
+      if constexpr (WIDE) fl.tl_mark(kdone, 1);     // (diag) this part's S' of block b is complete
       double own[RPG];
 #pragma unroll
       for (int r = 0; r < RPG; r++) {
@@ -1383,7 +1178,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
       else split_exchange(b, own, [] {});
 #pragma unroll
       for (int r = 0; r < RPG; r++) Stot[par][lane + 64 * r] = own[r];
-      signal(14, kdone);
+      fl.signal(AQ_FL_EXCHANGED, kdone);
     };
     if (a.mode == 1) {
       // init mode: R = Y - X beta.  This wave plays the recurrence's part: beta of block k goes where delta would (Ldel, by block
@@ -1393,8 +1188,8 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
         const int k = b - seg_b0, par = b & 1;
         if (k >= 2) {
 #pragma unroll
-          for (int m = 0; m < NWM; m++) wait_ge(m, k + 1);
-          if (NT3 > 0) wait_ge(11, k + 1);
+          for (int m = 0; m < NWM; m++) fl.wait_ge(aq_fl_matrix(m), k + 1);
+          if (NT3 > 0) fl.wait_ge(AQ_FL_REC_TILES, k + 1);
         }
 #pragma unroll
         for (int r = 0; r < RPG; r++) {
@@ -1411,7 +1206,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
             else cs2 += be * be;
           }
         }
-        signal(6, k + 1);
+        fl.signal(AQ_FL_REC_DONE, k + 1);
       }
     } else {
       // L2 warm-up of the X operand panels: the workgroups of an XCD walk through the SNP blocks nearly in step, and whichever
@@ -1457,12 +1252,12 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
         if constexpr (MASK) {
           // the Gram blocks of block b+1 go on their way as soon as the chain of block b has applied the cross blocks (which
           // also means that block b-1, the last reader of the other diagonal buffer, is through)
-          if (b >= seg_b0 && b + 1 < seg_b1) { wait_ge(13, b - seg_b0 + 1); stage_dma(b + 1, par ^ 1, b + 2); }
+          if (b >= seg_b0 && b + 1 < seg_b1) { fl.wait_ge(AQ_FL_XBLOCK_READ, b - seg_b0 + 1); stage_dma(b + 1, par ^ 1, b + 2); }
         }
         // block b-1 must be through the recurrence: its gam / mu are read here, and the parity buffers about to be
         // overwritten with block b+1 are the ones it read
         if (b > seg_b0) {
-          wait_ge(6, b - seg_b0);
+          fl.wait_ge(AQ_FL_REC_DONE, b - seg_b0);
           if constexpr (!MASK && !CXC) {
             // cross-block correction X_b'X_{b-1} delta_{b-1} of block b for the recurrence wave (a 16 x 16 by 16 x NTR product: 128
             // multiply-adds and 144 LDS reads per lane that would otherwise sit between "S' complete" and the first chain step)
@@ -1478,7 +1273,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
                 for (int i = 0; i < 16; i++) cx += gx[i] * dlp[i];
                 Lcx[lane + 64 * r] = cx;
               }
-              signal(12, b - seg_b0 + 1);
+              fl.signal(AQ_FL_CX_READY, b - seg_b0 + 1);
             }
           }
         }
@@ -1487,7 +1282,7 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
         if (b > seg_b0) finalize_block(b - 1, par ^ 1);
         if (b + 1 < seg_b1) {
           stage_block(b + 1, par ^ 1);
-          signal(7, b - seg_b0 + 2);
+          fl.signal(AQ_FL_STAGED, b - seg_b0 + 2);
           if constexpr (!SEG && TT == 1) { if (C > 1 && a.xhelper) exchange(b + 1); }
         }
         x_wait();
@@ -1504,9 +1299,9 @@ __global__ __launch_bounds__(8 * 64, 2) void aq_core_sweep_la_kernel(const AqCor
   }
 #ifdef AQ_DIAG_TIME
   if (lane == 0 && a.dbg) {
-    a.dbg[((size_t)blockIdx.x * 8 + w) * 3] = dg_wait;
-    a.dbg[((size_t)blockIdx.x * 8 + w) * 3 + 1] = dg_wait_b;
-    a.dbg[((size_t)blockIdx.x * 8 + w) * 3 + 2] = __builtin_readcyclecounter() - dg_t0;
+    a.dbg[((size_t)blockIdx.x * 8 + w) * 3] = fl.dg_wait;
+    a.dbg[((size_t)blockIdx.x * 8 + w) * 3 + 1] = fl.dg_wait_b;
+    a.dbg[((size_t)blockIdx.x * 8 + w) * 3 + 2] = __builtin_readcyclecounter() - fl.dg_t0;
   }
 #endif
   // ---- per-trait sums ----

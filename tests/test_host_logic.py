@@ -114,35 +114,71 @@ def test_list_dimension_checks():
         H.prepare_list_hyper_({"q_hyper": 4}, Yc, p, (2, 4), bool_rmvd_x)
 
 
-def test_operand_prefetch_protocol_is_consistent():
-    """The request / wait protocol of the look-ahead kernel's deeper operand prefetch (atlasqtl_amd/csrc/aq_core_sweep_la.h:
-    aq_req_index / aq_req_issued, D buffers per stream, tile k in buffer k % D, every wait = vmcnt(2 x requests issued after the
-    wanted one), loads complete in order), simulated on the host for every tile count and both depths over several phases:
-    every tile an MFMA consumes has returned by then and still sits in its buffer."""
-    def req_index(D, last, stream, k):
-        n = 0
-        for j in range(0, D - 1):
-            if stream == 0 and k == j:
+# the Python copy of aq_req_index / aq_req_issued (atlasqtl_amd/csrc/aq_la_req.h): the simulation below runs on it, and
+# test_operand_prefetch_python_copy_is_the_kernels_own holds it to what the header itself computes
+def req_index(D, last, stream, k):
+    n = 0
+    for j in range(0, D - 1):
+        if stream == 0 and k == j:
+            return n
+        n += 1
+        if j <= D - 3:
+            if stream == 1 and k == j:
                 return n
             n += 1
-            if j <= D - 3:
-                if stream == 1 and k == j:
-                    return n
-                n += 1
-        for t in range(0, last + 1):
-            if t + D - 1 <= last:
-                if stream == 0 and k == t + D - 1:
-                    return n
-                n += 1
-            if t + D - 2 <= last:
-                if stream == 1 and k == t + D - 2:
-                    return n
-                n += 1
-        return -1
+    for t in range(0, last + 1):
+        if t + D - 1 <= last:
+            if stream == 0 and k == t + D - 1:
+                return n
+            n += 1
+        if t + D - 2 <= last:
+            if stream == 1 and k == t + D - 2:
+                return n
+            n += 1
+    return -1
 
-    def req_issued(D, last, t):
-        return (D - 1) + (D - 2) + sum((s + D - 1 <= last) + (s + D - 2 <= last) for s in range(t + 1))
 
+def req_issued(D, last, t):
+    return (D - 1) + (D - 2) + sum((s + D - 1 <= last) + (s + D - 2 <= last) for s in range(t + 1))
+
+
+def test_operand_prefetch_python_copy_is_the_kernels_own(tmp_path):
+    """aq_la_req.h is plain C++: a program of a dozen lines (tests/tools/la_req_probe.cpp), built with the host compiler alone,
+    prints aq_req_index and aq_req_issued for every D in {2, 3, 4}, last in 0 .. 17, both streams and every tile; the Python
+    copy the protocol simulation runs on must say the same, value for value."""
+    import os
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++ on the path")
+    exe = tmp_path / "la_req_probe"
+    r = subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-I", os.path.join(root, "atlasqtl_amd", "csrc"),
+                        os.path.join(root, "tests", "tools", "la_req_probe.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got_index, got_issued = {}, {}
+    for ln in r.stdout.split("\n"):
+        f = ln.split()
+        if f and f[0] == "i":
+            got_index[tuple(int(v) for v in f[1:5])] = int(f[5])
+        elif f and f[0] == "n":
+            got_issued[tuple(int(v) for v in f[1:4])] = int(f[4])
+    want_index = {(D, last, st, k): req_index(D, last, st, k) for D in (2, 3, 4) for last in range(18) for st in (0, 1) for k in range(last + 1)}
+    want_issued = {(D, last, t): req_issued(D, last, t) for D in (2, 3, 4) for last in range(18) for t in range(last + 1)}
+    assert len(want_index) == 2 * 3 * 171 and len(want_issued) == 3 * 171
+    assert got_index == want_index
+    assert got_issued == want_issued
+
+
+def test_operand_prefetch_protocol_is_consistent():
+    """The request / wait protocol of the look-ahead kernel's deeper operand prefetch (atlasqtl_amd/csrc/aq_la_req.h:
+    aq_req_index / aq_req_issued, D buffers per stream, tile k in buffer k % D, every wait = vmcnt(2 x requests issued after the
+    wanted one), loads complete in order; the tile loop that issues and waits is `run` in aq_core_sweep_la.h), simulated on the
+    host for every tile count and both depths over several phases: every tile an MFMA consumes has returned by then and still
+    sits in its buffer."""
     def simulate(NTC, D, phases=4):
         last, queue, buf = NTC - 1, [], {}
 

@@ -140,3 +140,64 @@ def test_the_cis_modules_import_each_other_without_a_cycle():
         free = {m for m in graph if m not in done and graph[m] <= done}
         assert free, f"an import cycle among {sorted(set(graph) - done)}"
         done |= free
+
+
+# ---- the look-ahead sweep kernel: aq_core_sweep_la.h and the aq_la_*.h headers beside it ----
+
+def _la_sources():
+    src = {fn: s for fn, s in _sources(".h").items() if fn == "aq_core_sweep_la.h" or fn.startswith("aq_la_")}
+    assert {"aq_core_sweep_la.h", "aq_la_stream.h", "aq_la_req.h", "aq_la_flags.h", "aq_la_traits.h"} <= set(src)
+    return src
+
+
+def test_hand_off_counters_are_addressed_by_name():
+    """No call of signal( or wait_ge( -- plain or as a member of the counters' struct -- passes a number as the counter: the
+    names are aq_la_flags.h's."""
+    calls = 0
+    for fn, s in _la_sources().items():
+        for m in re.finditer(r"\b(?:signal|wait_ge)\s*\(\s*([^,)]*)", _without_comments(s)):
+            first = m.group(1).strip()
+            if re.match(r"AqLaFlag\s+\w+$", first):                  # the two definitions
+                continue
+            calls += 1
+            assert not first[:1].isdigit(), (fn, m.group(0))
+            assert "AQ_FL_" in first or "aq_fl_" in first, (fn, m.group(0))
+    assert calls >= 20
+    flags = _la_sources()["aq_la_flags.h"]
+    assert "static_assert" in flags and "alignof(AqLaFlagWords) == 16" in flags
+
+
+def test_asm_loads_and_exchange_atomics_stay_where_they_belong():
+    """The inline-asm load macros are defined in aq_la_stream.h alone and used only by the matrix and helper roles; a.Pbuf is
+    named only by the sample-split exchanges.  All three roles live in aq_core_sweep_la.h: taken out into headers of their
+    own they moved the register allocation of shipped instances (profiles/r06_la_split_isa.txt)."""
+    roles_file = "aq_core_sweep_la.h"
+    for fn, s in _sources().items():
+        code = _without_comments(s)
+        defines = set(re.findall(r"#\s*define\s+(AQ_LD2I|AQ_LD2|AQ_TOUCH)\b", code))
+        assert defines == ({"AQ_LD2", "AQ_LD2I", "AQ_TOUCH"} if fn == "aq_la_stream.h" else set()), fn
+        uses = re.findall(r"\b(?:AQ_LD2I|AQ_LD2|AQ_TOUCH)\s*\(", re.sub(r"#\s*define[^\n]*", "", code))
+        assert bool(uses) == (fn == roles_file), (fn, len(uses))
+        if fn in _la_sources():                                      # (the fallback kernel of aq_core_sweep_mis.h has a Pbuf of its own)
+            assert ("a.Pbuf" in code) == (fn == roles_file), fn
+    assert "asm volatile(\"global_load" not in _without_comments(_sources()[roles_file])
+
+
+def test_the_look_ahead_headers_include_each_other_without_a_cycle():
+    """The #include lines of aq_core_sweep_la.h and the aq_la_*.h headers, parsed: no cycle among them, and the kernel's header
+    reaches every one of them."""
+    src = _la_sources()
+    graph = {fn: {h for h in re.findall(r'^\s*#\s*include\s+"([^"]+)"', s, flags=re.M) if h in src} for fn, s in src.items()}
+    done = set()
+    while len(done) < len(graph):                                 # peel off the headers whose includes are all peeled off
+        free = {h for h in graph if h not in done and graph[h] <= done}
+        assert free, f"an include cycle among {sorted(set(graph) - done)}"
+        done |= free
+    reach, todo = set(), ["aq_core_sweep_la.h"]
+    while todo:
+        for h in graph[todo.pop()]:
+            if h not in reach:
+                reach.add(h)
+                todo.append(h)
+    assert reach == set(src) - {"aq_core_sweep_la.h"}
+    assert graph["aq_la_req.h"] == set() and "hip" not in _without_comments(src["aq_la_req.h"])      # plain C++: a host program includes it

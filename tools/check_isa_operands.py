@@ -1,4 +1,5 @@
-"""Build-time proof obligation for the hand-issued vector-memory loads of aq_core_sweep_la.h.
+"""Build-time proof obligation for the hand-issued vector-memory loads of the look-ahead sweep kernel (aq_core_sweep_la.h, which
+issues them through the macros of aq_la_stream.h).
 
 The X operand stream (AQ_LD2 / AQ_LD2I) and the L2 warm-up touches are requested by inline-asm `global_load_*` whose destination
 VGPRs are written when the data RETURNS -- long after the asm statement that names them as outputs, which the compiler cannot
